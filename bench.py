@@ -13,6 +13,7 @@ shared t, y; jittered hyperparameters, seed 1000 + id) of the N=1e6, J=30 (W=60)
 Ranks are independent (no data-path collective): weak scaling; value = total evals/s.
 
 Launch:  python bench.py [--gpus N --steps K --warmup W]        (N > 1: spawns its N ranks itself)
+         python bench.py ... --dump-outputs DIR    (also writes the last timed step's log-likelihoods, .npy)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0: the headline metric with ``roofline`` and ``cpu_baseline``; at
 N = 1 also ``exact_rows`` (the same workload with exact generator rows), ``parity`` (a gate over
@@ -77,7 +78,16 @@ def parse():
                          "record uses 1.0 = BASELINE.json's sizes)")
     ap.add_argument("--no-strong", action="store_true",
                     help="--gpus N > 1: skip the strong-scaling legs (cfg3 / cfg4 partitioned over the ranks)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the (evals,) float64 "
+                         "log-likelihoods) to DIR/log_likelihood.npy (rank r > 0: log_likelihood_rank<r>.npy); "
+                         "the inputs depend on the arguments only, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # -------------------------------------------------------------------------------------------------
@@ -412,6 +422,12 @@ def main():
         elapsed = float(tmax.item())
     timed_events = list(eng.factor_events)
     timed_period = int(eng.generator_period)
+    if args.dump_outputs:
+        # the last timed step's values as its caller reads them (after the accuracy guard's reruns)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "log_likelihood.npy" if rank == 0 else f"log_likelihood_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name),
+                outs[nsteps - 1].detach().cpu().numpy().astype(np.float64))
 
     # the same workload with exact generator rows (period 1), one step, for the record
     exact = None

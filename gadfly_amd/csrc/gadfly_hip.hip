@@ -1112,6 +1112,10 @@ k_factor3(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     }
     if (fail) {
         if (lane == 0) info[b] = fail;
+        if (zero_start) {                           // an output-only slot is never left stale: the combines read
+            for (int i = 0; i < 64; ++i) { if (fl) Fg[i] = 0.0; else Sg[i] = 0.0; }   // its padding as zeros
+            if (fl) for (int i = 0; i < 64; ++i) Sg[i] = 0.0;
+        }
         return;
     }
     wave_lds_fence();
@@ -1369,6 +1373,14 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     }
     if (fail) {
         if (lane == 0) info[b] = fail;
+        if (zero_start) {                           // an output-only slot is never left stale: the combines read
+            for (int m = 0; m < 32; ++m) {          // its padding as zeros (a failed chunk's state means nothing)
+                col0[4 * (m >> 1) + (m & 1)] = 0.0;
+                col1[4 * (m >> 1) + (m & 1)] = 0.0;
+            }
+            if (f31)
+                for (int m = 0; m < 32; ++m) Sg[63 * 64 + 2 * g + 4 * (m >> 1) + (m & 1)] = 0.0;
+        }
         return;
     }
     wave_lds_fence();

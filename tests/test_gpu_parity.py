@@ -739,3 +739,27 @@ def test_time_parallel_reports_first_failing_pivot(hip):
     gp = gadfly_amd.GaussianProcess(k)
     with pytest.raises(gadfly_amd.LinAlgError, match="pivot 5001 "):
         gp.compute(t, diag=bad)
+
+
+@pytest.mark.parametrize("variant", ["tiled", "column"])
+def test_time_parallel_failed_chunk_leaves_no_stale_state(hip, variant):
+    """A chunk whose nominal pass fails leaves its state slot cleared, as a successful one leaves its padding:
+    the combines read a slot's padding as zeros, so whatever a recycled buffer held before (NaN here) must not
+    reach the first failing chunk's final pass and move the reported pivot (the test above, made independent
+    of what the caching allocator hands out)."""
+    from gadfly_amd import _lib
+    from gadfly_amd.engine import StreamingBatch
+    prob = util.solar_problem(6, 12000)
+    k, t, y = prob["kernel"], prob["t"], prob["y"]
+    bad = prob["diag_user"].copy()
+    bad[5000:] = -2.0 * k.get_value(np.zeros(1))[0]          # first non-positive pivot: row 5001 (test above)
+    eng = StreamingBatch([k.get_device_coefficients()], t, y, diag=bad, tile_rows=1024)
+    eng.sweep_variant = {"tiled": _lib.GF_SWEEP_TILED, "column": _lib.GF_SWEEP_COLUMN}[variant]
+    for L in (256, 1024, 4096):             # tree combine (47 chunks), sequential combine (12 and 3 chunks)
+        eng.log_likelihood_time_parallel(chunk_len=L)         # allocates this chunking's slots
+        slots = [eng._tp["S"], eng._tp["F"]] + ([eng._tp["tree"]["X"], eng._tp["tree"]["Y"]]
+                                                 if "tree" in eng._tp else [])
+        for x in slots:
+            x.fill_(float("nan"))
+        ll = eng.log_likelihood_time_parallel(chunk_len=L).cpu().numpy()
+        assert ll[0] == -np.inf and int(eng.info[0]) == 5001, (L, int(eng.info[0]))
