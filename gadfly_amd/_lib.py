@@ -23,6 +23,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
 GF_SWEEP_AUTO, GF_SWEEP_COLUMN, GF_SWEEP_TILED = 0, 1, 2
 GF_SWEEP_ZERO_START = 0x100
+GF_SWEEP_LONG_SPAN = 0x200
 GF_MAX_WIDTH = 256
 
 _lib = None
@@ -44,6 +45,7 @@ SIGNATURES = {
     "gf_factor": (_int, [_int, _i64, _i64, _int, _int] + [_vp] * 4 + [_vp, _i64]
                   + [_vp] * 6 + [_vp]),
     "gf_scaled_supported": (_int, [_int]),
+    "gf_scaled_span": (_dbl, [_int]),
     "gf_scaled_wide_supported": (_int, [_int]),
     "gf_build_scaled": (_int, [_int, _i64, _i64, _int, _int, _int] + [_vp] * 8 + [_int]
                         + [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_vp]),

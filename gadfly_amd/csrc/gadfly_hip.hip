@@ -459,8 +459,14 @@ __global__ void __launch_bounds__(64 * NW) k_factor(const FactorArgs A) {
 // k_build2 writes u~, v~ (and E at reset rows); k_factor2 reads the row operands u~_i as
 // wave-uniform scalar loads (SGPR operands of v_fma_f64), so only w~ needs an LDS broadcast.
 // ------------------------------------------------------------------------------------
-// reset(n) = (n % block == 0) or cmax (t_n - t_{n-1}) > gap, with (block - 1) * gap <= 28
+// reset(n) = (n % block == 0) or cmax (t_n - t_{n-1}) > gap, with (block - 1) * gap = SC_SPAN: |log rho| <= SC_SPAN.
+// The streamed log-likelihood (gf_loglike_fused with GF_SWEEP_LONG_SPAN, one-wave sweeps only) may take
+// SC_SPAN_LONG: T~ then stays within e^+-2 SC_SPAN_LONG = e^+-256 of S, u~ / v~ / w~ / F~ within e^+-128 of the
+// unscaled rows, far inside FP64's e^+-708 for amplitudes and pivots within 1e+-100 (the host falls
+// back to SC_SPAN outside that range).  Every other route -- the time-parallel sweeps, the stored factor, the wide
+// kernels -- keeps SC_SPAN: their transition and solve kernels rebuild the reset rows from it.
 constexpr double SC_SPAN = 28.0;
+constexpr double SC_SPAN_LONG = 128.0;
 
 struct Build2Args {
     int64_t N, n_first;
@@ -5295,6 +5301,8 @@ int gf_factor(int B, int64_t N, int64_t n_first, int W, int ld,
 
 int gf_scaled_supported(int W) { return (W >= 1 && W <= 64) ? 1 : 0; }
 
+double gf_scaled_span(int long_span) { return long_span ? SC_SPAN_LONG : SC_SPAN; }
+
 // widths the block-scaled build + multi-wave sweep (k_build2 + k_factor2w) take beyond one wave
 int gf_scaled_wide_supported(int W) { return (W > 64 && W <= 192) ? 1 : 0; }   // (beyond: register spills, gf_factor is faster)
 
@@ -5421,11 +5429,14 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
     if (!t || !y || !d || !z || !S_state || (!F_state && W <= 63) || !info || !diag_add || !cmax)
         return set_err("%s: null pointer", who);
     const int zero_start = (variant & GF_SWEEP_ZERO_START) ? (1 << 30) : 0;
-    variant &= ~GF_SWEEP_ZERO_START;
+    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
+    variant &= ~(GF_SWEEP_ZERO_START | GF_SWEEP_LONG_SPAN);
+    if (long_span && (W > 63 || nch > 1 || r_out || Ut_out || Wt_out || de_out))
+        return set_err("%s: GF_SWEEP_LONG_SPAN is for the streamed one-wave sweep only (W <= 63, one chunk, no row outputs)", who);
     if (check_sweep_options(who, gen_period, W > 63 ? GF_SWEEP_AUTO : variant, Jr, Jc)) return -1;
     if (chunk_count == 0) return 0;
     const bool tiled = sweep_tiled(variant, Jr, Jc);
-    const double gap = (block > 1) ? SC_SPAN / (double)(block - 1) : 0.0;
+    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;
     hipStream_t st = (hipStream_t)stream;
     if (W > 63) {                       // wide kernels: one workgroup per (problem, chunk), k_factorw
         FactorWArgs A;

@@ -34,6 +34,13 @@ def _on_device(method):
     return wrapper
 
 
+@functools.lru_cache(maxsize=None)
+def _scaled_span(long_span):
+    """Largest c_max * (t - t_reset) inside a scaling block, as the library defines it (short: every route;
+    long: the streamed one-wave sweep with GF_SWEEP_LONG_SPAN)."""
+    return float(_lib.load().gf_scaled_span(1 if long_span else 0))
+
+
 def _coeff_pack(coeffs_list):
     """list of B (ar, cr, ac, bc, cc, dc, shift) -> stacked float64 arrays."""
     Jr = len(coeffs_list[0][0])
@@ -530,7 +537,7 @@ class WideFactor:
         self.de = torch.empty((B * N + 8,), **f64)[:B * N].view(B, N)
         self.d = torch.empty((B * N + 8,), **f64)[:B * N].view(B, N)
         self.z = torch.empty((B * N + 8,), **f64)[:B * N].view(B, N)
-        real, comp, diag_add, c, cmax, block, _ = owner._pack
+        real, comp, diag_add, c, cmax, block, _ = owner._pack[:7]
         self.c, self.t = c, owner.t
         self.info = torch.zeros((B,), dtype=torch.int32, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -999,16 +1006,41 @@ class StreamingBatch:
         self.generator_period = self.period_for_condition(cond, target)
         return cond, self.generator_period
 
+    #: amplitudes (kernel coefficients, jitter) within 10^+-LONG_SPAN_AMPLITUDE let the streamed sweep take the
+    #: long scaling span; outside it every route keeps the short one
+    LONG_SPAN_AMPLITUDE = 100.0
+
+    @staticmethod
+    def _scaling_block(x, span):
+        """Rows between forced resets of the scaled coordinates: the largest power of two <= 64 with
+        (block - 1) * x <= span, x = 1.5 * cmax * cadence (see k_build2)."""
+        block = 64
+        while block > 1 and (block - 1) * x > span:
+            block //= 2
+        return block
+
+    def _long_span_ok(self, real, comp, diag_add):
+        """The streamed one-wave sweep may take the long span: W <= 63 and every nonzero amplitude within
+        10^+-LONG_SPAN_AMPLITUDE (the exponent-range argument of DESIGN.md 3.1)."""
+        if self.W > 63:
+            return False
+        amp = np.abs(np.concatenate([np.ravel(real[0]), np.ravel(comp[0]), np.ravel(comp[1]), np.ravel(diag_add)]))
+        amp = amp[amp != 0.0]
+        if not np.all(np.isfinite(amp)):
+            return False
+        lim = 10.0 ** self.LONG_SPAN_AMPLITUDE
+        return amp.size == 0 or (float(amp.min()) >= 1.0 / lim and float(amp.max()) <= lim)
+
     def _make_pack(self, real, comp, diag_add, c):
         dev = self._dev
         cmax = np.max(c, axis=1)
         dmax = float(np.max(np.abs(comp[3]))) if comp.size else 0.0
-        # rows between forced resets of the scaled coordinates: largest power of two with
-        # 1.5 * (block - 1) * cmax * cadence <= 28 (see k_build2)
+        # rows between forced resets of the scaled coordinates (the spans come from the library: one place)
         x = 1.5 * float(np.max(cmax)) * max(getattr(self, "_dt_med", 0.0), 0.0)
-        block = 64
-        while block > 1 and (block - 1) * x > 28.0:
-            block //= 2
+        block = self._scaling_block(x, _scaled_span(False))
+        # the streamed log-likelihood's block (gf_loglike_fused): the long span where the amplitudes allow it,
+        # 0 = the short span and `block`
+        stream_block = self._scaling_block(x, _scaled_span(True)) if self._long_span_ok(real, comp, diag_add) else 0
         # ONE host-to-device copy for the five arrays (a chain of single evaluations pays every copy's latency
         # before its first kernel starts): views into one buffer, each starting on a 16-byte boundary
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (real, comp, diag_add, c, cmax)]
@@ -1021,7 +1053,7 @@ class StreamingBatch:
             host[o:o + a.size] = a.reshape(-1)
         buf = dev(host)
         real, comp, diag_add, c, cmax = (buf[o:o + a.size].view(a.shape) for a, o in zip(arrs, offs))
-        return real, comp, diag_add, c, cmax, block, dmax
+        return real, comp, diag_add, c, cmax, block, dmax, stream_block
 
     def pack_coefficients(self, coeffs_list):
         if len(coeffs_list) != self.B:
@@ -1044,7 +1076,7 @@ class StreamingBatch:
     def _build_tile(self, k, buf, stream):
         n0 = k * self.tile_rows
         rows = min(self.tile_rows, self.N - n0)
-        real, comp, diag_add, _, cmax, block, _ = self._pack
+        real, comp, diag_add, _, cmax, block, _ = self._pack[:7]
         p = _lib.ptr
         if self.scaled or self.scaled_wide:
             st = self.lib.gf_build_scaled(
@@ -1136,8 +1168,10 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         T, N, B = self.tile_rows, self.N, self.B
-        real, comp, diag_add, _, cmax, block, _ = self._pack
+        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack
         period, variant = int(self.generator_period), int(self.sweep_variant)
+        if stream_block:                    # the long scaling span (one-wave sweeps, amplitudes in range)
+            block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
         self.kernel_used = "fused-wide" if self.W > 63 else "fused"
         for k in range((N + T - 1) // T):
             n0 = k * T
@@ -1199,7 +1233,7 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         N, B = self.N, self.B
-        real, comp, diag_add, _, cmax, block, _ = self._pack
+        real, comp, diag_add, _, cmax, block, _ = self._pack[:7]
         chunk_len, nch = self._tp_chunking(chunk_len, store)
         opts = (int(self.generator_period), int(self.sweep_variant))
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -1309,7 +1343,7 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         N, B = self.N, self.B
-        real, comp, diag_add, _, cmax, block, _ = self._pack
+        real, comp, diag_add, _, cmax, block, _ = self._pack[:7]
         self._tp_generation = getattr(self, "_tp_generation", 0) + 1
         rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, 0, nch, self.Jr, self.Jc, block, *opts, *coeffs,
                                 p(diag_add), p(cmax), *tyd, p(w["d"]), p(w["z"]), p(w["r"]),
@@ -1457,7 +1491,7 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         B, N = self.B, self.N
-        real, comp, diag_add, c, cmax, block, _ = self._pack
+        real, comp, diag_add, c, cmax, block, _ = self._pack[:7]
         L, nch = self._wide_chunking(chunk_len)
         keep = stores is not None and nch > 1
         ws = self._wide_ws(L, nch, keep=stores is not None)

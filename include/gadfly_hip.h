@@ -55,6 +55,10 @@ extern "C" {
 /* OR-ed into gf_chunk_sweep's `variant`: every chunk of the call starts from a ZERO state (a nominal pass);
  * the S_state / F_state slots are then outputs only and need not be initialised. */
 #define GF_SWEEP_ZERO_START 0x100
+/* OR-ed into gf_loglike_fused's `variant` (W <= 63 only): the block-scaled coordinates may span
+ * gf_scaled_span(1) instead of gf_scaled_span(0) in c_max * (t - t_reset) -- fewer reset rows at the same `block`
+ * rule, or a longer `block`.  Safe for amplitudes and pivots within 1e+-100. */
+#define GF_SWEEP_LONG_SPAN 0x200
 
 int gf_version(void);
 const char *gf_last_error(void);
@@ -124,6 +128,9 @@ int gf_factor(int B, int64_t N, int64_t n_first, int W, int ld,
  *   two rows (elements) past the last row of the last problem.
  */
 int gf_scaled_supported(int W);
+/* Largest c_max * (t_n - t_reset) inside a scaling block: the block rule of every route is
+ * 1.5 * (block - 1) * c_max * cadence <= gf_scaled_span(0); with GF_SWEEP_LONG_SPAN, gf_scaled_span(1). */
+double gf_scaled_span(int long_span);
 int gf_scaled_wide_supported(int W);
 int gf_build_scaled(int B, int64_t N, int64_t n_first, int Jr, int Jc, int ld,
                     const double *ar, const double *cr, const double *ac,

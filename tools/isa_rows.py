@@ -1,0 +1,133 @@
+"""Instruction counts of a kernel's basic blocks in the gfx950 ISA, compiled on the host (no GPU).
+
+    python tools/isa_rows.py                       # k_factor7<60, false>: compile gadfly_hip.hip and count
+    python tools/isa_rows.py --asm out.s           # count an existing `hipcc --cuda-device-only -S` listing
+    python tools/isa_rows.py --kernel k_factor7 --rows 40 --rowstore
+
+Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
+most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
+Blocks that hold an exponential or a sincos (fm_exp / fm_sincos end in v_ldexp_f64) are marked `exp`: the reset
+row's decay and the generator's anchors.  VALU counts every v_* opcode
+(v_readlane / v_readfirstlane / v_permlane* included, as SQ_INSTS_VALU counts them); LDS counts ds_*, `spill`
+scratch_* (register spills), `mov64` 64-bit register copies, `movb32` 32-bit moves.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "gadfly_amd", "csrc", "gadfly_hip.hip")
+
+
+def compile_asm(out):
+    cmd = ["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", out, SRC]
+    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+
+
+def kernel_body(lines, kernel, rows, rowstore):
+    # mangled: ..._19k_factor7ILi60ELb0EEEv...  (template <int ROWS, bool ROWSTORE>)
+    tag = f"{len(kernel)}{kernel}ILi{rows}E" + (f"Lb{int(rowstore)}E" if rowstore is not None else "")
+    start = None
+    for i, ln in enumerate(lines):
+        if start is None and re.match(r"^_Z\S+:", ln) and tag in ln.split(":")[0]:
+            start = i
+        elif start is not None and ln.startswith(".Lfunc_end"):
+            return lines[start:i]
+    raise SystemExit(f"kernel {kernel}<{rows}> not found in the listing")
+
+
+def blocks(body):
+    """Basic blocks in listing order: name, instruction opcodes, branch targets."""
+    out, cur = [], {"name": "entry", "ins": [], "targets": []}
+    out.append(cur)
+    for ln in body:
+        s = ln.strip()
+        m = re.match(r"^(\.LBB\d+_\d+|; %bb\.\d+):?", s) if not ln.startswith("\t") else None
+        if m:
+            cur = {"name": m.group(1).lstrip("; "), "ins": [], "targets": []}
+            out.append(cur)
+            continue
+        if not s or s.startswith(";") or s.startswith("."):
+            continue
+        op = s.split()[0]
+        cur["ins"].append(op)
+        if op.startswith("s_cbranch") or op == "s_branch":
+            cur["targets"].append(s.split()[1])
+    return out
+
+
+def row_loop(bl, reg):
+    """Smallest [header, latch] range of blocks closed by a backward branch that contains block `reg`."""
+    idx = {b["name"]: i for i, b in enumerate(bl)}
+    best = None
+    for j, b in enumerate(bl):
+        for tgt in b["targets"]:
+            i = idx.get(tgt)
+            if i is not None and i <= reg <= j and (best is None or j - i < best[1] - best[0]):
+                best = (i, j)
+    return best
+
+
+def counts(ins):
+    c = {"valu": 0, "fma": 0, "lds": 0, "salu": 0, "mov64": 0, "movb32": 0, "ldexp": 0, "branch": 0, "scratch": 0}
+    for op in ins:
+        if op.startswith("v_"):
+            c["valu"] += 1
+            c["fma"] += op.startswith(("v_fma_f64", "v_fmac_f64"))
+            c["mov64"] += op in ("v_mov_b64", "v_mov_b64_e32", "v_pk_mov_b32", "v_lshl_add_u64")
+            c["movb32"] += op.startswith("v_mov_b32")
+            c["ldexp"] += op.startswith("v_ldexp_f64")
+        elif op.startswith("ds_"):
+            c["lds"] += 1
+        elif op.startswith("scratch_"):
+            c["scratch"] += 1
+        elif op.startswith("s_cbranch") or op == "s_branch":
+            c["branch"] += 1
+        elif op.startswith("s_"):
+            c["salu"] += 1
+    return c
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--asm", help="existing device assembly listing (default: compile gadfly_hip.hip)")
+    ap.add_argument("--kernel", default="k_factor7")
+    ap.add_argument("--rows", type=int, default=60)
+    ap.add_argument("--rowstore", action="store_true", help="the ROWSTORE = true instance (k_factor7 only)")
+    ap.add_argument("--all", action="store_true", help="also print blocks outside loops")
+    a = ap.parse_args()
+    asm = a.asm
+    if asm is None:
+        asm = os.path.join(tempfile.mkdtemp(prefix="isa_rows_"), "gadfly_hip.s")
+        compile_asm(asm)
+    lines = open(asm).read().splitlines()
+    rowstore = (a.rowstore if a.kernel == "k_factor7" else None)
+    body = kernel_body(lines, a.kernel, a.rows, rowstore)
+    bl = blocks(body)
+    vgpr = next((ln.split(",")[-1].strip() for ln in lines
+                 if ".num_vgpr," in ln and f"{a.kernel}ILi{a.rows}E" in ln
+                 and (rowstore is None or f"Lb{int(rowstore)}E" in ln)), "?")
+    total = counts([op for b in bl for op in b["ins"]])
+    print(f"{a.kernel}<{a.rows}{'' if rowstore is None else ', ' + str(rowstore).lower()}>: {len(bl)} blocks, "
+          f"{total['valu']} VALU, {total['lds']} LDS, {total['scratch']} scratch (spill) in all; {vgpr} VGPRs")
+    reg = max(range(len(bl)), key=lambda i: counts(bl[i]["ins"])["fma"])
+    i0, i1 = row_loop(bl, reg) if not a.all else (0, len(bl) - 1)
+    print(f"row loop: blocks {bl[i0]['name']} .. {bl[i1]['name']}; `regular` = the block with the mat-vec's FMAs, "
+          f"`exp` = a block holding fm_exp / fm_sincos (v_ldexp_f64)")
+    print(f"{'block':>14} {'VALU':>5} {'fma':>4} {'LDS':>4} {'SALU':>5} {'br':>3} {'mov64':>5} {'movb32':>6} {'spill':>5}  role")
+    for k in range(i0, i1 + 1):
+        b = bl[k]
+        if not b["ins"]:
+            continue
+        c = counts(b["ins"])
+        role = "regular" if k == reg else ("exp" if c["ldexp"] else "")
+        print(f"{b['name']:>14} {c['valu']:5d} {c['fma']:4d} {c['lds']:4d} {c['salu']:5d} {c['branch']:3d} "
+              f"{c['mov64']:5d} {c['movb32']:6d} {c['scratch']:5d}  {role}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
