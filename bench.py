@@ -14,11 +14,14 @@ Ranks are independent (no data-path collective): weak scaling; value = total eva
 
 Launch:  python bench.py [--gpus N --steps K --warmup W]        (N > 1: spawns its N ranks itself)
          python bench.py ... --dump-outputs DIR    (also writes the last timed step's log-likelihoods, .npy)
+         python bench.py ... --full                (also every leg beyond the headline, below)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
-Prints ONE JSON line on rank 0: the headline metric with ``roofline`` and ``cpu_baseline``; at
-N = 1 also ``exact_rows`` (the same workload with exact generator rows), ``parity`` (a gate over
-several timed evaluations) and ``configs`` (BASELINE.json's other configurations, each with a
-sampled oracle check) -- all measured by this run.
+Prints ONE JSON line on rank 0: the headline metric with ``roofline`` (from the HIP events of the
+timed steps themselves).  A plain run does nothing else: set-up, warm-up, the timed steps, the dump.
+With ``--full`` the line also carries, at N = 1, ``cpu_baseline``, ``exact_rows`` (the same
+workload with exact generator rows), ``parity`` (a gate over several timed evaluations),
+``configs`` (BASELINE.json's other configurations, each with a sampled oracle check) and
+``single_chain``; at N > 1 ``configs`` holds the strong-scaling legs -- all measured by that run.
 """
 import argparse
 import json
@@ -62,22 +65,28 @@ def parse():
                          "(1 = exact rows ... 64 = at the scaling-block resets only); 0 = chosen "
                          "after the warm-up from the measured conditioning so that the generator's "
                          "share of the log-likelihood error stays below 1e-9 (DESIGN.md 2.1a)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs it does not need: the step with exact generator "
+                         "rows, the oracle legs (cpu_baseline, parity gate, config checks), BASELINE.json's other "
+                         "configurations and, at --gpus N > 1, the strong-scaling legs (the --no-* options below "
+                         "drop single legs of a full run)")
     ap.add_argument("--gate", type=int, default=8,
-                    help="timed evaluations checked against the oracle (N = 1 only)")
+                    help="timed evaluations checked against the oracle (--full, N = 1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the oracle legs (cpu_baseline, parity gate, config checks)")
+                    help="--full: skip the oracle legs (cpu_baseline, parity gate, config checks)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip BASELINE.json's other configurations (cfg2 predict, cfg3, cfg4, cfg5)")
+                    help="--full: skip BASELINE.json's other configurations (cfg2 predict, cfg3, cfg4, cfg5) "
+                         "and the strong-scaling legs")
     ap.add_argument("--no-exact-rows", action="store_true",
-                    help="skip the extra step with exact generator rows (period 1)")
+                    help="--full: skip the extra step with exact generator rows (period 1)")
     ap.add_argument("--cpu-threads", type=int, default=0,
-                    help="host threads of the all-cores CPU baseline (0 = every core this process may use, "
+                    help="--full: host threads of the all-cores CPU baseline (0 = every core this process may use, "
                          "at most 64: an evaluation holds 1.5 GB)")
     ap.add_argument("--strong-rows-scale", type=float, default=1.0,
                     help="scale the series length of the strong-scaling legs (rehearsals on one GPU; the "
                          "record uses 1.0 = BASELINE.json's sizes)")
     ap.add_argument("--no-strong", action="store_true",
-                    help="--gpus N > 1: skip the strong-scaling legs (cfg3 / cfg4 partitioned over the ranks)")
+                    help="--full, --gpus N > 1: skip the strong-scaling legs (cfg3 / cfg4 partitioned over the ranks)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (the (evals,) float64 "
                          "log-likelihoods) to DIR/log_likelihood.npy (rank r > 0: log_likelihood_rank<r>.npy); "
@@ -155,6 +164,20 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return n, how
+
+
+def walker_proposals(base, seeds, frac=0.10):
+    """(S0, w0, Q), each (len(seeds), J): the hyperparameters ``jitter_hyperparameters(base, seed, frac)``
+    gives for every seed, value for value (the same generator and draws -- one call of 3 J uniforms is the
+    J calls of 3 --, the same products and floor), without a Hyperparameters list per walker: 2048 of those
+    cost ~0.4 s per step of set-up."""
+    h = {k: np.array([p["hyperparameters"][k] for p in base], dtype=np.float64) for k in ("S0", "w0", "Q")}
+    lo, hi = np.log1p(-frac), np.log1p(frac)
+    u = np.empty((len(seeds), len(base), 3))
+    for i, seed in enumerate(seeds):
+        u[i] = np.random.Generator(np.random.PCG64(seed)).uniform(lo, hi, size=(len(base), 3))
+    f = np.exp(u)
+    return h["S0"] * f[..., 0], h["w0"] * f[..., 1], np.maximum(h["Q"] * f[..., 2], 0.5)
 
 
 def celerite2_loglike(hp, delta, t, yerr, y):
@@ -368,19 +391,18 @@ def main():
     delta = first[0].delta                           # the kernels' exposure in 1/uHz
 
     def proposals(step):
-        hps = [jitter_hyperparameters(base, 1000 + i) for i in walker_ids(step)]
-        return tuple(np.array([[p["hyperparameters"][k] for p in hp] for hp in hps])
-                     for k in ("S0", "w0", "Q"))
+        return walker_proposals(base, [1000 + i for i in walker_ids(step)])
 
-    extra = 0 if (args.no_exact_rows or world > 1) else 1      # one more step with exact rows
+    extra = 0 if (not args.full or args.no_exact_rows or world > 1) else 1      # one more step with exact rows
     params = [proposals(s) for s in range(nsteps + extra)]
     eng = ev.engine
-    ref_pack, vec_pack = ev.pack(first), ev.pack_parameters(*params[0], delta)
-    for a, b in zip(ref_pack[:5], vec_pack[:5]):        # same numbers as the per-object path
-        a = a if isinstance(a, (tuple, list)) else (a,)
-        b = b if isinstance(b, (tuple, list)) else (b,)
-        if not all(bool(torch.equal(x, y_)) for x, y_ in zip(a, b)):
-            raise SystemExit("vectorised coefficient pack differs from the per-kernel path")
+    if args.full:
+        ref_pack, vec_pack = ev.pack(first), ev.pack_parameters(*params[0], delta)
+        for a, b in zip(ref_pack[:5], vec_pack[:5]):        # same numbers as the per-object path
+            a = a if isinstance(a, (tuple, list)) else (a,)
+            b = b if isinstance(b, (tuple, list)) else (b,)
+            if not all(bool(torch.equal(x, y_)) for x, y_ in zip(a, b)):
+                raise SystemExit("vectorised coefficient pack differs from the per-kernel path")
     del first
     eng.sweep_variant = {"auto": _lib.GF_SWEEP_AUTO, "column": _lib.GF_SWEEP_COLUMN,
                          "tiled": _lib.GF_SWEEP_TILED}[args.kernel]
@@ -528,7 +550,7 @@ def main():
         }
         if exact is not None:
             result["exact_rows"] = exact
-        oracle_ok = not args.no_cpu_baseline and world == 1
+        oracle_ok = args.full and not args.no_cpu_baseline and world == 1
         if oracle_ok:
             usable, how = host_cores()
             threads = args.cpu_threads or min(usable, 64)
@@ -587,7 +609,7 @@ def main():
             if any(infos) or info1[0] or max(rels) > 1e-8 or \
                     result["parity"]["loglike_rel_err_first_timed"] > 1e-8:
                 raise SystemExit(f"parity gate failed: {result['parity']}")
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             del ev, eng, outs, mind
             torch.cuda.empty_cache()
             result["configs"] = other_configs(check=oracle_ok)
@@ -605,7 +627,7 @@ def main():
                                  "ms_per_eval": api["evaluator_b1_ms"]},
             }
     # ---- strong scaling of the sharded configurations (every rank takes part: collectives) ----------
-    if dist is not None and world > 1 and not args.no_strong and not args.no_configs:
+    if dist is not None and world > 1 and args.full and not args.no_strong and not args.no_configs:
         try:
             del ev, eng, outs, mind
         except NameError:

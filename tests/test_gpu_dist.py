@@ -84,7 +84,7 @@ def test_bench_self_launch_two_ranks(hip):
 
 
 def test_bench_strong_scaling_legs_two_ranks(hip):
-    """`bench.py --gpus 2`: after the weak-scaling headline every rank takes its block of cfg3's 256 light
+    """`bench.py --gpus 2 --full`: after the weak-scaling headline every rank takes its block of cfg3's 256 light
     curves and of cfg4's 512 walkers (static partition), evaluates it, and the results are all_gathered --
     the strong-scaling legs the driver's multi-GPU run records.  Two ranks share the box's one GPU here
     (gloo, short series); entry 0 of each batch is checked against the oracle by rank 0."""
@@ -92,7 +92,7 @@ def test_bench_strong_scaling_legs_two_ranks(hip):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(GADFLY_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--rows", "16384", "--evals", "64", "--strong-rows-scale", "0.05"]
+           "--rows", "16384", "--evals", "64", "--strong-rows-scale", "0.05", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Latency of the drop-in GaussianProcess API on BASELINE.json's single-series configs:
 cfg2 (N=1e6, J=30: compute, log_likelihood, predict) and cfg5 (N=5e5, J=30: sample(size=64)).
-(The CPU side of the comparison is bench.py's cpu_baseline leg.)"""
+(The CPU side of the comparison is the cpu_baseline leg of `bench.py --full`.)"""
 import os
 import sys
 import time

@@ -10,9 +10,9 @@ BASELINE.json's configurations beyond the headline, measured on ONE GPU (whole b
 
 Each function returns a dict of measured numbers (ms, units/s, algorithmic GB/s per SURVEY.md 8d and
 its fraction of the 8 TB/s HBM peak) plus a ``_sample``: the inputs and the GPU's answer for ONE
-entry, which bench.py checks against the oracle (this module never touches oracle/).
+entry, which `bench.py --full` checks against the oracle (this module never touches oracle/).
 
-Usage: python tools/configs.py           (prints the table; bench.py embeds the same numbers)
+Usage: python tools/configs.py           (prints the table; `bench.py --full` embeds the same numbers)
 """
 import os
 import sys

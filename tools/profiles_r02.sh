@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02
 rm -rf $O; mkdir -p $O
-echo "== bench" ; timeout -k 10 900 python3 $R/bench.py > $O/r02_bench.json 2> $O/bench.err; echo rc=$?
+echo "== bench" ; timeout -k 10 900 python3 $R/bench.py --full > $O/r02_bench.json 2> $O/bench.err; echo rc=$?
 echo "== rocprof bench"; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_prof -- python3 $R/bench.py --no-cpu-baseline --no-configs --no-exact-rows --generator-period 64 --steps 3 --warmup 1 > $O/bench_prof.log 2>&1
 cp $(find $O/bench_prof -name "*kernel_stats.csv" | head -1) $O/r02_bench_kernel_stats.csv
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -28,7 +28,7 @@ sq() {    # out kernel work script args... : the SQ counter groups, reduced per 
 }
 for w in $WHAT; do case $w in
 bench)
-  echo "== bench"; timeout -k 10 900 python3 $R/bench.py > $O/r03_bench.json 2> $O/bench.err; echo rc=$?
+  echo "== bench"; timeout -k 10 900 python3 $R/bench.py --full > $O/r03_bench.json 2> $O/bench.err; echo rc=$?
   prof bench bench.py --no-cpu-baseline --no-configs --no-exact-rows --generator-period 64 --steps 3 --warmup 1
   BA="bench.py --rows 131072 --evals 2048 --no-cpu-baseline --no-configs --no-exact-rows --steps 1 --warmup 0 --generator-period 64"
   f=$(pmc fetch FETCH_SIZE $BA); g=$(pmc write WRITE_SIZE $BA)
