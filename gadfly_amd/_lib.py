@@ -17,7 +17,8 @@ CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(CSRC, "libgadfly_hip.so")
 if os.environ.get("GADFLY_SO"):                 # another build of the same library (A/B measurements)
     SO_PATH = os.path.abspath(os.environ["GADFLY_SO"])
-SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dense.hip")]
+SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dense.hip"),
+           os.path.join(CSRC, "gadfly_ls.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -95,6 +96,9 @@ SIGNATURES = {
     "gf_interp_fill": (_int, [_i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp]),
     "gf_psd_power": (_int, [_int, _i64, _i64, _dbl, _vp, _vp, _vp]),
     "gf_psd_bin": (_int, [_int, _i64, _int, _vp, _vp, _vp, _dbl, _vp, _vp, _vp]),
+    "gf_ls_segments": (_int, [_i64]),
+    "gf_ls_work": (_i64, [_i64, _i64, _int]),
+    "gf_ls_power": (_int, [_int, _i64, _i64, _i64, _int, _int] + [_vp] * 8 + [_vp]),
     "gf_general_matmul_work": (_i64, [_int, _i64, _i64, _int]),
     "gf_general_matmul": (_int, [_int, _i64, _i64, _int, _int, _vp,
                                  _vp, _i64, _vp, _vp,

@@ -9,15 +9,22 @@ compared with ``kernel.get_psd``) and SURVEY.md 8f rank 3.  The transform is hip
 (psd.py:566-587) and ``gf_psd_bin`` the two binned statistics of ``bin_power_spectrum``
 (psd.py:186-300) for all series of a batch in one launch.  Frequencies are in uHz, power in
 ppm^2/uHz, sampling intervals in 1/uHz (= 1e6 s) -- gadfly's native units; astropy Quantities are
-accepted where astropy is installed.  Plotting and the Lomb-Scargle estimate (astropy.timeseries)
-stay with the reference.
+accepted where astropy is installed.
+
+``PowerSpectrum.from_lomb_scargle`` (and ``from_light_curve(..., method='lomb-scargle')``) is the
+reference's estimate for gapped, unevenly sampled photometry (psd.py:589-601, astropy's
+``LombScargle(normalization='psd')`` on ``rfftfreq``'s grid) without astropy: ``gf_ls_power``
+evaluates the floating-mean periodogram as the exact direct sum over every (point, frequency) pair
+in float64, for one series, an (R, N) batch or a ragged list in one call.  Where astropy would pick
+its approximate Press-Rybicki "fast" method (a regular grid of this size), this is the exact value
+of the quantity that method approximates.  Plotting stays with the reference.
 """
 import numpy as np
 
 from . import _lib
 from . import units as _units
 
-__all__ = ["PowerSpectrum", "bin_power_spectrum"]
+__all__ = ["PowerSpectrum", "bin_power_spectrum", "ls_grid"]
 
 
 def _value(x, unit_name):
@@ -55,6 +62,97 @@ def _bin_starts(axis, bins):
     on_edge = (axis >= edges[-1]) & (np.around(axis, decimal) == np.around(edges[-1], decimal))
     start[-1] += int(np.count_nonzero(on_edge))
     return edges, start
+
+
+def ls_grid(n, d):
+    """rfftfreq's frequency grid of an n-point series with step d [1/uHz]: (frequencies [uHz], df), bit for
+    bit ``np.fft.rfftfreq(n, d)`` (``k * (1.0 / (n * d))`` in float64); the device forms the same products."""
+    df = 1.0 / (n * d)
+    return np.arange(n // 2 + 1, dtype=np.int64) * df, df
+
+
+def _finite_1d(x, what):
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1 or len(x) < 2:
+        raise ValueError(f"{what} must be 1-D with at least 2 points (shape {x.shape})")
+    if not np.all(np.isfinite(x)):
+        raise ValueError(f"{what} holds NaN or Inf")
+    return x
+
+
+def _ls_d(t, d):
+    if d is None:
+        d = float(np.median(np.diff(t)))
+    d = float(_value(d, "1/uHz"))
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError(f"the sampling interval d must be finite and positive (d = {d})")
+    return d
+
+
+def _flux_rows(flux):
+    """flux as given (device tensors stay on the device), its shape."""
+    import torch
+    if torch.is_tensor(flux):
+        if flux.is_complex() or not flux.is_floating_point():
+            raise ValueError("flux must be a real floating-point array")
+        return flux, tuple(flux.shape)
+    f = np.asarray(_value(flux, "ppm"), dtype=np.float64)
+    if not np.all(np.isfinite(f)):
+        raise ValueError("flux holds NaN or Inf")
+    return f, f.shape
+
+
+def _ls_series(t, flux, d):
+    """Host-side validation and layout of from_lomb_scargle's inputs (no device call): a list of
+    (t_r [numpy], flux_r [numpy or tensor], d_r) and one of "single", "batch", "list"."""
+    if flux is None:
+        if not isinstance(t, (list, tuple)) or len(t) == 0:
+            raise ValueError("without `flux`, `t` must be a non-empty list of (t, flux) pairs")
+        out = []
+        for pair in t:
+            if len(pair) != 2:
+                raise ValueError("`t` must be a list of (t, flux) pairs")
+            tr = _finite_1d(_value(pair[0], "1/uHz"), "t")
+            fr, shape = _flux_rows(pair[1])
+            if shape != tr.shape:
+                raise ValueError(f"t {tr.shape} and flux {shape} of a pair differ in shape")
+            out.append((tr, fr, _ls_d(tr, d)))
+        return out, "list"
+    t = np.asarray(_value(t, "1/uHz"), dtype=np.float64)
+    f, shape = _flux_rows(flux)
+    if len(shape) not in (1, 2) or shape[-1] < 2:
+        raise ValueError(f"flux must have shape (N,) or (R, N) with N >= 2 (shape {shape})")
+    if t.shape != shape and t.shape != shape[-1:]:
+        raise ValueError(f"t {t.shape} must have shape (N,) or that of flux {shape}")
+    if len(shape) == 1:
+        tr = _finite_1d(t, "t")
+        return [(tr, f, _ls_d(tr, d))], "single"
+    if shape[0] < 1:
+        raise ValueError("flux has no rows")
+    rows = [_finite_1d(t if t.ndim == 1 else t[r], "t") for r in range(shape[0])]
+    ds = [_ls_d(tr, d) for tr in rows]
+    if any(x != ds[0] for x in ds):
+        raise ValueError("the rows of t have different median steps: pass `d`, or a list of (t, flux) pairs")
+    return [(rows[r], f[r], ds[r]) for r in range(shape[0])], "batch"
+
+
+_LS_WORK_BUDGET = 1 << 27                  # doubles (1 GiB) of partial sums per launch
+
+
+def _ls_groups(lib, counts, outs):
+    """Consecutive runs of series [a, b) whose workspace fits the budget (at least one series each).  A
+    series' result does not depend on its group: its segment count is a function of its own length."""
+    groups, a = [], 0
+    while a < len(counts):
+        b, s_max = a + 1, lib.gf_ls_segments(int(counts[a]))
+        while b < len(counts):
+            s2 = max(s_max, lib.gf_ls_segments(int(counts[b])))
+            if lib.gf_ls_work(int(counts[a:b + 1].sum()), int(outs[a:b + 1].sum()), s2) > _LS_WORK_BUDGET:
+                break
+            b, s_max = b + 1, s2
+        groups.append((a, b))
+        a = b
+    return groups
 
 
 class PowerSpectrum:
@@ -145,26 +243,113 @@ class PowerSpectrum:
         return ps
 
     @classmethod
+    def from_lomb_scargle(cls, t, flux=None, d=None, include_zero_freq=False, name=None, device=None):
+        """Lomb-Scargle power spectrum of unevenly sampled (gapped) fluxes [ppm] at times ``t`` [1/uHz].
+
+        The reference's ``PowerSpectrum._lomb_scargle`` (psd.py:589-601): astropy's floating-mean
+        ``LombScargle(t, flux, normalization='psd').power(rfftfreq(N, d))`` times ``norm = d / sqrt(2 pi)``,
+        ``d`` the median time step unless given, the zero frequency dropped unless asked for
+        (psd.py:559-561).  Evaluated exactly (direct sum in float64) by ``gf_ls_power``; astropy's
+        ``method='auto'`` would use its approximate Press-Rybicki method on such a grid instead
+        (DESIGN.md 3.6).  Accepted shapes:
+
+        * ``t`` (N,), ``flux`` (N,)              -> one spectrum, power (M,)
+        * ``t`` (N,), ``flux`` (R, N)            -> power (R, M) on one frequency axis
+        * ``t`` (R, N), ``flux`` (R, N)          -> power (R, M); every row must have the same ``d``
+          (or ``d`` given), so that the rows share the frequency axis
+        * ``t`` a list of ``(t_r, flux_r)`` pairs (any lengths), ``flux`` None -> a list of spectra
+
+        ``flux`` may be a float64 tensor already on the device (e.g. a ``sample_device`` draw); the
+        result keeps the device copy of the power, so ``.bin()`` stays on the GPU.
+        """
+        import torch
+        series, layout = _ls_series(t, flux, d)
+        lib = _lib.load()
+        first = 0 if include_zero_freq else 1
+        dev = device
+        for _, y, _ in series:
+            if torch.is_tensor(y) and y.is_cuda:
+                dev = y.device
+                break
+        if dev is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = torch.device(dev)
+        grids = [ls_grid(len(tr), dr) for tr, _, dr in series]
+        norms = [dr / (2 * np.pi) ** 0.5 for _, _, dr in series]
+        counts = np.array([len(tr) for tr, _, _ in series], dtype=np.int64)
+        outs = counts // 2 + 1 - first
+        out_off = np.concatenate([[0], np.cumsum(outs)]).astype(np.int64)
+        with torch.cuda.device(dev):
+            ys = []
+            for _, y, _ in series:
+                yd = y.to(device=dev, dtype=torch.float64) if torch.is_tensor(y) else \
+                    torch.as_tensor(np.ascontiguousarray(y, dtype=np.float64), device=dev)
+                ys.append(yd.reshape(-1))
+            y_all = torch.cat(ys).contiguous()
+            if not bool(torch.isfinite(y_all).all()):
+                raise ValueError("flux holds NaN or Inf")
+            t_all = torch.as_tensor(np.concatenate([tr for tr, _, _ in series]), device=dev)
+            power = torch.empty(int(out_off[-1]), dtype=torch.float64, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            pt_all = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            for a, b in _ls_groups(lib, counts, outs):
+                n = counts[a:b]
+                pt = pt_all[a:b + 1] - pt_all[a]
+                oo = out_off[a:b + 1] - out_off[a]
+                s_max = max(lib.gf_ls_segments(int(x)) for x in n)
+                work = torch.empty(int(lib.gf_ls_work(int(pt[-1]), int(oo[-1]), s_max)) + 4,
+                                   dtype=torch.float64, device=dev)
+                w = work[(-work.data_ptr() // 8) % 4:]                     # 32-byte aligned
+                meta_i = torch.as_tensor(np.concatenate([pt, oo]), device=dev)
+                meta_d = torch.as_tensor(np.array([g[1] for g in grids[a:b]] + norms[a:b],
+                                                  dtype=np.float64), device=dev)
+                _lib.check(lib.gf_ls_power(
+                    b - a, int(n.max()), int(pt[-1]), int(oo[-1]), s_max, first,
+                    _lib.ptr(meta_i), _lib.ptr(meta_i[b - a + 1:]), _lib.ptr(meta_d),
+                    _lib.ptr(meta_d[b - a:]), _lib.ptr(t_all[int(pt_all[a]):]), _lib.ptr(y_all[int(pt_all[a]):]),
+                    _lib.ptr(w), _lib.ptr(power[int(out_off[a]):]), st), "gf_ls_power")
+            host = power.cpu().numpy()
+        spectra = []
+        for r in range(len(series)):
+            p_dev = power[int(out_off[r]):int(out_off[r + 1])].view(1, -1)
+            ps = cls(grids[r][0][first:], host[out_off[r]:out_off[r + 1]], name=name, norm=norms[r])
+            ps._power_dev = p_dev
+            spectra.append(ps)
+        if layout == "list":
+            return spectra
+        if layout == "single":
+            return spectra[0]
+        R, m = len(series), int(outs[0])
+        ps = cls(grids[0][0][first:], host.reshape(R, m), name=name, norm=norms[0])
+        ps._power_dev = power.view(R, m)
+        return ps
+
+    @classmethod
     def from_light_curve(cls, light_curve, method="fft", include_zero_freq=False, name=None,
                          detrend=False, **kwargs):
         """Power spectrum of a light-curve-like object (``.time`` [days or Time], ``.flux`` [ppm]).
 
-        Only the plain FFT estimate of an evenly sampled, already normalised light curve runs
-        here (reference psd.py:537-563, ``detrend=False`` branch); detrending / gap interpolation
-        (psd.py:474-535, lightkurve) and Lomb-Scargle (psd.py:589-601, astropy) are the
-        reference's.
+        The ``detrend=False`` branch of the reference (psd.py:537-563) on an already normalised
+        light curve: ``method='fft'`` for an evenly sampled one, ``method='lomb-scargle'`` (the
+        time axis ``jd * day`` in 1/uHz, see :meth:`from_lomb_scargle`) for a gapped one.
+        Detrending / gap interpolation (psd.py:474-535) needs lightkurve and stays with the
+        reference.
         """
         if method.lower() not in ("fft", "lomb-scargle"):
             raise ValueError(f'PowerSpectrum.from_lightcurve was given method="{method}", but it '
                              "must be one of: ['fft', 'lomb-scargle'].")
-        if method.lower() != "fft" or detrend:
+        if detrend:
             raise NotImplementedError(
-                "only method='fft' with detrend=False runs on the device; detrending and "
-                "Lomb-Scargle need lightkurve / astropy (reference psd.py:474-535, :589-601)")
+                "only detrend=False runs on the device; detrending needs lightkurve "
+                "(reference psd.py:474-535)")
         time = light_curve.time
         jd = np.asarray(getattr(time, "jd", time), dtype=np.float64)
-        d = np.median(np.diff(jd)) * 86400.0 / _units.SECONDS_PER_INVERSE_UHZ
         meta = getattr(light_curve, "meta", None) or {}
+        if method.lower() == "lomb-scargle":
+            t = jd * 86400.0 / _units.SECONDS_PER_INVERSE_UHZ
+            return cls.from_lomb_scargle(t, light_curve.flux, include_zero_freq=include_zero_freq,
+                                         name=meta.get("name", name))
+        d = np.median(np.diff(jd)) * 86400.0 / _units.SECONDS_PER_INVERSE_UHZ
         return cls.from_flux(light_curve.flux, d, include_zero_freq=include_zero_freq,
                              name=meta.get("name", name))
 

@@ -475,6 +475,26 @@ int gf_psd_bin(int R, int64_t M, int nb, const double *x, const double *power,
                const int64_t *start, double constant, double *stat, double *err, void *stream);
 
 /*
+ * Lomb-Scargle power spectra of R (gapped, unevenly sampled) series: replaces PowerSpectrum._lomb_scargle
+ * (gadfly/psd.py:589-601), i.e. astropy's LombScargle(t, y, normalization='psd').power(rfftfreq(n, d)) * norm
+ * with its defaults (no dy, fit_mean, center_data, nterms = 1), as the exact direct sum over every (point,
+ * frequency) pair -- not the Press-Rybicki approximation astropy's method='auto' picks for a regular grid.
+ * Series r holds the points pt_off[r] <= i < pt_off[r+1] of t, y (concatenated, [n_total], n_r >= 2) and its
+ * frequencies k df[r], first <= k <= n_r/2 (df = 1/(n_r d_r): rfftfreq's grid; first = 1 drops f = 0);
+ * power[out_off[r] + k - first] = P(k df[r]) * norm[r] (out_off[r+1] - out_off[r] = n_r/2 + 1 - first).
+ * pt_off, out_off [R+1] int64, df, norm [R] are device arrays; n_max = max n_r; S_max >= gf_ls_segments(n_max)
+ * (a series' own segment count depends on n_r alone, so its result does not depend on the batch around it);
+ * work: gf_ls_work(n_total, out_total, S_max) doubles, 32-byte aligned.  Degenerate frequencies (f = 0, the
+ * Nyquist frequency of an even, evenly sampled series, a constant series) take the rank-one or zero limit
+ * (DESIGN.md 3.6): no NaN or Inf reaches power.
+ */
+int gf_ls_segments(int64_t n);
+int64_t gf_ls_work(int64_t n_total, int64_t out_total, int S_max);
+int gf_ls_power(int R, int64_t n_max, int64_t n_total, int64_t out_total, int S_max, int first,
+                const int64_t *pt_off, const int64_t *out_off, const double *df, const double *norm,
+                const double *t, const double *y, double *work, double *power, void *stream);
+
+/*
  * Missing cadences of an evenly sampled light curve filled by linear interpolation: replaces
  * interpolate_missing_data (gadfly/interp.py:6-60; called at psd.py:495, :531 before every FFT).
  * t, f [N] ascending times and fluxes; cadences [N] int64 or NULL (then the cadence index of a
