@@ -5,47 +5,11 @@ test_gpu_parity.py; the seeds are fixed, so a failure is reproducible."""
 import numpy as np
 import pytest
 
+from tests.random_cases import (BKJD0, QMODE_PHASE, float64_limit, narrow_problem as _problem, relmax as _relmax,
+                                wmax)
+
 pytestmark = pytest.mark.gpu
 RTOL_LL, TOL_VEC = 1e-8, 1e-6
-
-
-def _relmax(x, ref):
-    return float(np.max(np.abs(np.asarray(x) - ref)) / max(float(np.max(np.abs(ref))), 1e-300))
-
-
-def _problem(seed):
-    from gadfly_amd.terms import SHOTerm, TermSum, TermConvolution
-    rng = np.random.Generator(np.random.PCG64(seed))
-    J = int(rng.integers(1, 31))
-    n_over = int(rng.integers(0, min(J, 3) + 1)) if rng.random() < 0.4 else 0
-    terms = []
-    for j in range(J):
-        w0 = float(np.exp(rng.uniform(np.log(0.5), np.log(3000.0))))
-        Q = float(rng.uniform(0.05, 0.45)) if j < n_over else float(np.exp(rng.uniform(np.log(0.5), np.log(300.0))))
-        S0 = float(np.exp(rng.uniform(-2, 4)))
-        terms.append(SHOTerm(S0=S0, w0=w0, Q=Q))
-    dt = float(np.exp(rng.uniform(np.log(2e-5), np.log(2e-3))))          # cadence in 1e6 s
-    N = int(rng.integers(40, 5000))
-    kind = rng.choice(["uniform", "jitter", "gaps", "clusters"])
-    t = np.arange(N) * dt
-    if kind == "jitter":
-        t = t + rng.uniform(-0.3, 0.3, N) * dt
-    elif kind == "gaps":
-        keep = np.ones(N, bool)
-        for _ in range(int(rng.integers(1, 4))):
-            a = int(rng.integers(0, N - 1)); keep[a:a + int(rng.integers(1, max(2, N // 8)))] = False
-        keep[0] = True
-        t = t[keep]
-    elif kind == "clusters":
-        t = np.sort(rng.uniform(0, N * dt, N))
-        t = np.unique(np.round(t / (dt * 1e-3)) * (dt * 1e-3))            # no exact duplicates
-    t = np.sort(t)
-    N = len(t)
-    kernel = TermConvolution(TermSum(*terms), float(rng.uniform(0.1, 1.0)) * dt)
-    yerr = 0.0 if rng.random() < 0.2 else float(np.exp(rng.uniform(-3, 2)))
-    amp = float(np.sqrt(kernel.get_value(np.zeros(1))[0]))
-    y = amp * rng.normal(size=N) + np.cumsum(rng.normal(size=N)) * 0.1 * amp
-    return dict(kernel=kernel, t=t, y=y, diag_user=np.full(N, yerr ** 2), rng=rng, kind=kind, J=J)
 
 
 @pytest.mark.parametrize("seed", range(100, 140))
@@ -203,3 +167,72 @@ def test_accuracy_guard_reruns_an_ill_conditioned_walker(hip):
     ev.engine.generator_period = 1
     exact = ev.evaluate_device(ev.pack(kernels2)).cpu().numpy()
     assert exact[3] == got[3]
+
+
+@pytest.mark.parametrize("seed", range(140, 172))
+def test_random_problem_at_the_product_period(hip, seed):
+    """test_random_problem's problems at the generator period the product itself picks (calibrate_generator:
+    period_for_condition of the measured condition, up to 64 -- not capped at 16), odd seeds on a BKJD axis
+    (phases beyond QMODE_PHASE: RowGen::qmode on).  Streamed sweep, three- and two-sweep time-parallel evaluation and
+    the stored factor's solves at that period against the oracle; the shared skip rule (random_cases.float64_limit).
+    Seeds 2 mod 4 sit on an axis that crosses QMODE_PHASE in the first tile or chunk."""
+    import torch
+    from gadfly_amd.engine import StreamingBatch
+    from oracle import cref
+    from tests.random_cases import oracle_problems
+    prob = _problem(seed)
+    k, t, y, du, rng = prob["kernel"], prob["t"], prob["y"], prob["diag_user"], prob["rng"]
+    co = k.get_device_coefficients()
+    axis = "bkjd" if seed % 2 else ("qcross" if seed % 4 == 2 else "zero")
+    if axis == "bkjd":
+        t = t + BKJD0
+    elif axis == "qcross":
+        # moved so that wmax * t crosses QMODE_PHASE between two of the first 31 rows (RowGen::init decides qmode
+        # from the first row of a tile or chunk: the rows after the crossing run without it)
+        r0 = min(30, len(t) // 2)
+        t = t + (QMODE_PHASE / wmax(co) - 0.5 * (t[r0 - 1] + t[r0]))
+        ph = wmax(co) * np.abs(t)
+        assert ph[0] < QMODE_PHASE < ph[r0]
+    N = len(t)
+    orc = oracle_problems([co], t, du, y)
+    ref, info = float(orc["ref"][0]), int(orc["info"][0])
+    tile = int(rng.choice([64, 128, 320, 1024, 8192]))
+    eng = StreamingBatch([co], t, y, diag=du, tile_rows=tile)
+    if info != 0:
+        assert float(eng.log_likelihood()[0]) == float("-inf") and int(eng.info[0]) == info
+        return
+    why = float64_limit([co], t, du, y, orc)
+    if why:
+        pytest.skip(why)
+    if axis != "qcross":
+        assert (eng._tmax > 2.0e5) == (axis == "bkjd")
+    eng.log_likelihood()
+    cond, per = eng.calibrate_generator()
+    cond_ref = float(orc["cond"][0])
+    # the streamed sweep's estimate is the oracle's condition; the period is never longer than it allows
+    assert abs(cond - cond_ref) <= 1e-6 * cond_ref and per == eng.period_for_condition(cond), (cond, cond_ref)
+    assert eng.generator_period == per <= eng.period_for_condition(cond_ref)
+    tag = (seed, prob["kind"], axis, prob["J"], N, tile, eng._pack[5], eng._fused_ok(), per, cond)
+    ll = float(eng.log_likelihood()[0])
+    assert int(eng.info[0]) == 0 and eng.generator_period == per, tag
+    assert abs(ll - ref) <= RTOL_LL * abs(ref), (tag, ll, ref)
+    if not eng._fused_ok():
+        return
+    assert eng.kernel_used == "fused"
+    L = int(rng.choice([64, 128, 256, 512])) * max(1, eng._pack[5] // 64)
+    for two in (False, True):
+        eng.two_sweep = two
+        ll_tp = float(eng.log_likelihood_time_parallel(chunk_len=L)[0])
+        assert eng._tp_used == (eng._tp_chunking(L)[1] > 1), tag
+        assert eng._two_sweep_used == (two and eng._tp_used), tag
+        assert abs(ll_tp - ref) <= RTOL_LL * abs(ref), (tag, L, two, ll_tp, ref)
+    eng.two_sweep = False
+    c, a, U, V = orc["mats"][0]
+    d_ref, W_ref = orc["d"][0], orc["W"][0]
+    Y = rng.normal(size=(N, 3))
+    Yd = torch.as_tensor(Y).cuda().reshape(1, N, 3)
+    fac = eng.stored_factor(chunk_len=L)
+    ai_ref = cref.solve_upper(t, c, U, W_ref, cref.solve_lower(t, c, U, W_ref, Y) / d_ref[:, None])
+    assert _relmax(fac.apply_inverse(Yd)[0].cpu().numpy(), ai_ref) < TOL_VEC, (tag, L)
+    dt_ref = cref.matmul_lower(t, c, U, W_ref, Y * np.sqrt(d_ref)[:, None])
+    assert _relmax(fac.dot_tril(Yd)[0].cpu().numpy(), dt_ref) < TOL_VEC, (tag, L)
