@@ -17,3 +17,11 @@ from .psd import PowerSpectrum, bin_power_spectrum  # noqa: F401
 from .interp import interpolate_missing_data, stitch_quarters  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # torch.autograd.Function over BatchedLogLikelihood.value_and_grad (gadfly_amd.grad); imported on first use
+    if name == "LogLikelihood":
+        from .grad import LogLikelihood
+        return LogLikelihood
+    raise AttributeError(f"module 'gadfly_amd' has no attribute {name!r}")

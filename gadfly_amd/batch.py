@@ -18,6 +18,7 @@ Batch shapes:
 """
 import numpy as np
 
+from . import _lib
 from .engine import StreamingBatch
 
 __all__ = ["BatchedLogLikelihood", "log_likelihood_batch", "sho_coefficient_pack"]
@@ -284,6 +285,73 @@ class BatchedLogLikelihood:
                            and all(_exposure_resolved(float(dl), self._dt_min, self._t_abs_max)
                                    for dl in np.atleast_1d(np.asarray(delta, dtype=np.float64))))
         return pk
+
+    #: cap on the gradient workspace of one call in bytes (:meth:`value_and_grad`): larger batches run in groups
+    grad_workspace_bytes = _lib.GF_GRAD_WORKSPACE_BYTES
+
+    def _host_pack(self, pack_or_kernels):
+        """Stacked host coefficients (Jr, Jc, real, comp, diag_add) of the batch's original term structure from a
+        list of kernels, a host pack (:func:`sho_coefficient_pack`, ``engine._coeff_pack``) or a device pack."""
+        x = pack_or_kernels
+        if isinstance(x, tuple) and len(x) >= 5 and isinstance(x[0], (int, np.integer)):
+            return int(x[0]), int(x[1]), np.asarray(x[2]), np.asarray(x[3]), np.asarray(x[4])
+        if isinstance(x, tuple):                       # a device pack (pack / pack_parameters)
+            if self.engine._complexified:
+                raise NotImplementedError("gradients of complexified (W > 63) packs are not supported")
+            Jr, Jc = self.engine._struct0
+            return (Jr, Jc, x[0].cpu().numpy(), x[1].cpu().numpy(), x[2].cpu().numpy())
+        from .engine import _coeff_pack
+        Jr, Jc, real, comp, diag_add, _ = _coeff_pack([k.get_device_coefficients() for k in x])
+        return Jr, Jc, real, comp, diag_add
+
+    def _grad_check_width(self):
+        from .grad import check_width
+        Jr, Jc = self.engine._struct0
+        check_width(Jr + 2 * Jc)
+
+    def value_and_grad_coefficients(self, pack_or_kernels):
+        """log-likelihoods and their gradients with respect to the celerite coefficients.
+        Returns ``(ll, grads)``: ll (B,) numpy (-inf where K is not positive definite, whose gradients are NaN);
+        grads in the engine's stacked layout: ``real`` (2, B, Jr) = d/d(a, c), ``comp`` (4, B, Jc) =
+        d/d(a, b, c, d), ``diag_add`` (B,) (also d/d of a constant added to the diagonal), ``mean`` (B,)."""
+        self._grad_check_width()
+        from .grad import coefficient_gradients
+        Jr, Jc, real, comp, diag_add = self._host_pack(pack_or_kernels)
+        res = coefficient_gradients(self.engine, Jr, Jc, real, comp, diag_add, self.grad_workspace_bytes)
+        #: (workspace bytes of a group, number of groups, problems per group) and the device time of the last call
+        self.last_grad_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self.last_grad_device_ms = res["device_ms"]
+        ll = res["ll"]
+        if self._pad_corr is not None:
+            ll = ll + self._pad_corr.cpu().numpy()       # ragged batch: the missing-data rows' constants
+        return ll, {k: res[k] for k in ("real", "comp", "diag_add", "mean")}
+
+    def value_and_grad(self, S0, w0, Q, delta, wrt=("S0", "w0", "Q")):
+        """log-likelihoods at (B, J) SHO hyperparameter arrays (as :meth:`pack_parameters` takes them) and their
+        gradients.  Returns ``(ll, grads)``: ll (B,) numpy; grads a dict holding the names of ``wrt`` among
+        ``"S0"``, ``"w0"``, ``"Q"`` ((B, J) each), ``"mean"`` ((B,): d/d of a constant mean, sum alpha) and
+        ``"diag"`` ((B,): d/d of a constant added to the diagonal).  A problem whose matrix is not positive
+        definite gets -inf and NaN gradients; the others are unaffected."""
+        self._grad_check_width()
+        from .grad import parameter_vjp
+        wrt = tuple(wrt)
+        unknown = set(wrt) - {"S0", "w0", "Q", "mean", "diag"}
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        shapes = {np.shape(np.atleast_2d(np.asarray(v))) for v in (S0, w0, Q)}
+        if len(shapes) != 1 or next(iter(shapes))[0] != self.B:
+            raise ValueError(f"S0, w0, Q of shapes {sorted(shapes)} do not hold the batch's {self.B} problems")
+        pk = sho_coefficient_pack(S0, w0, Q, delta)
+        ll, g = self.value_and_grad_coefficients(pk)
+        out = {}
+        if {"S0", "w0", "Q"} & set(wrt):
+            gS0, gw0, gQ = parameter_vjp(S0, w0, Q, delta, g["real"], g["comp"], g["diag_add"])
+            out.update({k: v for k, v in (("S0", gS0), ("w0", gw0), ("Q", gQ)) if k in wrt})
+        if "mean" in wrt:
+            out["mean"] = g["mean"]
+        if "diag" in wrt:
+            out["diag"] = g["diag_add"]
+        return ll, out
 
     def evaluate_device(self, pack=None):
         """Enqueue one evaluation per problem; returns the (B,) device tensor (no host sync).

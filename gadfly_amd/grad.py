@@ -1,0 +1,229 @@
+"""
+Gradients of batched log-likelihoods.
+
+The device computes d log L / d (celerite coefficients) for B problems at once (``gf_loglike_grad``, the
+reverse-mode counterpart of celerite2's ``driver.factor_rev`` / ``solve_lower_rev``); this module
+  * sizes its workspace and splits a batch into groups under a byte cap (a problem's result does not depend on
+    the group it lands in);
+  * restates :func:`gadfly_amd.batch.sho_coefficient_pack` in torch (float64 / complex128), so that the chain
+    rule from the coefficient adjoints to (S0, w0, Q) -- exposure integration, the diagonal shift and
+    ``diag_add``'s dependence on the amplitudes included -- is ONE autograd vector-Jacobian product, with no
+    hand-written derivative;
+  * provides :class:`LogLikelihood`, a ``torch.autograd.Function`` over a :class:`BatchedLogLikelihood`.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+
+__all__ = ["sho_coefficient_pack_torch", "check_width", "check_pack_batch", "workspace_plan",
+           "coefficient_gradients", "parameter_vjp", "LogLikelihood", "DEFAULT_WORKSPACE_BYTES"]
+
+#: default cap on the gradient workspace of one call (the batch is split into groups beneath it)
+DEFAULT_WORKSPACE_BYTES = _lib.GF_GRAD_WORKSPACE_BYTES
+
+
+def sho_coefficient_pack_torch(S0, w0, Q, delta, eps=1e-5):
+    """:func:`gadfly_amd.batch.sho_coefficient_pack` on torch tensors (float64, differentiable): returns
+    ``(Jr, Jc, real, comp, diag_add)`` in the engine's stacked layout, real (2, B, max(Jr, 1)), comp
+    (4, B, max(Jc, 1)), diag_add (B,), with the numpy pack's values."""
+    S0, w0, Q = (torch.atleast_2d(torch.as_tensor(v, dtype=torch.float64)) for v in (S0, w0, Q))
+    if not (S0.shape == w0.shape == Q.shape):
+        raise ValueError("dimension mismatch")
+    B = S0.shape[0]
+    over = (Q < 0.5).detach().cpu()
+    if bool(torch.any(over != over[0])):
+        raise ValueError("all problems of a batch must share the term structure "
+                         "(the same terms overdamped, Q < 1/2, in every problem)")
+    over = over[0].to(S0.device)
+    und = ~over
+    delta = torch.broadcast_to(torch.as_tensor(delta, dtype=torch.float64, device=S0.device), (B,))[:, None]
+    So, wo, Qo = S0[:, over], w0[:, over], Q[:, over]
+    f = torch.sqrt(torch.clamp(1.0 - 4.0 * Qo * Qo, min=eps))
+    amp = 0.5 * So * wo * Qo
+    ar = torch.stack([amp * (1.0 + 1.0 / f), amp * (1.0 - 1.0 / f)], dim=-1).reshape(B, -1)
+    cr = torch.stack([0.5 * wo / Qo * (1.0 - f), 0.5 * wo / Qo * (1.0 + f)], dim=-1).reshape(B, -1)
+    Su, wu, Qu = S0[:, und], w0[:, und], Q[:, und]
+    f = torch.sqrt(torch.clamp(4.0 * Qu * Qu - 1.0, min=eps))
+    a = Su * wu * Qu
+    cc = 0.5 * wu / Qu
+    A = torch.cat([torch.complex(ar, torch.zeros_like(ar)), torch.complex(a, -(a / f))], dim=1)
+    z = torch.cat([torch.complex(cr, torch.zeros_like(cr)), torch.complex(cc, -(cc * f))], dim=1)
+    zd = z * delta
+    Ap = 2.0 * A * (torch.cosh(zd) - 1.0) / zd ** 2
+    shift = torch.sum((2.0 * A * (zd - torch.sinh(zd)) / zd ** 2).real, dim=1)
+    Jr, Jc = ar.shape[1], a.shape[1]
+    zr = S0.new_zeros((B, 1))
+    real = torch.stack([Ap[:, :Jr].real, z[:, :Jr].real]) if Jr else torch.stack([zr, zr])
+    comp = (torch.stack([Ap[:, Jr:].real, -Ap[:, Jr:].imag, z[:, Jr:].real, -z[:, Jr:].imag]) if Jc
+            else torch.stack([zr, zr, zr, zr]))
+    diag_add = torch.sum(real[0, :, :Jr], dim=1) + torch.sum(comp[0, :, :Jc], dim=1) + shift
+    return Jr, Jc, real, comp, diag_add
+
+
+def check_width(W):
+    """The one-wave gradient kernel's width limit: NotImplementedError beyond it."""
+    if W > _lib.GF_GRAD_MAX_WIDTH:
+        raise NotImplementedError(
+            f"gradients take celerite widths W <= {_lib.GF_GRAD_MAX_WIDTH} (one wave per problem); this kernel "
+            f"has W = {W}")
+
+
+def check_pack_batch(B, Jr, Jc, real, comp, diag_add):
+    """ValueError unless a stacked coefficient pack holds exactly B problems of the structure (Jr, Jc) in the
+    layout the device reads (real (2, B, max(Jr, 1)), comp (4, B, max(Jc, 1)), diag_add (B,)): gf_loglike_grad
+    indexes every array by the problem, so a shorter pack must never reach it."""
+    want = ((2, B, max(Jr, 1)), (4, B, max(Jc, 1)), (B,))
+    got = tuple(tuple(np.shape(x)) for x in (real, comp, diag_add))
+    if got != want:
+        raise ValueError(f"coefficient pack of shapes {got} does not match the batch of {B} problems "
+                         f"(expected {want})")
+
+
+def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES):
+    """(doubles per problem, problems per group, number of groups) of a gradient call."""
+    check_width(W)
+    per = int(_lib.load().gf_grad_work(int(N), int(W)))
+    if per <= 0:
+        raise ValueError(f"no gradient workspace for N = {N}, W = {W}")
+    group = int(max(1, min(B, int(cap_bytes) // (8 * per))))
+    return per, group, (B + group - 1) // group
+
+
+def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES):
+    """Run ``gf_loglike_grad`` over an engine's data (t, y - mean, diag on the device) for stacked host
+    coefficient arrays of its ORIGINAL term structure.  Returns a dict of numpy arrays: ``ll`` (B,),
+    ``real`` (2, B, Jr) = d/d(a, c), ``comp`` (4, B, Jc) = d/d(a, b, c, d), ``diag_add`` (B,), ``mean`` (B,),
+    ``info`` (B,), the plan (``workspace_bytes``, ``groups``, ``group_size``) and ``device_ms``, the summed
+    device time of the gf_loglike_grad launches (HIP events around each)."""
+    W = Jr + 2 * Jc
+    if (Jr, Jc) != engine._struct0:
+        raise ValueError("coefficient pack does not match the batch structure")
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, diag_add)
+    per, group, ngroups = workspace_plan(N, W, B, cap_bytes)
+    lib, p = engine.lib, _lib.ptr
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        work = torch.empty((group * per,), **f64)
+        ll = torch.empty((B,), **f64)
+        info = torch.zeros((B,), dtype=torch.int32, device=dev)
+        g_diag = torch.empty((B,), **f64)
+        g_mean = torch.empty((B,), **f64)
+        lr, lc = max(Jr, 1), max(Jc, 1)
+        g_real = np.zeros((2, B, lr))
+        g_comp = np.zeros((4, B, lc))
+        real = np.ascontiguousarray(real, dtype=np.float64)
+        comp = np.ascontiguousarray(comp, dtype=np.float64)
+        diag_add = np.ascontiguousarray(diag_add, dtype=np.float64)
+        t, y, dg = engine.t, engine.y, engine.diag
+        tbs, ybs = engine._bs(t), engine._bs(y)
+        dbs = 0 if dg is None else engine._bs(dg)
+        events = []
+        for b0 in range(0, B, group):
+            nb = min(group, B - b0)
+            cr_ = torch.as_tensor(np.ascontiguousarray(real[:, b0:b0 + nb]), **f64)
+            cc_ = torch.as_tensor(np.ascontiguousarray(comp[:, b0:b0 + nb]), **f64)
+            da = torch.as_tensor(diag_add[b0:b0 + nb], **f64)
+            gr = torch.zeros((2, nb, lr), **f64)
+            gc = torch.zeros((4, nb, lc), **f64)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            st = lib.gf_loglike_grad(
+                nb, N, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]), p(da),
+                t.data_ptr() + 8 * b0 * tbs, tbs,
+                None if dg is None else dg.data_ptr() + 8 * b0 * dbs, dbs,
+                y.data_ptr() + 8 * b0 * ybs, ybs, p(work), per,
+                ll.data_ptr() + 8 * b0, p(gr), p(gc), g_diag.data_ptr() + 8 * b0, g_mean.data_ptr() + 8 * b0,
+                info.data_ptr() + 4 * b0, stream)
+            _lib.check(st, "gf_loglike_grad")
+            e1.record()
+            events.append((e0, e1))
+            g_real[:, b0:b0 + nb] = gr.cpu().numpy()
+            g_comp[:, b0:b0 + nb] = gc.cpu().numpy()
+        return dict(ll=ll.cpu().numpy(), real=g_real[:, :, :Jr], comp=g_comp[:, :, :Jc],
+                    diag_add=g_diag.cpu().numpy(), mean=g_mean.cpu().numpy(), info=info.cpu().numpy(),
+                    workspace_bytes=8 * per * group, groups=ngroups, group_size=group,
+                    device_ms=sum(a.elapsed_time(b) for a, b in events))
+
+
+#: terms of each kind (overdamped, underdamped) padded to a multiple of this in the chain rule's layout
+_VJP_ALIGN = 8
+
+
+def parameter_vjp(S0, w0, Q, delta, g_real, g_comp, g_diag_add):
+    """d log L / d (S0, w0, Q), (B, J) each, from the coefficient adjoints: one vector-Jacobian product through
+    :func:`sho_coefficient_pack_torch` (CPU, float64).
+
+    A problem's result does not depend on the batch around it, to the bit: the overdamped and the underdamped terms
+    are each padded with inert dummy terms to a multiple of _VJP_ALIGN per problem (every row of every intermediate
+    then starts on a SIMD-vector boundary and has no tail), and the product runs on one CPU thread (no chunking of
+    the rows between threads).  The thread count is torch's PROCESS-WIDE intra-op setting: other threads that run
+    torch CPU work during the product run on one thread too, until it is restored.  The bit-identity rests on
+    torch's CPU kernels treating equal, aligned rows alike (tested on the installed torch, not guaranteed by it)."""
+    S0, w0, Q = (np.atleast_2d(np.asarray(v, dtype=np.float64)) for v in (S0, w0, Q))
+    B, J = S0.shape
+    over = Q[0] < 0.5
+    io, iu = np.flatnonzero(over), np.flatnonzero(~over)
+    po = -(-len(io) // _VJP_ALIGN) * _VJP_ALIGN
+    pu = -(-len(iu) // _VJP_ALIGN) * _VJP_ALIGN
+    cols = np.concatenate([io, np.full(po - len(io), -1), iu, np.full(pu - len(iu), -1)])
+    dummy = cols < 0
+    fill = np.where(np.arange(po + pu) < po, 0.25, 2.0)          # dummy Q: overdamped / underdamped side
+    pad = []
+    for v, d in ((S0, 1.0), (w0, 100.0), (Q, None)):
+        x = np.where(dummy[None, :], d if d is not None else fill[None, :], v[:, np.where(dummy, 0, cols)])
+        pad.append(np.ascontiguousarray(np.broadcast_to(x, (B, po + pu))))
+    nthreads = torch.get_num_threads()
+    torch.set_num_threads(1)                  # process-wide (see the docstring), restored below
+    try:
+        with torch.enable_grad():
+            xs = [torch.tensor(x, requires_grad=True) for x in pad]
+            Jr, Jc, real, comp, diag_add = sho_coefficient_pack_torch(*xs, delta)
+            jr, jc = 2 * len(io), len(iu)
+            gr = torch.zeros_like(real)
+            gc = torch.zeros_like(comp)
+            if jr:
+                gr[:, :, :jr] = torch.as_tensor(np.asarray(g_real)[:, :, :jr])
+            if jc:
+                gc[:, :, :jc] = torch.as_tensor(np.asarray(g_comp)[:, :, :jc])
+            gd = torch.as_tensor(np.asarray(g_diag_add, dtype=np.float64))
+            outs, gouts = [diag_add], [gd]
+            if Jr:
+                outs.append(real)
+                gouts.append(gr)
+            if Jc:
+                outs.append(comp)
+                gouts.append(gc)
+            grads = torch.autograd.grad(outs, xs, grad_outputs=gouts, allow_unused=True)
+    finally:
+        torch.set_num_threads(nthreads)
+    res = []
+    for g in grads:
+        g = np.zeros((B, po + pu)) if g is None else g.detach().numpy()
+        out = np.empty((B, J))
+        out[:, cols[~dummy]] = g[:, ~dummy]
+        res.append(out)
+    return tuple(res)
+
+
+class LogLikelihood(torch.autograd.Function):
+    """``LogLikelihood.apply(S0, w0, Q, evaluator, delta)``: the (B,) log-likelihoods of a
+    :class:`gadfly_amd.BatchedLogLikelihood` at (B, J) tensors of SHO hyperparameters, differentiable with
+    respect to S0, w0 and Q (the device gradient of :meth:`BatchedLogLikelihood.value_and_grad`)."""
+
+    @staticmethod
+    def forward(ctx, S0, w0, Q, evaluator, delta):
+        host = [x.detach().cpu().numpy() for x in (S0, w0, Q)]
+        ll, g = evaluator.value_and_grad(*host, delta)
+        ctx.save_for_backward(*(torch.as_tensor(g[k], dtype=S0.dtype, device=S0.device)
+                                for k in ("S0", "w0", "Q")))
+        return torch.as_tensor(ll, dtype=S0.dtype, device=S0.device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gS0, gw0, gQ = ctx.saved_tensors
+        go = grad_output[:, None]
+        return go * gS0, go * gw0, go * gQ, None, None

@@ -15,6 +15,8 @@
  *                                                      <- gp.py:350, :370, :232, :327, :391
  *   gf_general_matmul   driver.general_matmul_lower + general_matmul_upper
  *                                                      <- gp.py:232 (predict at new times)
+ *   gf_loglike_grad     driver.factor_rev + solve_lower_rev + the norm's adjoint
+ *                                                      (no gadfly call site: gradients for samplers)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HIP) unless marked "host"; float64 throughout;
@@ -533,6 +535,32 @@ int gf_general_matmul(int B, int64_t M, int64_t N, int W, int ld,
                       const double *t2, int64_t t2_bs, const double *U2, const double *V2,
                       const double *P2, const double *alpha, const int64_t *qidx,
                       double *work, double *mu, void *stream);
+
+/*
+ * Log-likelihoods of B problems and their gradients with respect to the celerite coefficients:
+ * the reverse-mode ops celerite2 ships for its JAX / PyMC interfaces (driver.factor_rev, driver.solve_lower_rev
+ * and the adjoint of -1/2 (z^T D^-1 z + sum log D)), on the plain recurrence of oracle/celerite_ref.c with exact
+ * generator rows at every row (theta_n = fl(d t_n)).  One wave per problem; W = Jr + 2 Jc <= 63 (-3 beyond).
+ *   coefficients as gf_build_matrices: ar, cr [B][max(Jr,1)]; ac, bc, cc, dc [B][max(Jc,1)]; diag_add [B]
+ *     (A_n = diag[n] + diag_add); t, diag, y with batch strides in elements (0 = shared; diag may be NULL)
+ *   work: work_bs >= gf_grad_work(N, W) doubles per problem (checkpoints of the forward sweep and one segment's
+ *     staged rows); B * work_bs in all
+ *   ll [B]      log-likelihood, -inf where a pivot is not positive (info = the 1-based failing row)
+ *   g_real [2][B][max(Jr,1)]      d log L / d (ar, cr)
+ *   g_comp [4][B][max(Jc,1)]      d log L / d (ac, bc, cc, dc)
+ *   g_diag [B]  d log L / d diag_add = sum_n d log L / d A_n   (a constant added to the diagonal)
+ *   g_mean [B]  d log L / d mean = sum_n alpha_n               (y holds the data minus a constant mean)
+ *   every gradient of a failed problem is NaN.  No atomics: results are bit-identical from run to run and do not
+ *   depend on the other problems of the call.
+ */
+int64_t gf_grad_work(int64_t N, int W);
+int gf_loglike_grad(int B, int64_t N, int Jr, int Jc,
+                    const double *ar, const double *cr, const double *ac, const double *bc,
+                    const double *cc, const double *dc, const double *diag_add,
+                    const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                    const double *y, int64_t y_bs, double *work, int64_t work_bs,
+                    double *ll, double *g_real, double *g_comp, double *g_diag, double *g_mean,
+                    int32_t *info, void *stream);
 
 #ifdef __cplusplus
 }

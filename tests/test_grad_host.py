@@ -1,0 +1,119 @@
+"""CPU: the host side of the log-likelihood gradient -- the torch coefficient pack against the numpy
+one, the numpy reverse pass (tests/grad_ref.py) against dense autograd, and the pack's vector-Jacobian product
+against central differences."""
+import numpy as np
+import pytest
+import torch
+
+from gadfly_amd.batch import sho_coefficient_pack
+from gadfly_amd.grad import check_pack_batch, parameter_vjp, sho_coefficient_pack_torch
+from tests.grad_ref import batch_grad, dense_loglike
+
+
+def _params(rng, B, J, n_over=0):
+    S0 = rng.uniform(0.2, 5.0, (B, J))
+    w0 = rng.uniform(20.0, 3000.0, (B, J))
+    Q = rng.uniform(0.6, 30.0, (B, J))
+    if n_over:
+        Q[:, :n_over] = rng.uniform(0.1, 0.45, (B, n_over))
+    return S0, w0, Q
+
+
+def test_torch_pack_equals_numpy_pack():
+    rng = np.random.default_rng(7)
+    for J, n_over in ((1, 0), (5, 2), (20, 3)):
+        S0, w0, Q = _params(rng, 6, J, n_over)
+        if J > 2:
+            Q[:, n_over] = 0.5                      # Q = 1/2 exactly: the underdamped side with f = sqrt(eps)
+            Q[:, n_over + 1] = 0.5 + 1e-9
+        delta = rng.uniform(2e-5, 2e-4, 6)
+        want = sho_coefficient_pack(S0, w0, Q, delta)
+        got = sho_coefficient_pack_torch(torch.tensor(S0), torch.tensor(w0), torch.tensor(Q), delta)
+        assert got[:2] == want[:2]
+        for g, w in zip(got[2:], want[2:5]):
+            g = g.detach().numpy()
+            assert g.shape == w.shape
+            assert np.all(np.abs(g - w) <= 1e-15 * np.maximum(np.abs(w), np.max(np.abs(w)) * 1e-300) + 1e-300)
+
+
+def _problem(rng, N, gaps=True):
+    dt = 60.0 / 1e6
+    t = np.cumsum(np.full(N, dt))
+    if gaps:
+        t[N // 3:] += 40 * dt
+        t[2 * N // 3:] += 7 * dt
+    y = rng.normal(size=N) * 30.0
+    diag = np.full(N, 400.0) + rng.uniform(0.0, 50.0, N)
+    return t, y, diag
+
+
+@pytest.mark.parametrize("J,n_over,N", [(1, 0, 1500), (1, 1, 900), (5, 2, 1200), (20, 0, 600)])
+def test_numpy_reverse_pass_matches_dense_autograd(J, n_over, N):
+    rng = np.random.default_rng(100 + J + n_over)
+    B = 2
+    S0, w0, Q = _params(rng, B, J, n_over)
+    S0 *= 2.0
+    w0 = rng.uniform(50.0, 1500.0, (B, J))
+    delta = 60.0 / 1e6
+    t, y, diag = _problem(rng, N)
+    # numpy reverse pass -> coefficient adjoints -> (S0, w0, Q) through the torch pack's VJP
+    Jr, Jc, real, comp, diag_add, _ = sho_coefficient_pack(S0, w0, Q, delta)
+    ll, g = batch_grad(np.broadcast_to(t, (B, N)), np.broadcast_to(y, (B, N)), np.broadcast_to(diag, (B, N)),
+                       Jr, Jc, real, comp, diag_add)
+    gS0, gw0, gQ = parameter_vjp(S0, w0, Q, delta, g["real"], g["comp"], g["diag_add"])
+    # dense reference
+    th = [torch.tensor(x, requires_grad=True) for x in (S0, w0, Q)]
+    lld = dense_loglike(*th, delta, t, y, diag)
+    refs = torch.autograd.grad(lld.sum(), th)
+    assert np.all(np.abs(ll - lld.detach().numpy()) <= 1e-9 * np.abs(ll))
+    for theta, got, ref in zip((S0, w0, Q), (gS0, gw0, gQ), refs):
+        a, r = theta * got, theta * ref.numpy()
+        assert np.max(np.abs(a - r)) <= 1e-9 * max(1.0, np.max(np.abs(r))), (np.max(np.abs(a - r)), np.max(np.abs(r)))
+    # the mean and diagonal adjoints: sum alpha and d/d(constant on the diagonal)
+    yt, dt_ = torch.tensor(y), torch.tensor(diag)
+    m = torch.zeros((), dtype=torch.float64, requires_grad=True)
+    s = torch.zeros((), dtype=torch.float64, requires_grad=True)
+    l0 = dense_loglike(*(torch.tensor(x) for x in (S0[:1], w0[:1], Q[:1])), delta, t, yt - m, dt_ + s)[0]
+    gm, gs = torch.autograd.grad(l0, (m, s))
+    assert abs(g["mean"][0] - gm.item()) <= 1e-8 * max(1.0, abs(gm.item()))
+    assert abs(g["diag_add"][0] - gs.item()) <= 1e-8 * max(1.0, abs(gs.item()))
+
+
+def test_pack_vjp_matches_central_differences():
+    rng = np.random.default_rng(3)
+    B, J = 3, 4
+    S0, w0, Q = _params(rng, B, J, 1)
+    delta = rng.uniform(3e-5, 1e-4, B)
+    Jr, Jc, real, comp, diag_add, _ = sho_coefficient_pack(S0, w0, Q, delta)
+    gr, gc, gd = rng.normal(size=real.shape), rng.normal(size=comp.shape), rng.normal(size=diag_add.shape)
+    got = parameter_vjp(S0, w0, Q, delta, gr, gc, gd)
+
+    def f(S0_, w0_, Q_):
+        _, _, r, c, d, _ = sho_coefficient_pack(S0_, w0_, Q_, delta)
+        return np.sum(r * gr, axis=(0, 2)) + np.sum(c * gc, axis=(0, 2)) + d * gd
+
+    args = [S0, w0, Q]
+    for i in range(3):
+        for j in range(J):
+            h = 1e-4 * args[i][:, j]         # (the pack loses digits to cosh(z delta) - 1: a step of 1e-6 shows them)
+            up = [a.copy() for a in args]
+            dn = [a.copy() for a in args]
+            up[i][:, j] += h
+            dn[i][:, j] -= h
+            fd = (f(*up) - f(*dn)) / (2.0 * h)
+            assert np.allclose(got[i][:, j], fd, rtol=1e-5, atol=1e-6 * np.max(np.abs(fd)) + 1e-12), (i, j)
+
+
+def test_pack_of_another_batch_size_is_refused():
+    """The device indexes every coefficient array by the problem: a pack of another size never reaches it."""
+    rng = np.random.default_rng(4)
+    S0, w0, Q = _params(rng, 5, 3, 1)
+    Jr, Jc, real, comp, diag_add, _ = sho_coefficient_pack(S0, w0, Q, 6e-5)
+    check_pack_batch(5, Jr, Jc, real, comp, diag_add)
+    for B in (4, 6):
+        with pytest.raises(ValueError, match="batch"):
+            check_pack_batch(B, Jr, Jc, real, comp, diag_add)
+    with pytest.raises(ValueError, match="batch"):
+        check_pack_batch(5, Jr, Jc, real[:, :, :1], comp, diag_add)      # a term column short
+    with pytest.raises(ValueError, match="batch"):
+        check_pack_batch(5, Jr, Jc, real, comp, diag_add[:4])

@@ -1,0 +1,85 @@
+#!/usr/bin/env python
+"""Latency of BatchedLogLikelihood.value_and_grad against evaluate() on the same batch: one JSON line
+per shape, medians of 5 calls -- (a) walkers B = 2048, N = 1e5, J = 30; (b) cfg3-shaped B = 256, N = 65 000, J = 20;
+(c) one star B = 1, N = 1e5, J = 30.  `--shapes a,c` runs a subset, `--reps` sets the count.
+
+grad_device_ms: the gf_loglike_grad launches alone (HIP events around each, summed over the groups);
+grad_api_ms: the whole call as a caller sees it (coefficient pack, launches, copies, the host chain rule);
+evaluate_device_ms: HIP events around evaluate_device(pack_parameters(...)) (pack upload and every kernel);
+evaluate_api_ms: the same with the copy of the result to the host, wall time."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import gadfly_amd  # noqa: E402
+from gadfly_amd.synth import solar_like_hyperparameters, uniform_times  # noqa: E402
+
+SHAPES = {"a": (2048, 100_000, 30), "b": (256, 65_000, 20), "c": (1, 100_000, 30)}
+
+
+def median_ms(fn, reps):
+    """Medians of (wall ms, value fn returns) over `reps` calls after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    ts, vs = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        vs.append(fn())
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)) * 1e3, float(np.median(vs))
+
+
+def device_span(fn):
+    """fn() enqueued between two HIP events: their elapsed time in ms."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="a,b,c")
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    rng = np.random.Generator(np.random.PCG64(2024))
+    for name in args.shapes.split(","):
+        B, N, J = SHAPES[name]
+        kern = gadfly_amd.StellarOscillatorKernel(solar_like_hyperparameters(J), texp=60.0)
+        terms = kern.term.terms
+        base = [np.array([[getattr(tm, k) for tm in terms]]) for k in ("S0", "w0", "Q")]
+        # proposals around the kernel's own parameters (Q untouched: every proposal keeps its overdamped terms)
+        S0, w0 = (np.repeat(b, B, axis=0) * np.exp(0.05 * rng.normal(size=(B, J))) for b in base[:2])
+        Q = np.repeat(base[2], B, axis=0)
+        t = uniform_times(N, 60.0)
+        y = 100.0 * rng.normal(size=N)
+        ev = gadfly_amd.BatchedLogLikelihood([kern] * B, t, y, yerr=30.0)
+        delta = float(kern.delta)
+        run_ev = lambda: ev.evaluate_device(ev.pack_parameters(S0, w0, Q, delta))       # noqa: E731
+        ev_api, _ = median_ms(lambda: run_ev().cpu(), args.reps)
+        _, ev_dev = median_ms(lambda: device_span(run_ev), args.reps)
+
+        def run_grad():
+            ev.value_and_grad(S0, w0, Q, delta)
+            return ev.last_grad_device_ms
+
+        gr_api, gr_dev = median_ms(run_grad, args.reps)
+        ws, groups, group_size = ev.last_grad_plan
+        print(json.dumps(dict(shape=name, B=B, N=N, J=J, W=2 * J, grad_device_ms=round(gr_dev, 2),
+                              grad_api_ms=round(gr_api, 2), evaluate_device_ms=round(ev_dev, 3),
+                              evaluate_api_ms=round(ev_api, 3), device_ratio=round(gr_dev / ev_dev, 2),
+                              api_ratio=round(gr_api / ev_api, 2), workspace_bytes=int(ws), groups=int(groups),
+                              group_size=int(group_size), reps=args.reps)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
