@@ -21,7 +21,8 @@ import numpy as np
 from . import _lib
 from .engine import StreamingBatch
 
-__all__ = ["BatchedLogLikelihood", "log_likelihood_batch", "sho_coefficient_pack"]
+__all__ = ["BatchedLogLikelihood", "log_likelihood_batch", "sho_coefficient_pack",
+           "BatchedSampler", "sample_batch"]
 
 
 def sho_coefficient_pack(S0, w0, Q, delta, eps=1e-5):
@@ -484,3 +485,254 @@ def log_likelihood_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, device=N
     positive definite (celerite2's ``quiet=True`` convention)."""
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
                                 device=device).evaluate()
+
+
+def _is_series_list(x):
+    return isinstance(x, (list, tuple)) or (isinstance(x, np.ndarray) and x.dtype == object)
+
+
+def _center_draws(x, size):
+    """The reference's centring rule (gp.py:392: ``result -= result.mean(axis=0 if result.ndim == 2 else None)``) per
+    problem, in place, on a tensor whose last axis is time: a single draw ((..., N), ``size`` None) loses its
+    time-mean, ``size`` draws ((..., size, N)) their across-realisation mean."""
+    x -= x.mean(dim=-1, keepdim=True) if size is None else x.mean(dim=-2, keepdim=True)
+    return x
+
+
+class BatchedSampler:
+    """Light curves of B DIFFERENT kernels in one fused device sweep: ``y_b = L_b D_b^{1/2} eps_b`` with
+    ``K_b = L_b D_b L_b^T``, what ``GaussianProcess(kernel_b, t, yerr).sample()`` gives one kernel at a time
+    (the reference's gp.py:372-395).  The sweep that factors draws as it goes (gf_sample_fused: the pad
+    column that carries the log-likelihood's forward solve carries the draw), so no factor is ever stored and a
+    call costs what one :meth:`BatchedLogLikelihood.evaluate` costs.
+
+    Constructor arguments and validation are :class:`BatchedLogLikelihood`'s without ``y``: ``t`` shared ((N,)),
+    per problem ((B, N)) or -- ragged -- a list of B axes of different lengths (``yerr`` / ``diag`` then a scalar,
+    one value per problem or a list of per-series arrays; ``mean`` a scalar or one value per problem).  A ragged
+    batch is extended to the longest series with missing-data rows at the END of each series.  A draw is a
+    FORWARD recurrence -- row n depends on rows < n only -- so pad rows cannot touch the real rows: they are cut
+    off, and there is no pad correction of any kind.
+
+    ``size`` draws per problem take ``size`` sweeps (cost: ``size`` x one sweep, each with its own factorisation in
+    registers).  For many draws of ONE kernel use :meth:`GaussianProcess.sample_device`: its stored factor and
+    MFMA ``dot_tril`` are the right tool there.  One wave (a workgroup of up to seven for wide kernels) works
+    per problem: a batch below a few hundred problems leaves most of the chip idle.  That is accepted; there is
+    no time-parallel sampler and no sharding of draws over several GPUs.
+
+    Generator rows: exact every row by default (``generator_period = 1``, any power of two up to 64 may be set).
+    With ``auto_generator_period = True`` the evaluator's rule applies instead: the period follows
+    ``engine.period_for_condition`` on the max a / min d the last call measured (``generator_target``), and a
+    call whose own conditioning does not allow the period it ran at is repeated with exact rows.
+
+    Kernels whose structure or phases the fused sweeps do not take (W > 176, wide kernels that are not made of
+    complex terms after rewriting, phases beyond 1e12 rad) raise ``NotImplementedError`` naming the condition."""
+
+    def __init__(self, kernels, t, yerr=None, diag=None, mean=0.0, device=None, tile_rows=8192):
+        if yerr is not None and diag is not None:
+            raise ValueError("only one of 'diag' and 'yerr' can be provided")
+        kernels = list(kernels)
+        B = len(kernels)
+        if B < 1:
+            raise ValueError("dimension mismatch")
+        self.rows = None                    # ragged batches: real rows per problem
+        self._dmax = None
+        if _is_ragged(t):
+            if len(t) != B:
+                raise ValueError("dimension mismatch")
+            dd = diag
+            if yerr is not None:
+                dd = ([np.asarray(e, dtype=np.float64) ** 2 for e in yerr] if _is_series_list(yerr)
+                      else np.asarray(yerr, dtype=np.float64) ** 2)
+            zeros = [np.zeros(np.shape(x)) for x in t]
+            t, _, d, self.rows, self._dmax, _, dt_min, tabs = _pad_ragged(t, zeros, dd, mean)
+            mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), (B,)).copy()
+        else:
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            if t.ndim not in (1, 2) or t.shape[-1] < 1 or (t.ndim == 2 and t.shape[0] not in (1, B)):
+                raise ValueError("dimension mismatch")
+            if np.any(np.diff(t, axis=-1) < 0.0):
+                raise ValueError("The input coordinates must be sorted")
+            N = t.shape[-1]
+            d = None
+            if yerr is not None:
+                d = np.asarray(yerr, dtype=np.float64) ** 2
+            elif diag is not None:
+                d = np.asarray(diag, dtype=np.float64)
+            if d is not None:
+                if d.ndim == 0:
+                    d = np.full(N, float(d))
+                if d.ndim > 2 or d.shape[-1] != N or (d.ndim == 2 and d.shape[0] not in (1, B)):
+                    raise ValueError("dimension mismatch")
+            mean = np.asarray(mean, dtype=np.float64)
+            if not (mean.ndim == 0 or mean.shape == (B,) or mean.shape == (B, N)):
+                raise ValueError("dimension mismatch")
+            dt_min = float(np.min(np.diff(t, axis=-1))) if N > 1 else None
+            tabs = float(np.max(np.abs(t)))
+        self._t, self._d, self._mean = t, d, mean
+        self._dt_min, self._t_abs_max = dt_min, tabs
+        self._B, self._N = B, int(t.shape[-1])
+        self._device, self._tile_rows = device, tile_rows
+        # (host work only: the term structures are compared here, the device is first touched by the first draw)
+        self._coeffs = [k.get_device_coefficients() for k in kernels]
+        from .engine import _coeff_pack
+        _coeff_pack(self._coeffs)
+        self._engine = None
+        #: rows between exact re-anchorings of the row generator (1: exact rows, the default)
+        self.generator_period = 1
+        #: True: the evaluator's rule instead -- period from the measured conditioning, with its re-run
+        self.auto_generator_period = False
+        self.generator_target = 1e-9
+        #: draws repeated with exact rows by the guard of the automatic period so far
+        self.guard_reruns = 0
+        self._auto_period = None
+        self._info = None
+
+    @property
+    def B(self):
+        return self._B
+
+    @property
+    def N(self):
+        """Rows per problem (the longest series of a ragged batch)."""
+        return self._N
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            eng = StreamingBatch(self._coeffs, self._t, np.zeros((1, self._N)), diag=self._d,
+                                 tile_rows=self._tile_rows, device=self._device)
+            if self._dmax is not None:      # ragged: the condition estimates look at the REAL rows' diagonal
+                eng._diag_amax = eng.torch.as_tensor(self._dmax, dtype=eng.torch.float64, device=eng.device)
+            self._engine = eng
+        return self._engine
+
+    def pack(self, kernels):
+        return self.engine.pack_coefficients([k.get_device_coefficients() for k in kernels])
+
+    def pack_parameters(self, S0, w0, Q, delta):
+        """Coefficient pack straight from (B, J) hyperparameter arrays (:func:`sho_coefficient_pack`)."""
+        return self.engine.pack_arrays(*sho_coefficient_pack(S0, w0, Q, delta))
+
+    @property
+    def last_info(self):
+        """Per problem: 0, or the 1-based row at which the last call's factorisation failed (synchronises)."""
+        return None if self._info is None else self._info.cpu().numpy()
+
+    def _check_normals(self, normals, size):
+        """Shape of ``normals`` against the output's, on the host (before anything is enqueued)."""
+        B, N = self._B, self._N
+
+        def shape(x):                       # (a device tensor is not to be converted for this)
+            return tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+
+        if self.rows is not None:
+            if not _is_series_list(normals) or len(normals) != B:
+                raise ValueError("dimension mismatch")
+            for x, n in zip(normals, self.rows):
+                if shape(x) != ((int(n),) if size is None else (size, int(n))):
+                    raise ValueError("dimension mismatch")
+        elif shape(normals) != ((B, N) if size is None else (B, size, N)):
+            raise ValueError("dimension mismatch")
+
+    def _sweeps(self, eps, out, period):
+        eng = self.engine
+        torch = eng.torch
+        eng.generator_period = int(period)
+        dmin = info = None
+        for r in range(eps.shape[1]):       # one sweep per draw
+            m, i = eng.sample_fused(eps[:, r, :], out[:, r, :])
+            dmin = m if dmin is None else torch.minimum(dmin, m)
+            info = i if info is None else torch.maximum(info, i)
+        return dmin, info
+
+    def sample_device(self, pack=None, size=None, normals=None, seed=None, include_mean=True, center=True):
+        """One draw per problem -- a float64 device tensor (B, N) -- or ``size`` draws, (B, size, N); a ragged
+        batch returns a list of B tensors (N_b,) / (size, N_b).  ``size`` draws cost ``size`` sweeps.
+
+        ``pack``: new kernels for this and the following calls (:meth:`pack`, :meth:`pack_parameters`).
+        ``normals``: the standard normals eps to use, a host array or device tensor of the output's shape (a list
+        for a ragged batch); otherwise they come from ONE ``torch.randn`` call for the whole (B[, size], N) block
+        on the device, from a ``torch.Generator`` seeded with ``seed``.  ``center=True`` applies the
+        reference's rule per problem (gp.py:392): the time-mean of a single draw is removed, the
+        across-realisation mean of ``size`` draws.  ``center=False`` returns ``L D^{1/2} eps`` (+ mean) untouched.
+        A problem whose matrix is not positive definite gets NaN in all its rows and its failing row in
+        :attr:`last_info`; the other problems are unaffected."""
+        if size is not None:
+            size = int(size)
+            if size < 1:
+                raise ValueError("size must be a positive number of draws")
+        if normals is not None:
+            self._check_normals(normals, size)
+        B, N, R = self._B, self._N, (1 if size is None else size)
+        eng = self.engine
+        torch = eng.torch
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        if pack is not None:
+            eng.use_coefficients(pack)
+        with torch.cuda.device(eng.device):
+            buf = torch.empty((B * R * N + 4,), **f64)      # (the sweeps read three elements past the end)
+            buf[B * R * N:] = 0.0
+            eps = buf[:B * R * N].view(B, R, N)
+            if normals is None:
+                gen = None
+                if seed is not None:
+                    gen = torch.Generator(device=eng.device)
+                    gen.manual_seed(int(seed))
+                torch.randn((B, R, N), generator=gen, out=eps)
+            elif self.rows is not None:
+                eps.zero_()
+                for b, (x, n) in enumerate(zip(normals, self.rows)):
+                    eps[b, :, :int(n)] = torch.as_tensor(x).to(**f64).reshape(R, int(n))
+            else:
+                eps.copy_(torch.as_tensor(normals).to(**f64).reshape(B, R, N))
+            out = torch.empty((B, R, N), **f64)
+            period = int(self.generator_period)
+            if self.auto_generator_period:
+                period = int(self._auto_period or eng.generator_period)
+            dmin, info = self._sweeps(eps, out, period)
+            if self.auto_generator_period:
+                amax = eng._pack[2] if eng._diag_amax is None else eng._pack[2] + eng._diag_amax
+                ok = info == 0
+                if period > 1:
+                    flag = (eng.generator_error_coefficient(period) * amax > self.generator_target * dmin) & ok
+                    if bool(flag.any()):            # (host synchronisation, as the evaluator's resolve())
+                        dmin, info = self._sweeps(eps, out, 1)
+                        ok = info == 0
+                        self.guard_reruns += 1
+                worst = torch.where(ok, amax / dmin, torch.zeros_like(dmin)).max()
+                self._auto_period = eng.period_for_condition(float(worst), self.generator_target)
+            self._info = info
+            out.masked_fill_((info != 0)[:, None, None], float("nan"))
+            if include_mean and np.any(self._mean != 0.0):
+                mu = torch.as_tensor(np.ascontiguousarray(self._mean)).to(**f64)
+                out += mu.reshape((1, 1, 1) if mu.ndim == 0 else ((B, 1, 1) if mu.ndim == 1 else (B, 1, N)))
+            if center and size is not None:
+                _center_draws(out, size)
+            if self.rows is not None:
+                res = []
+                for b, n in enumerate(self.rows):
+                    x = out[b, :, :int(n)]
+                    x = x[0] if size is None else x.contiguous()
+                    res.append(_center_draws(x.clone(), None) if (center and size is None) else x)
+                return res
+            if size is None:
+                out = out[:, 0, :]
+                if center:
+                    _center_draws(out, None)
+            return out
+
+    def sample(self, pack=None, size=None, normals=None, seed=None, include_mean=True, center=True):
+        """:meth:`sample_device`, returned as numpy (a list of arrays for a ragged batch)."""
+        out = self.sample_device(pack=pack, size=size, normals=normals, seed=seed, include_mean=include_mean,
+                                 center=center)
+        if isinstance(out, list):
+            return [x.cpu().numpy() for x in out]
+        return out.cpu().numpy()
+
+
+def sample_batch(kernels, t, yerr=None, diag=None, mean=0.0, size=None, normals=None, seed=None, device=None):
+    """One-shot form of :class:`BatchedSampler`: draws of B kernels as a float64 device tensor (B, N) or
+    (B, size, N) (a list for ragged ``t``), centred as the reference centres its draws -- ready for
+    ``PowerSpectrum.from_flux``."""
+    return BatchedSampler(kernels, t, yerr=yerr, diag=diag, mean=mean,
+                          device=device).sample_device(size=size, normals=normals, seed=seed)

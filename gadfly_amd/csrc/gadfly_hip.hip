@@ -989,7 +989,12 @@ struct RowGen {
     }
 };
 
-template <int ROWS>
+// SAMPLE = true: the sampling sweep (gf_sample_fused).  y_ holds the standard normals eps and the pad column
+// carries the DRAW instead of the solve:  x_n = sqrt(d_n) eps_n,  F~ += r x_n / d_n,  out_n = x_n + u~ . F~
+// (y = L D^1/2 eps, celerite2's matmul_lower with V := W after factor) -- the solve's recurrence with the sign
+// flipped and the input carried instead of the output.  z_ is then the draw, indexed by the GLOBAL row with
+// y's batch stride.  Reset rows, decays, block scaling and the row generator are the log-likelihood's.
+template <int ROWS, bool SAMPLE = false>
 __global__ void __launch_bounds__(64, 2)
 k_factor3(const int64_t N, const int64_t n_first, const int64_t chunk_len, const int nch,
           const int ch0, const int nsel, const int Jr, const int Jc, const int block_sub, const double gap,
@@ -1020,7 +1025,7 @@ k_factor3(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     const bool has_g = diag_ != nullptr;
     const double *__restrict__ gg = has_g ? diag_ + (size_t)pr * diag_bs + g0 : yg;
     double *__restrict__ dg = d_ + pb;
-    double *__restrict__ zg = z_ + pb;
+    double *__restrict__ zg = SAMPLE ? z_ + (size_t)pr * y_bs + g0 : z_ + pb;
     // chunk-mode row stores: loop-invariant per-lane pointers, indexed with opaque_uniform(row)
     double *__restrict__ rg = r_out ? r_out + pb * 64 + lane : nullptr;
     double *__restrict__ ug = Ut_out ? Ut_out + pb * 64 + lane : nullptr;   // stored factor:
@@ -1100,7 +1105,7 @@ k_factor3(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
         const double s1 = wave_sum(ut_c * tmp);     // u~ = 0 in lane 63
         const double s2 = read_lane(tmp, 63);       // u~ . F~
         const double dn = a_n - s1;
-        const double zn = yy - s2;
+        const double zn = SAMPLE ? __dsqrt_rn(dn) * yy : yy - s2;      // (the draw: x_n rides where z_n does)
         if (!(dn > 0.0)) {
             const int64_t gf = g0 + n + 1;
             fail = (int32_t)(gf > 0x7fffffff ? 0x7fffffff : gf);
@@ -1114,7 +1119,7 @@ k_factor3(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
             if (ug) ug[ro] = ut_c;
             if (wg) wg[ro] = fl ? 0.0 : q;
         }
-        if (lane == 0) { dg[n] = dn; zg[n] = zn; }
+        if (lane == 0) { dg[n] = dn; zg[n] = SAMPLE ? zn + s2 : zn; }
     }
     if (fail) {
         if (lane == 0) info[b] = fail;
@@ -1237,7 +1242,8 @@ __device__ __forceinline__ void sweep7_run(double (&T)[ROWS / 2][2], double2 (&u
 
 // ROWSTORE = false: no row is stored (r_out, Ut_out, Wt_out, de_out all null: the streamed log-likelihood
 // and the plain final pass) -- their tests, pointer arithmetic and exec-mask switches leave the row loop
-template <int ROWS, bool ROWSTORE>
+// SAMPLE = true: the sampling sweep, column 63 carries the draw (see k_factor3)
+template <int ROWS, bool ROWSTORE, bool SAMPLE = false>
 __global__ void __launch_bounds__(64, 2)
 k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const int nch,
           const int ch0, const int nsel, const int Jr, const int Jc, const int block_sub, const double gap,
@@ -1267,7 +1273,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     const bool has_g = diag_ != nullptr;
     const double *__restrict__ gg = has_g ? diag_ + (size_t)pr * diag_bs + g0 : yg;
     double *__restrict__ dg = d_ + pb;
-    double *__restrict__ zg = z_ + pb;
+    double *__restrict__ zg = SAMPLE ? z_ + (size_t)pr * y_bs + g0 : z_ + pb;
     const int own = 2 * c + g;                      // the column whose row-vector entries this lane carries
     // chunk-mode row stores: loop-invariant per-lane pointers, indexed with opaque_uniform(row)
     double *__restrict__ rg = (ROWSTORE && r_out) ? r_out + pb * 64 + own : nullptr;
@@ -1358,7 +1364,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
         const double s1 = wave_sum(ut_c * tmp);     // u~ = 0 in the pad / forward-solve columns
         const double s2 = read_lane(tmp, 63);       // u~ . F~ (column 63)
         const double dn = a_n - s1;
-        const double zn = yy - s2;
+        const double zn = SAMPLE ? __dsqrt_rn(dn) * yy : yy - s2;      // (the draw: x_n rides where z_n does)
         if (!(dn > 0.0)) {
             const int64_t gf = g0 + n + 1;
             fail = (int32_t)(gf > 0x7fffffff ? 0x7fffffff : gf);
@@ -1375,7 +1381,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
                 if (wg) wg[ro] = r * inv;
             }
         }
-        if (lane == 0) { dg[n] = dn; zg[n] = zn; }
+        if (lane == 0) { dg[n] = dn; zg[n] = SAMPLE ? zn + s2 : zn; }
     }
     if (fail) {
         if (lane == 0) info[b] = fail;
@@ -1770,7 +1776,10 @@ constexpr int WIDE_FAIL_CHECK = 64;
 
 // (The arrays are passed as separate __restrict__ parameters, not inside FactorWArgs: only then can
 // hipcc prove the wave-uniform t loads unclobbered and issue them as scalar loads.)
-template <int TR, int NW>
+// SAMPLE = true: the sampling sweep, column FCOL carries the draw (see k_factor3); y_ = eps, z_ = the draw by
+// global row (y's batch stride).  The sweep waves hold nothing more than in the log-likelihood: sqrt(d_n) is
+// formed where z_n was.
+template <int TR, int NW, bool SAMPLE = false>
 __global__ void __launch_bounds__(64 * (NW + 1), 2)
 k_factorw(const FactorWArgs A,
           const double *__restrict__ ac_, const double *__restrict__ bc_,
@@ -1809,7 +1818,7 @@ k_factorw(const FactorWArgs A,
         const double *__restrict__ gg = has_g ? diag_ + (size_t)pr * A.diag_bs + g0 : yg;
         const double diag_add = diag_add_[pr];
         double *__restrict__ dg = d_ + pb;
-        double *__restrict__ zg = z_ + pb;
+        double *__restrict__ zg = SAMPLE ? z_ + (size_t)pr * A.y_bs + g0 : z_ + pb;
         constexpr int NP = (CP / 2 + 63) / 64;      // phasors per lane (1 up to W + 1 <= 128 columns, else 2)
         RowGen gen[NP];
         bool live[NP];
@@ -1882,7 +1891,8 @@ k_factorw(const FactorWArgs A,
 #pragma unroll
             for (int w2 = 0; w2 < NW; ++w2) s1 += sh.p[nxt][w2][0];
             const double dn = a_n - s1;
-            const double zn = yy - sh.p[nxt][NW - 1][1];
+            const double zn = SAMPLE ? fma(__dsqrt_rn(dn), yy, sh.p[nxt][NW - 1][1])   // the draw x_n + u~ . F~
+                                     : yy - sh.p[nxt][NW - 1][1];
             // d, z leave in coalesced blocks of 64 rows (lane j keeps row 64 m + j): a store per row would
             // sit in the same in-order queue as the y / diag prefetches and make their waits wait for HBM
             // write acknowledgements
@@ -2001,7 +2011,7 @@ k_factorw(const FactorWArgs A,
             for (int k = 0; k < NK; ++k) wb[k] = ((const double2 *)sh.w[nxt] + g)[4 * k];
         }
         const double dn = fa.y - s1;                // every wave forms the pivot itself
-        const double zn = yy - s2;
+        const double zn = SAMPLE ? __dsqrt_rn(dn) * yy : yy - s2;      // (the draw: x_n rides where z_n does)
         vt_c = vt_n; u01 = u01_n; fa = fa_n; yy = yy_n;
         de = read_lane(fa.x, 0);
         b0 = b1; b1 = (b1 == 2) ? 0 : b1 + 1;
@@ -5180,17 +5190,17 @@ inline WideShape wide_shape(int W) {
     return s;
 }
 
-template <int TR, int NW>
+template <int TR, int NW, bool SAMPLE>
 int launch_factorw(const FactorWArgs &A, const FactorWPtrs &P, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_factorw<TR, NW>), dim3(grid), dim3(64 * (NW + 1)), 0, st, A, P.ac, P.bc, P.cc, P.dc,
+    hipLaunchKernelGGL((k_factorw<TR, NW, SAMPLE>), dim3(grid), dim3(64 * (NW + 1)), 0, st, A, P.ac, P.bc, P.cc, P.dc,
                        P.diag_add, P.cmax, P.t, P.diag, P.y, P.d, P.z, P.r_out, P.Ut_out, P.Wt_out, P.de_out,
                        P.S_state, P.info);
     return 0;
 }
 
-int dispatch_factorw(const FactorWArgs &A, const FactorWPtrs &P, int W, int grid, hipStream_t st) {
+int dispatch_factorw(const FactorWArgs &A, const FactorWPtrs &P, int W, int grid, bool sample, hipStream_t st) {
     const WideShape s = wide_shape(W);
-#define GF_FW(TRv, NWv) if (s.tr == TRv && s.nw == NWv) return launch_factorw<TRv, NWv>(A, P, grid, st);
+#define GF_FW(TRv, NWv) if (s.tr == TRv && s.nw == NWv) return sample ? launch_factorw<TRv, NWv, true>(A, P, grid, st) : launch_factorw<TRv, NWv, false>(A, P, grid, st);
     GF_FW(16, 3) GF_FW(20, 3) GF_FW(24, 3)
     GF_FW(24, 4) GF_FW(28, 4) GF_FW(32, 4)
     GF_FW(32, 5) GF_FW(36, 5) GF_FW(40, 5)
@@ -5389,6 +5399,7 @@ static bool sweep_tiled(int variant, int Jr, int Jc) {
 }
 
 #define GF_F3_ARGS dim3(B * chunk_count), dim3(64), 0, st, N, n_first, chunk_len, nch, chunk_first, chunk_count, Jr, Jc, (block | (gen_period << 8) | zero_start), gap, ar, cr, ac, bc, cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, r_out, Ut_out, Wt_out, de_out, S_state, F_state, info
+#define GF_S3_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_factor7<R, false, true>), GF_F3_ARGS); else hipLaunchKernelGGL((k_factor3<R, true>), GF_F3_ARGS); break;
 #define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
 
 static int check_sweep_options(const char *who, int gen_period, int variant, int Jr, int Jc) {
@@ -5411,9 +5422,12 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
                         const double *y, int64_t y_bs,
                         double *d, double *z, double *r_out, double *Ut_out, double *Wt_out,
                         double *de_out, double *S_state, double *F_state,
-                        int32_t *info, void *stream) {
+                        int32_t *info, void *stream, bool sample = false) {
     const int W = Jr + 2 * Jc;
     if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
+    // the sampling sweeps (y = eps, z = the draw by global row with y's batch stride): streamed tiles only
+    if (sample && (nch > 1 || r_out || Ut_out || Wt_out || de_out || (variant & GF_SWEEP_ZERO_START) || (B > 1 && y_bs < 1)))
+        return set_err("%s: one chunk, no row outputs, and a batch stride for eps / out (eps_bs=%lld)", who, y_bs);
     // (u~ rows / reset spans and the w~ rows are stored independently: a nominal pass needs no w~ rows)
     if ((Ut_out != nullptr) != (de_out != nullptr) || (Wt_out && !Ut_out))
         return set_err("%s: Ut_out and de_out go together, Wt_out needs them", who);
@@ -5448,11 +5462,20 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
         P.t = t; P.diag = diag; P.y = y;
         P.d = d; P.z = z; P.r_out = r_out; P.Ut_out = Ut_out; P.Wt_out = Wt_out; P.de_out = de_out;
         P.S_state = S_state; P.info = info;
-        if (dispatch_factorw(A, P, W, B * chunk_count, st)) return set_err("%s: internal dispatch error (wide)", who);
+        if (dispatch_factorw(A, P, W, B * chunk_count, sample, st)) return set_err("%s: internal dispatch error (wide)", who);
         return check_launch(who);
     }
     const int rows = (W + 3) / 4 * 4;
     const bool rowstore = r_out || Ut_out || Wt_out || de_out;
+    if (sample) {
+        switch (rows) {
+            GF_S3_CASE(4) GF_S3_CASE(8) GF_S3_CASE(12) GF_S3_CASE(16) GF_S3_CASE(20) GF_S3_CASE(24)
+            GF_S3_CASE(28) GF_S3_CASE(32) GF_S3_CASE(36) GF_S3_CASE(40) GF_S3_CASE(44) GF_S3_CASE(48)
+            GF_S3_CASE(52) GF_S3_CASE(56) GF_S3_CASE(60) GF_S3_CASE(64)
+            default: return set_err("%s: internal dispatch error", who);
+        }
+        return check_launch(who);
+    }
     switch (rows) {
         GF_F3_CASE(4) GF_F3_CASE(8) GF_F3_CASE(12) GF_F3_CASE(16) GF_F3_CASE(20) GF_F3_CASE(24)
         GF_F3_CASE(28) GF_F3_CASE(32) GF_F3_CASE(36) GF_F3_CASE(40) GF_F3_CASE(44) GF_F3_CASE(48)
@@ -5474,6 +5497,20 @@ int gf_loglike_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int bloc
     return fused_launch("gf_loglike_fused", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
                         diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
                         nullptr, nullptr, nullptr, S_state, F_state, info, stream);
+}
+
+int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                    int gen_period, int variant,
+                    const double *ar, const double *cr, const double *ac,
+                    const double *bc, const double *cc, const double *dc,
+                    const double *diag_add, const double *cmax,
+                    const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                    const double *eps, int64_t eps_bs,
+                    double *d, double *out, double *S_state, double *F_state,
+                    int32_t *info, void *stream) {
+    return fused_launch("gf_sample_fused", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                        diag_add, cmax, t, t_bs, diag, diag_bs, eps, eps_bs, d, out, nullptr,
+                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, true);
 }
 
 int gf_chunk_sweep(int B, int64_t N, int64_t chunk_len, int nch, int chunk_first, int chunk_count,

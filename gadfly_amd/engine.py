@@ -1200,6 +1200,65 @@ class StreamingBatch:
         _lib.check(st, "gf_loglike_finish")
         return out
 
+    def _fused_refusal(self):
+        """Why neither fused sweep takes this batch (None when one does): what a caller that has no slower
+        route to offer -- the sampling pass -- puts into its error."""
+        if self._fused_ok() or self._wide_ok():
+            return None
+        if not (self.allow_fused or self.allow_wide):
+            return (f"the fused sweeps take W <= 63 with any mix of terms and 64 <= W <= 176 with complex terms "
+                    f"only (here W = {self.W}, Jr = {self.Jr}, Jc = {self.Jc})")
+        return (f"the fused sweeps need phases max|d| * max|t| < {SINCOS_RANGE:g} rad "
+                f"(here {float(self._pack[6]) * self._tmax:.3g})")
+
+    @_on_device
+    def sample_fused(self, eps, out):
+        """One draw per problem, ``out = L D^{1/2} eps`` with K = L D L^T, by gf_sample_fused: the tile loop of
+        :meth:`_log_likelihood_fused` with the draw carried in the pad column that carries the forward solve there,
+        no factor stored and no reductions except min d.  ``eps``, ``out``: (B, N) float64 device views with unit
+        row stride and the SAME batch stride (``eps`` readable three elements past its last row).  Block, span and
+        generator period are the pack's and the engine's, unchanged.  Returns ``(dmin, info)``: the smallest pivot
+        per problem and the 1-based failing row (0: none; the rows of ``out`` from there on are then undefined).
+        No host synchronisation."""
+        reason = self._fused_refusal()
+        if reason is not None:
+            raise NotImplementedError("batched sampling runs on the fused sweeps only: " + reason)
+        torch = self.torch
+        lib, p = self.lib, _lib.ptr
+        T, N, B = self.tile_rows, self.N, self.B
+        for x in (eps, out):
+            if (x.dtype != torch.float64 or x.device != self.device or tuple(x.shape) != (B, N)
+                    or (N > 1 and x.stride(1) != 1)):
+                raise ValueError("dimension mismatch")
+        bs = int(eps.stride(0)) if B > 1 else max(int(eps.stride(0)), N)
+        if B > 1 and (int(out.stride(0)) != bs or bs < N):
+            raise ValueError("eps and out must share one batch stride")
+        main = torch.cuda.current_stream(self.device)
+        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack
+        period, variant = int(self.generator_period), int(self.sweep_variant)
+        if stream_block:                    # the long scaling span (one-wave sweeps, amplitudes in range)
+            block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
+        self.S_state.zero_()
+        self.F_state.zero_()
+        info = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        self.kernel_used = "sample-wide" if self.W > 63 else "sample"
+        dmin = None
+        for k in range((N + T - 1) // T):
+            n0 = k * T
+            rows = min(T, N - n0)
+            st = lib.gf_sample_fused(
+                B, rows, n0, self.Jr, self.Jc, block, period, variant,
+                p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
+                p(diag_add), p(cmax), p(self.t), self._bs(self.t),
+                p(self.diag), 0 if self.diag is None else self._bs(self.diag),
+                p(eps), bs, p(self.d), p(out),
+                p(self.S_state), p(self.F_state), p(info), main.cuda_stream)
+            _lib.check(st, "gf_sample_fused")
+            # (rows of a problem that has failed are stale here: its info says so, its dmin means nothing)
+            m = self.d.view(-1)[:B * rows].view(B, rows).amin(dim=1)
+            dmin = m if dmin is None else torch.minimum(dmin, m)
+        return dmin, info
+
     # -- exact time-parallel evaluation (few problems, long series) ------------------------
     #: two-sweep evaluations of at most this many rows in all (B N), at widths beyond 48, run on ~1024 chunks instead of ~2048
     two_sweep_small_rows = 1_500_000

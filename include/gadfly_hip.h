@@ -184,6 +184,34 @@ int gf_loglike_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int bloc
                      int32_t *info, void *stream);
 
 /*
+ * Fused sampling sweep: B draws y = L D^1/2 eps of B different kernels, K = L D L^T, in the sweep that factors
+ * -- no factor is stored (24 B read, 16 B written per row: t, diag, eps; d, out).  Replaces celerite2's
+ * driver.matmul_lower with V := W after driver.factor (the reference's GaussianProcess.sample, gp.py:391) for
+ * one realisation per kernel.  The pad column that carries gf_loglike_fused's forward solve carries the draw:
+ *     x_n = sqrt(d_n) eps_n (correctly rounded sqrt),  F_n = P_n (F_{n-1} + W_{n-1} x_{n-1}),  out_n = x_n + U_n^T F_n.
+ * Arguments and conventions are gf_loglike_fused's -- tiles through n_first with S_state / F_state carried
+ * between the calls (zeroed by the caller before the first), block, gen_period, variant (GF_SWEEP_LONG_SPAN
+ * included), t / diag / eps readable three elements past row n_first + N - 1, info -- with two differences:
+ *   eps  (in)  the standard normals, WHOLE series (global row index, batch stride eps_bs), where y stands;
+ *   out  (out) the draw, WHOLE series too: row n_first + n of problem b goes to out[b * eps_bs + n_first + n]
+ *              (eps's batch stride, which must be >= 1 when B > 1) -- unlike z, which gf_loglike_fused writes
+ *              tile-local: the draw is the product, not an intermediate.
+ * d (out) is tile-local, (B, N), as in gf_loglike_fused: the caller takes min d from it for the generator-period
+ * rule.  A problem whose pivot fails leaves its 1-based global row in info and stops; what its out rows hold
+ * from there on is undefined (the caller blanks them).  Takes every term structure gf_fused_supported accepts:
+ * W <= 63 with any mix of terms, 64 <= W <= 176 with complex terms only.
+ */
+int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                    int gen_period, int variant,
+                    const double *ar, const double *cr, const double *ac,
+                    const double *bc, const double *cc, const double *dc,
+                    const double *diag_add, const double *cmax,
+                    const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                    const double *eps, int64_t eps_bs,
+                    double *d, double *out, double *S_state, double *F_state,
+                    int32_t *info, void *stream);
+
+/*
  * Exact time-parallel evaluation of ONE long series (or a few): the N rows are cut into nch
  * chunks of chunk_len rows (a multiple of `block`; the last chunk may be shorter) that are swept
  * concurrently, then stitched with an exact linear-fractional combine:

@@ -3,6 +3,7 @@
     python tools/isa_rows.py                       # k_factor7<60, false>: compile gadfly_hip.hip and count
     python tools/isa_rows.py --asm out.s           # count an existing `hipcc --cuda-device-only -S` listing
     python tools/isa_rows.py --kernel k_factor7 --rows 40 --rowstore
+    python tools/isa_rows.py --kernel k_factorw --rows 44 --sample   # the sampling instance (gf_sample_fused)
 
 Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
 most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
@@ -27,12 +28,19 @@ def compile_asm(out):
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 
 
-def kernel_body(lines, kernel, rows, rowstore):
-    # mangled: ..._19k_factor7ILi60ELb0EEEv...  (template <int ROWS, bool ROWSTORE>)
-    tag = f"{len(kernel)}{kernel}ILi{rows}E" + (f"Lb{int(rowstore)}E" if rowstore is not None else "")
+def kernel_tag(kernel, rows, rowstore, sample):
+    # mangled: ..._19k_factor7ILi60ELb0ELb0EEEv...  (template <int ROWS, bool ROWSTORE, bool SAMPLE>); k_factorw has a
+    # second integer (its sweep waves) and k_factor3 / k_factorw no ROWSTORE.  The whole argument list is matched.
+    mid = r"Li\d+E" if kernel == "k_factorw" else (f"Lb{int(rowstore)}E" if rowstore is not None else "")
+    smp = f"Lb{int(sample)}E" if kernel in ("k_factor3", "k_factor7", "k_factorw") else ""
+    return re.compile(f"{len(kernel)}{kernel}ILi{rows}E{mid}{smp}E")
+
+
+def kernel_body(lines, kernel, rows, rowstore, sample=False):
+    tag = kernel_tag(kernel, rows, rowstore, sample)
     start = None
     for i, ln in enumerate(lines):
-        if start is None and re.match(r"^_Z\S+:", ln) and tag in ln.split(":")[0]:
+        if start is None and re.match(r"^_Z\S+:", ln) and tag.search(ln.split(":")[0]):
             start = i
         elif start is not None and ln.startswith(".Lfunc_end"):
             return lines[start:i]
@@ -97,6 +105,7 @@ def main():
     ap.add_argument("--kernel", default="k_factor7")
     ap.add_argument("--rows", type=int, default=60)
     ap.add_argument("--rowstore", action="store_true", help="the ROWSTORE = true instance (k_factor7 only)")
+    ap.add_argument("--sample", action="store_true", help="the SAMPLE = true instance (the sampling sweeps)")
     ap.add_argument("--all", action="store_true", help="also print blocks outside loops")
     a = ap.parse_args()
     asm = a.asm
@@ -105,13 +114,14 @@ def main():
         compile_asm(asm)
     lines = open(asm).read().splitlines()
     rowstore = (a.rowstore if a.kernel == "k_factor7" else None)
-    body = kernel_body(lines, a.kernel, a.rows, rowstore)
+    body = kernel_body(lines, a.kernel, a.rows, rowstore, a.sample)
+    tag = kernel_tag(a.kernel, a.rows, rowstore, a.sample)
     bl = blocks(body)
     vgpr = next((ln.split(",")[-1].strip() for ln in lines
-                 if ".num_vgpr," in ln and f"{a.kernel}ILi{a.rows}E" in ln
-                 and (rowstore is None or f"Lb{int(rowstore)}E" in ln)), "?")
+                 if ".num_vgpr," in ln and tag.search(ln)), "?")
     total = counts([op for b in bl for op in b["ins"]])
-    print(f"{a.kernel}<{a.rows}{'' if rowstore is None else ', ' + str(rowstore).lower()}>: {len(bl)} blocks, "
+    print(f"{a.kernel}<{a.rows}{'' if rowstore is None else ', ' + str(rowstore).lower()}>"
+          f"{' (sampling)' if a.sample else ''}: {len(bl)} blocks, "
           f"{total['valu']} VALU, {total['lds']} LDS, {total['scratch']} scratch (spill) in all; {vgpr} VGPRs")
     reg = max(range(len(bl)), key=lambda i: counts(bl[i]["ins"])["fma"])
     i0, i1 = row_loop(bl, reg) if not a.all else (0, len(bl) - 1)
