@@ -317,6 +317,32 @@ def batch_calibration(prob, orc0=None):
     return tp, two, product_period(coeffs, prob["t"], cond * (SB.TWO_SWEEP_MARGIN if two else 1.0))
 
 
+def grad_problem(seed):
+    """test_gpu_grad_random.py's problem: B = 2-6 walkers around a base kernel of J 1-30 SHO terms (a shared overdamped
+    pattern; W = 2J <= 60, the gradient kernel's one-wave range), exposure 0.1-1 cadence, N = 40-1500 rows on an axis of
+    AXES (the QMODE_PHASE-crossing one placed by walker 0's rates), white noise of 5-100 % of the kernel's amplitude:
+    well conditioned by construction (test_grad_host.py checks max(a) / min(d) <= 1e4 for every walker), so no seed
+    and no walker is ever skipped."""
+    rng = _rng(seed)
+    J = int(rng.integers(1, 31))
+    n_over = int(rng.integers(1, min(J, 3) + 1)) if rng.random() < 0.35 else 0
+    base = _base_terms(rng, J, n_over)
+    B = int(rng.integers(2, 7))
+    S0, w0, Q = _walkers(rng, base, B)
+    assert np.all((Q < 0.5) == (base[2] < 0.5)[None, :])
+    dt = float(np.exp(rng.uniform(np.log(2e-5), np.log(2e-3))))
+    delta = float(rng.uniform(0.1, 1.0)) * dt
+    N = int(rng.integers(40, 1501))
+    kind = str(rng.choice(AXES))
+    co = sho_kernels(S0[:1], w0[:1], Q[:1], delta)[0].get_device_coefficients()
+    t = _axis(rng, N, dt, kind, w_cross=wmax(co))
+    amp = float(np.sqrt(np.sum(base[0] * base[1] * base[2])))
+    yerr = amp * float(np.exp(rng.uniform(np.log(0.05), 0.0)))
+    y = amp * rng.normal(size=N) + np.cumsum(rng.normal(size=N)) * 0.1 * amp
+    return dict(S0=S0, w0=w0, Q=Q, delta=delta, t=t, y=y, yerr=yerr, diag_user=np.full(N, yerr ** 2), kind=kind,
+                J=J, B=B, N=N, n_over=n_over, rng=rng)
+
+
 def wide_problem(seed):
     """A wide kernel (J 32-88 SHO terms, W = 64 ... 176 after the overdamped terms' complexification; 40 % of the
     seeds with 1-3 overdamped terms) and TWO walkers with different coefficients (+-2 ... 30 %) on a uniform,

@@ -1,13 +1,16 @@
 """CPU: the host side of the log-likelihood gradient -- the torch coefficient pack against the numpy
 one, the numpy reverse pass (tests/grad_ref.py) against dense autograd, and the pack's vector-Jacobian product
-against central differences."""
+against central differences; the two oracles against each other at the edge shapes of tests/grad_cases.py, the float64
+pass against the 80-bit one on far time axes, and what the seeds of random_cases.grad_problem cover."""
 import numpy as np
 import pytest
 import torch
 
 from gadfly_amd.batch import sho_coefficient_pack
 from gadfly_amd.grad import check_pack_batch, parameter_vjp, sho_coefficient_pack_torch
-from tests.grad_ref import batch_grad, dense_loglike
+from tests import grad_cases as gc
+from tests import random_cases as rc
+from tests.grad_ref import batch_grad, dense_loglike, loglike_grad
 
 
 def _params(rng, B, J, n_over=0):
@@ -117,3 +120,73 @@ def test_pack_of_another_batch_size_is_refused():
         check_pack_batch(5, Jr, Jc, real[:, :, :1], comp, diag_add)      # a term column short
     with pytest.raises(ValueError, match="batch"):
         check_pack_batch(5, Jr, Jc, real, comp, diag_add[:4])
+
+
+@pytest.mark.parametrize("Jr,Jc", gc.STRUCTURES)
+def test_numpy_reverse_pass_matches_dense_coefficient_autograd(Jr, Jc):
+    """Every width at a register-layout boundary of the device kernel, odd ones included, at every length where its
+    segments end: the numpy pass the device is compared with is itself right there."""
+    worst = 0.0
+    for N in gc.LENGTHS:
+        prob = gc.edge_problem(Jr, Jc, N, B=1)
+        co = gc.coefficients(prob, 0)
+        ll, g = loglike_grad(prob["t"], prob["y"][0], prob["diag"][0], Jr, Jc, *co, prob["diag_add"][0])
+        lld, gd = gc.dense_grad(prob, 0)
+        errs = [abs(ll - lld) / abs(lld)] + [gc.scaled_error(c, g[k], gd[k]) for k, c in zip(gc.NAMES, co)]
+        errs += [abs(g[k] - gd[k]) / max(1.0, abs(gd[k])) for k in ("mean", "diag_add")]
+        assert max(errs) <= 1e-9, (N, errs)
+        worst = max(worst, max(errs))
+    print(f"(Jr, Jc) = ({Jr}, {Jc}): numpy pass vs dense autograd {worst:.1e}")
+
+
+def _walker0(prob):
+    """(t, y, diag, Jr, Jc, ar, cr, ac, bc, cc, dc, diag_add) of walker 0 of a random_cases.grad_problem."""
+    Jr, Jc, real, comp, diag_add, _ = sho_coefficient_pack(prob["S0"][:1], prob["w0"][:1], prob["Q"][:1], prob["delta"])
+    return (prob["t"], prob["y"], prob["diag_user"], Jr, Jc, real[0, 0], real[1, 0], comp[0, 0], comp[1, 0],
+            comp[2, 0], comp[3, 0], diag_add[0])
+
+
+@pytest.mark.parametrize("seed", [512, 520])
+def test_far_axis_dc_adjoint(seed):
+    """On a BKJD or QMODE_PHASE-crossing axis the float64 pass stays within 1e-8 of the 80-bit one in every adjoint
+    -- with dc's summed as sum (t_n - t_0) thbar_n.  Summed as sum t_n thbar_n it does not (> 1e-7 on both seeds):
+    sum thbar_n is zero analytically (rotating all phases of a term leaves K unchanged), rounding residue in
+    float64, and t_0 multiplies it."""
+    prob = rc.grad_problem(seed)
+    assert prob["kind"] in ("bkjd", "qcross")
+    args = _walker0(prob)
+    co = [np.asarray(x)[:n] for x, n in zip(args[5:11], (args[3],) * 2 + (args[4],) * 4)]
+    ll, g = loglike_grad(*args)
+    ll80, g80 = loglike_grad(*args, dtype=np.longdouble)
+    assert abs(ll - float(ll80)) <= 1e-9 * abs(float(ll80))
+    for k, c in zip(gc.NAMES, co):
+        err = gc.scaled_error(c, g[k], np.asarray(g80[k], dtype=np.float64))
+        print(f"seed {seed} ({prob['kind']}) {k}: float64 vs 80-bit {err:.1e}")
+        assert err <= 1e-8, (k, err)
+    # the plain association on the float64 pass's own rows
+    plain = np.sum(np.asarray(args[0])[:, None] * g["phase_rows"], axis=0)
+    err = gc.scaled_error(co[5], plain, np.asarray(g80["dc"], dtype=np.float64))
+    print(f"seed {seed} ({prob['kind']}) dc summed as sum t_n thbar_n: {err:.1e}")
+    assert err > 1e-7, err
+
+
+def test_grad_problem_seeds_are_well_conditioned_and_cover_every_axis_and_width():
+    """What tests/test_gpu_grad_random.py relies on when it skips no seed and no walker: the C oracle factors every
+    walker of seeds 500-531, at conditions max(a) / min(d) <= 1e4 (where float64 holds the bars on any axis), and the
+    seeds reach all five axis kinds and the smallest and largest widths (W = 2 and W = 60)."""
+    kinds, widths, worst = set(), set(), 0.0
+    for seed in range(500, 532):
+        p = rc.grad_problem(seed)
+        assert 2 <= p["B"] <= 6 and 1 <= p["J"] <= 30 and 40 <= p["N"] <= 1500 and p["S0"].shape == (p["B"], p["J"])
+        over = p["Q"] < 0.5
+        assert np.all(over == over[0][None, :]) and over[0].sum() == p["n_over"]
+        assert np.all(np.isfinite(p["t"])) and np.all(np.diff(p["t"]) > 0)
+        coeffs = [k.get_device_coefficients() for k in rc.sho_kernels(p["S0"], p["w0"], p["Q"], p["delta"])]
+        orc = rc.oracle_problems(coeffs, p["t"], p["diag_user"], p["y"])
+        assert np.all(orc["info"] == 0), (seed, orc["info"])
+        assert orc["cond"].max() <= 1e4, (seed, orc["cond"])
+        worst = max(worst, float(orc["cond"].max()))
+        kinds.add(p["kind"])
+        widths.add(2 * p["J"])
+    print(f"grad_problem seeds 500-531: largest condition {worst:.1e}")
+    assert kinds == set(rc.AXES) and {2, 60} <= widths, (kinds, sorted(widths))
