@@ -11,7 +11,8 @@ from .core import (  # noqa: F401
 )
 from . import scale  # noqa: F401
 from .gp import GaussianProcess, ConditionalDistribution, LinAlgError  # noqa: F401
-from .batch import BatchedLogLikelihood, log_likelihood_batch, BatchedSampler, sample_batch  # noqa: F401
+from .batch import (BatchedLogLikelihood, log_likelihood_batch, BatchedSampler, sample_batch,  # noqa: F401
+                    predict_batch)
 from . import terms  # noqa: F401
 from .psd import PowerSpectrum, bin_power_spectrum  # noqa: F401
 from .interp import interpolate_missing_data, stitch_quarters  # noqa: F401

@@ -18,7 +18,8 @@ SO_PATH = os.path.join(CSRC, "libgadfly_hip.so")
 if os.environ.get("GADFLY_SO"):                 # another build of the same library (A/B measurements)
     SO_PATH = os.path.abspath(os.environ["GADFLY_SO"])
 SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dense.hip"),
-           os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip")]
+           os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip"),
+           os.path.join(CSRC, "gadfly_solve.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -28,6 +29,8 @@ GF_SWEEP_LONG_SPAN = 0x200
 GF_MAX_WIDTH = 256
 GF_GRAD_MAX_WIDTH = 63          # gf_loglike_grad: one wave per problem
 GF_GRAD_WORKSPACE_BYTES = 16 << 30   # default cap on gf_loglike_grad's workspace per call (batches run in groups)
+GF_SOLVE_MAX_WIDTH = 63         # gf_solve_batch: one wave per problem (kernel and component alike)
+GF_SOLVE_WORKSPACE_BYTES = 16 << 30  # default cap on gf_solve_batch's workspace per call
 
 _lib = None
 
@@ -106,6 +109,10 @@ SIGNATURES = {
     "gf_grad_work": (_i64, [_i64, _int]),
     "gf_loglike_grad": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
                         + [_vp] * 6 + [_vp]),
+    "gf_solve_batch_seg": (_i64, [_i64, _int]),
+    "gf_solve_batch_work": (_i64, [_i64, _int, _i64]),
+    "gf_solve_batch": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_int, _int] + [_vp] * 6
+                       + [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64] + [_vp] * 5 + [_vp]),
     "gf_general_matmul_work": (_i64, [_int, _i64, _i64, _int]),
     "gf_general_matmul": (_int, [_int, _i64, _i64, _int, _int, _vp,
                                  _vp, _i64, _vp, _vp,

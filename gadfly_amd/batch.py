@@ -22,7 +22,7 @@ from . import _lib
 from .engine import StreamingBatch
 
 __all__ = ["BatchedLogLikelihood", "log_likelihood_batch", "sho_coefficient_pack",
-           "BatchedSampler", "sample_batch"]
+           "BatchedSampler", "sample_batch", "predict_batch"]
 
 
 def sho_coefficient_pack(S0, w0, Q, delta, eps=1e-5):
@@ -224,6 +224,7 @@ class BatchedLogLikelihood:
                                              dtype=torch.float64, device=eng.device)
             self._diag_nonneg = dmin_real >= 0.0
             self._dt_min, self._t_abs_max = dt_min, tabs
+            self._mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), (len(kernels),)).copy()
             self._finish_init(kernels)
             return
         t = np.ascontiguousarray(t, dtype=np.float64)
@@ -247,6 +248,7 @@ class BatchedLogLikelihood:
         #: only while no two stamps are closer than its exposure time (see _sho_only)
         self._dt_min = float(np.min(np.diff(t, axis=-1))) if t.shape[-1] > 1 else None
         self._t_abs_max = float(np.max(np.abs(t))) if t.size else 0.0
+        self._mean = np.asarray(mean, dtype=np.float64)
         self._finish_init(kernels)
 
     def _finish_init(self, kernels):
@@ -264,6 +266,10 @@ class BatchedLogLikelihood:
         self.auto_generator_period = True
         #: evaluations whose accuracy guard has not been looked at yet: (out, flag, pack, period)
         self._unresolved = []
+        #: host coefficients of the kernels of construction (what :meth:`predict` takes when given none); a
+        #: complexified batch (W > 63) is beyond :meth:`predict` anyway
+        eng = self.engine
+        self._pack0 = None if eng._complexified else tuple(eng._struct0) + tuple(eng._coeff_host[:3])
         #: evaluations repeated with exact generator rows by the guard so far
         self.guard_reruns = 0
         self._last_cond = None
@@ -353,6 +359,68 @@ class BatchedLogLikelihood:
         if "diag" in wrt:
             out["diag"] = g["diag_add"]
         return ll, out
+
+    #: cap on the workspace of one :meth:`predict` call in bytes: larger batches run in groups
+    predict_workspace_bytes = _lib.GF_SOLVE_WORKSPACE_BYTES
+
+    def predict_device(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False):
+        """Conditional means of the B problems at their observed times in one device call: what
+        ``GaussianProcess(kernel_b, t, yerr).predict(y)`` gives one kernel at a time -- mu = y - diag alpha with
+        alpha = K^-1 (y - mean) -- as a float64 device tensor (B, N); a ragged batch returns a list of B tensors cut
+        to each series' rows.  Nothing is copied back (no host synchronisation).
+
+        ``pack_or_kernels``: a list of B kernels, a host pack (:func:`sho_coefficient_pack`) or a device pack
+        (:meth:`pack`, :meth:`pack_parameters`); None: the kernels of construction.  ``kernel``: the part of the
+        kernel whose share of the data is wanted (``predict(y, kernel=component)``: K'(t, t) alpha, the component's
+        exposure shift not added) -- a list of B component kernels, one kernel for all problems or a host pack, all
+        of one term structure.  ``include_mean=False`` leaves the mean out of the result.  ``return_alpha``: also
+        alpha, ``(mu, alpha)``.  A problem whose matrix is not positive definite gets NaN in all its rows (the
+        others are unaffected); :attr:`last_predict_ll` holds the log-likelihoods (-inf there) and
+        :attr:`last_predict_info` the failing rows, both on the device.  Kernels or components wider than W = 63
+        raise ``NotImplementedError``."""
+        from .predict import check_width, component_pack, solve_batch
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        component = None if kernel is None else component_pack(kernel, self.B)
+        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
+        res = solve_batch(eng, Jr, Jc, real, comp, diag_add, component, self.predict_workspace_bytes,
+                          want_alpha=return_alpha, want_mu=component is None)
+        #: (workspace bytes of a group, number of groups, problems per group) and the HIP events of the last call
+        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self._predict_events = res["events"]
+        self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
+        self.last_predict_info = res["info"]
+        mu = res["mu"] if component is None else res["mu_comp"]
+        torch = eng.torch
+        if include_mean and np.any(self._mean != 0.0):
+            # (whatever y - mean broadcast at construction: a scalar, (N,), (B, 1) or (B, N); ragged: one per problem)
+            m = self._mean[:, None] if self.rows is not None else self._mean
+            m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
+            mu += torch.as_tensor(m, dtype=torch.float64, device=eng.device)
+        if self.rows is not None:
+            mu = [mu[b, :int(n)] for b, n in enumerate(self.rows)]
+            alpha = None if res["alpha"] is None else [res["alpha"][b, :int(n)] for b, n in enumerate(self.rows)]
+        else:
+            alpha = res["alpha"]
+        return (mu, alpha) if return_alpha else mu
+
+    @property
+    def last_predict_device_ms(self):
+        """Summed device time of the last :meth:`predict_device` call's launches (synchronises)."""
+        for _, e1 in self._predict_events:
+            e1.synchronize()
+        return sum(a.elapsed_time(b) for a, b in self._predict_events)
+
+    def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False):
+        """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch)."""
+        out = self.predict_device(pack_or_kernels, kernel=kernel, include_mean=include_mean,
+                                  return_alpha=return_alpha)
+
+        def host(x):
+            return [v.cpu().numpy() for v in x] if isinstance(x, list) else x.cpu().numpy()
+
+        return tuple(host(x) for x in out) if return_alpha else host(out)
 
     def evaluate_device(self, pack=None):
         """Enqueue one evaluation per problem; returns the (B,) device tensor (no host sync).
@@ -485,6 +553,14 @@ def log_likelihood_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, device=N
     positive definite (celerite2's ``quiet=True`` convention)."""
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
                                 device=device).evaluate()
+
+
+def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, device=None):
+    """One-shot form of :meth:`BatchedLogLikelihood.predict`: the conditional means of B problems at their observed
+    times as numpy, (B, N) or a list of B arrays for ragged ``t``; ``kernel=`` selects the share of one part of the
+    kernel (a list of B components, or one for all)."""
+    return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
+                                device=device).predict(kernel=kernel)
 
 
 def _is_series_list(x):

@@ -1,0 +1,125 @@
+"""
+Conditional means of batched problems.
+
+The device computes alpha = K^-1 (y - mean), mu = y - diag alpha and, optionally, the share of the data one part of
+the kernel explains for B problems at once (``gf_solve_batch``: a checkpointed forward sweep and the upper solve
+backwards, no stored factor); this module sizes its workspace, splits a batch into groups under a byte cap (a
+problem's result does not depend on the group it lands in) and stacks the component's coefficients.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .grad import check_pack_batch
+
+__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "DEFAULT_WORKSPACE_BYTES"]
+
+#: default cap on the workspace of one call (the batch is split into groups beneath it)
+DEFAULT_WORKSPACE_BYTES = _lib.GF_SOLVE_WORKSPACE_BYTES
+
+
+def check_width(W, what="this kernel"):
+    """The one-wave solve kernel's width limit: NotImplementedError beyond it."""
+    if W > _lib.GF_SOLVE_MAX_WIDTH:
+        raise NotImplementedError(
+            f"batched conditional means take celerite widths W <= {_lib.GF_SOLVE_MAX_WIDTH} (one wave per problem); "
+            f"{what} has W = {W}")
+
+
+def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0):
+    """(doubles per problem, problems per group, number of groups) of a gf_solve_batch call."""
+    check_width(W)
+    per = int(_lib.load().gf_solve_batch_work(int(N), int(W), int(seg)))
+    if per <= 0:
+        raise ValueError(f"no solve workspace for N = {N}, W = {W}, seg = {seg}")
+    group = int(max(1, min(B, int(cap_bytes) // (8 * per))))
+    return per, group, (B + group - 1) // group
+
+
+def component_pack(kernel, B):
+    """Stacked host coefficients (Jr', Jc', real', comp') of a component for B problems from a list of B kernels, one
+    kernel for all problems, or a host pack (``sho_coefficient_pack``, ``engine._coeff_pack``) of B (or one) rows.
+    ValueError when the list does not hold B kernels or they do not share one term structure; NotImplementedError
+    when the component is wider than one wave."""
+    from .engine import _coeff_pack
+    if isinstance(kernel, tuple) and len(kernel) >= 4 and isinstance(kernel[0], (int, np.integer)):
+        Jr, Jc = int(kernel[0]), int(kernel[1])
+        real, comp = np.asarray(kernel[2], dtype=np.float64), np.asarray(kernel[3], dtype=np.float64)
+        if real.ndim != 3 or comp.ndim != 3 or real.shape[1] != comp.shape[1] or real.shape[1] not in (1, B):
+            raise ValueError("dimension mismatch")
+        if real.shape[1] == 1 and B > 1:
+            real, comp = np.repeat(real, B, axis=1), np.repeat(comp, B, axis=1)
+    else:
+        if hasattr(kernel, "get_device_coefficients"):
+            kernel = [kernel] * B
+        kernel = list(kernel)
+        if len(kernel) != B:
+            raise ValueError(f"kernel= holds {len(kernel)} components for a batch of {B} problems")
+        Jr, Jc, real, comp, _, _ = _coeff_pack([k.get_device_coefficients() for k in kernel])
+    if Jr + 2 * Jc < 1:
+        raise ValueError("the component has no terms")
+    check_width(Jr + 2 * Jc, "the component")
+    check_pack_batch(B, Jr, Jc, real, comp, np.zeros(B))
+    return Jr, Jc, np.ascontiguousarray(real), np.ascontiguousarray(comp)
+
+
+def solve_batch(engine, Jr, Jc, real, comp, diag_add, component=None, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0,
+                want_alpha=True, want_mu=True):
+    """Enqueue ``gf_solve_batch`` over an engine's data (t, y - mean, diag on the device) for stacked host coefficient
+    arrays of its ORIGINAL term structure; ``component`` = (Jr', Jc', real', comp') or None.  Returns a dict of
+    device tensors -- ``alpha``, ``mu``, ``mu_comp`` ((B, N) each, None where not asked for), ``ll`` (B,), ``info``
+    (B,) -- with the plan (``workspace_bytes``, ``groups``, ``group_size``) and ``events``, one pair of HIP events
+    around each launch.  Nothing is copied back: no host synchronisation."""
+    W = Jr + 2 * Jc
+    if (Jr, Jc) != engine._struct0:
+        raise ValueError("coefficient pack does not match the batch structure")
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, diag_add)
+    per, group, ngroups = workspace_plan(N, W, B, cap_bytes, seg)
+    lib, p = engine.lib, _lib.ptr
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    jr2 = jc2 = 0
+    if component is not None:
+        jr2, jc2, real2, comp2 = component
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        work = torch.empty((group * per,), **f64)
+        ll = torch.empty((B,), **f64)
+        info = torch.zeros((B,), dtype=torch.int32, device=dev)
+        alpha = torch.empty((B, N), **f64) if want_alpha else None
+        mu = torch.empty((B, N), **f64) if want_mu else None
+        mu_comp = torch.empty((B, N), **f64) if component is not None else None
+        real = np.ascontiguousarray(real, dtype=np.float64)
+        comp = np.ascontiguousarray(comp, dtype=np.float64)
+        diag_add = np.ascontiguousarray(diag_add, dtype=np.float64)
+        t, y, dg = engine.t, engine.y, engine.diag
+        tbs, ybs = engine._bs(t), engine._bs(y)
+        dbs = 0 if dg is None else engine._bs(dg)
+        at = lambda x, off: None if x is None else x.data_ptr() + off      # noqa: E731
+        events = []
+        for b0 in range(0, B, group):
+            nb = min(group, B - b0)
+            cr_ = torch.as_tensor(np.ascontiguousarray(real[:, b0:b0 + nb]), **f64)
+            cc_ = torch.as_tensor(np.ascontiguousarray(comp[:, b0:b0 + nb]), **f64)
+            da = torch.as_tensor(diag_add[b0:b0 + nb], **f64)
+            c2 = [None] * 6
+            if component is not None:
+                r2_ = torch.as_tensor(np.ascontiguousarray(real2[:, b0:b0 + nb]), **f64)
+                c2_ = torch.as_tensor(np.ascontiguousarray(comp2[:, b0:b0 + nb]), **f64)
+                c2 = [p(r2_[0]), p(r2_[1]), p(c2_[0]), p(c2_[1]), p(c2_[2]), p(c2_[3])]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            st = lib.gf_solve_batch(
+                nb, N, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]), p(da),
+                jr2, jc2, *c2,
+                t.data_ptr() + 8 * b0 * tbs, tbs,
+                None if dg is None else dg.data_ptr() + 8 * b0 * dbs, dbs,
+                y.data_ptr() + 8 * b0 * ybs, ybs, int(seg), p(work), per,
+                at(alpha, 8 * b0 * N), at(mu, 8 * b0 * N), at(mu_comp, 8 * b0 * N),
+                ll.data_ptr() + 8 * b0, info.data_ptr() + 4 * b0, stream)
+            _lib.check(st, "gf_solve_batch")
+            e1.record()
+            events.append((e0, e1))
+        return dict(alpha=alpha, mu=mu, mu_comp=mu_comp, ll=ll, info=info, workspace_bytes=8 * per * group,
+                    groups=ngroups, group_size=group, events=events)

@@ -17,6 +17,8 @@
  *                                                      <- gp.py:232 (predict at new times)
  *   gf_loglike_grad     driver.factor_rev + solve_lower_rev + the norm's adjoint
  *                                                      (no gadfly call site: gradients for samplers)
+ *   gf_solve_batch      driver.factor + solve_lower + solve_upper + general_matmul_lower / _upper at t* = t
+ *                                                      <- gp.py:370, :232 for B kernels at once
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HIP) unless marked "host"; float64 throughout;
@@ -589,6 +591,40 @@ int gf_loglike_grad(int B, int64_t N, int Jr, int Jc,
                     const double *y, int64_t y_bs, double *work, int64_t work_bs,
                     double *ll, double *g_real, double *g_comp, double *g_diag, double *g_mean,
                     int32_t *info, void *stream);
+
+/*
+ * alpha = K^-1 y and the conditional means of B problems: what celerite2's
+ * GaussianProcess.apply_inverse (driver.factor + solve_lower + solve_upper) and predict(y[, kernel=component]) at the
+ * observed times (general_matmul_lower + general_matmul_upper at t* = t) give one kernel at a time, on the plain
+ * recurrence of oracle/celerite_ref.c with exact generator rows at every row.  One wave per problem; W = Jr + 2 Jc
+ * <= 63 and W' = Jr2 + 2 Jc2 <= 63 (-3 beyond).  No stored factor: a forward sweep with checkpoints every `seg` rows,
+ * then the upper solve backwards over segments recomputed from them.
+ *   coefficients, t, diag, y and their strides as gf_loglike_grad (A_n = diag[n] + diag_add; diag may be NULL)
+ *   component (optional): a second coefficient set ar2, cr2 [B][max(Jr2,1)]; ac2 .. dc2 [B][max(Jc2,1)].  Pass
+ *     Jr2 = Jc2 = 0 and mu_comp = NULL for none; a component and mu_comp go together (-1 otherwise)
+ *   seg: rows per segment, 0 = gf_solve_batch_seg(N, W) (values above N mean N).  Every output is bit-identical for
+ *     every seg
+ *   work: work_bs >= gf_solve_batch_work(N, W, seg) doubles per problem (checkpoints, one segment's staged rows,
+ *     z and D of every row); B * work_bs in all
+ *   alpha [B][N]    K^-1 y                                                   (may be NULL)
+ *   mu [B][N]       y - diag alpha: the observational diagonal only, not diag_add; diag = NULL gives y   (may be NULL)
+ *   mu_comp [B][N]  sum_m k'(t_n - t_m) alpha_m over ALL m, the coincident stamp with the earlier ones; the
+ *                   component's own diagonal shift is not added (celerite2's predict(y, kernel=...))
+ *   ll [B]          log-likelihood, -inf where a pivot is not positive (info = the 1-based failing row); every row of
+ *                   alpha, mu and mu_comp of such a problem is NaN
+ * No atomics: results are bit-identical from run to run and do not depend on the other problems of the call.
+ */
+int64_t gf_solve_batch_seg(int64_t N, int W);
+int64_t gf_solve_batch_work(int64_t N, int W, int64_t seg);
+int gf_solve_batch(int B, int64_t N, int Jr, int Jc,
+                   const double *ar, const double *cr, const double *ac, const double *bc,
+                   const double *cc, const double *dc, const double *diag_add,
+                   int Jr2, int Jc2,
+                   const double *ar2, const double *cr2, const double *ac2, const double *bc2,
+                   const double *cc2, const double *dc2,
+                   const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                   const double *y, int64_t y_bs, int64_t seg, double *work, int64_t work_bs,
+                   double *alpha, double *mu, double *mu_comp, double *ll, int32_t *info, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,125 @@
+#!/usr/bin/env python
+"""Latency of BatchedLogLikelihood.predict_device: one JSON line per leg and variant, medians of 5 calls
+-- (a) walkers B = 2048, N = 1e5, J = 30; (b) cfg3-shaped B = 256, N = 65 000, J = 20; (c) one star B = 1, N = 1e5,
+J = 30 -- each without and with a component (the first third of the terms).  `--shapes a,c` runs a subset, `--reps`
+sets the count, `--loop` the number of problems of the per-kernel loop (0 skips it).
+
+predict_device_ms: the gf_solve_batch launches alone (HIP events around each, summed over the groups);
+predict_api_ms: predict_device() and a device synchronise, wall time (coefficient pack and upload included);
+predict_numpy_ms: predict(), the results copied to the host as numpy, wall time of one call (what the loop returns);
+evaluate_device_ms: HIP events around evaluate_device(pack_parameters(...)) at generator_period = 1 on the same batch;
+loop_ms_per_problem: GaussianProcess(kernel_b, t, yerr).predict(y[, kernel=sub]) one kernel at a time, wall time
+per problem (median over `--loop` problems after one warm-up); loop_scaled_ms = that times B; speedup_over_loop =
+loop_scaled_ms / predict_numpy_ms."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import gadfly_amd  # noqa: E402
+from gadfly_amd.batch import sho_coefficient_pack  # noqa: E402
+from gadfly_amd.synth import solar_like_hyperparameters, uniform_times  # noqa: E402
+from gadfly_amd.terms import SHOTerm, TermConvolution, TermSum  # noqa: E402
+
+SHAPES = {"a": (2048, 100_000, 30), "b": (256, 65_000, 20), "c": (1, 100_000, 30)}
+
+
+def median_ms(fn, reps):
+    """Medians of (wall ms, value fn returns) over `reps` calls after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    ts, vs = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        vs.append(fn())
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)) * 1e3, float(np.median(vs))
+
+
+def device_span(fn):
+    """fn() enqueued between two HIP events: their elapsed time in ms."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def kernel_of(S0, w0, Q, delta, first=None):
+    return TermConvolution(TermSum(*[SHOTerm(S0=float(s), w0=float(w), Q=float(q))
+                                     for s, w, q in list(zip(S0, w0, Q))[:first]]), delta)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="a,b,c")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--loop", type=int, default=16)
+    args = ap.parse_args()
+    rng = np.random.Generator(np.random.PCG64(2024))
+    for name in args.shapes.split(","):
+        B, N, J = SHAPES[name]
+        kern = gadfly_amd.StellarOscillatorKernel(solar_like_hyperparameters(J), texp=60.0)
+        terms = kern.term.terms
+        base = [np.array([[getattr(tm, k) for tm in terms]]) for k in ("S0", "w0", "Q")]
+        # proposals around the kernel's own parameters (Q untouched: every proposal keeps its overdamped terms)
+        S0, w0 = (np.repeat(b, B, axis=0) * np.exp(0.05 * rng.normal(size=(B, J))) for b in base[:2])
+        Q = np.repeat(base[2], B, axis=0)
+        t = uniform_times(N, 60.0)
+        y = 100.0 * rng.normal(size=N)
+        delta = float(kern.delta)
+        first = J // 3
+        ev = gadfly_amd.BatchedLogLikelihood([kern] * B, t, y, yerr=30.0)
+        ev.auto_generator_period = False
+        ev.engine.generator_period = 1
+        run_ev = lambda: ev.evaluate_device(ev.pack_parameters(S0, w0, Q, delta))       # noqa: E731
+        _, ev_dev = median_ms(lambda: device_span(run_ev), args.reps)
+        ev.resolve()
+        pack = sho_coefficient_pack(S0, w0, Q, delta)
+        sub = sho_coefficient_pack(S0[:, :first], w0[:, :first], Q[:, :first], delta)
+        nloop = min(args.loop, max(B, 1)) if B > 1 else args.loop
+        for comp in (False, True):
+            def run_predict():
+                ev.predict_device(pack, kernel=sub if comp else None)
+                return ev.last_predict_device_ms
+
+            api, dev = median_ms(run_predict, args.reps)
+            ws, groups, group_size = ev.last_predict_plan
+            rec = dict(shape=name, B=B, N=N, J=J, W=2 * J, component_W=2 * first if comp else 0,
+                       predict_device_ms=round(dev, 2), predict_api_ms=round(api, 2),
+                       evaluate_device_ms=round(ev_dev, 3), ratio_to_evaluate=round(dev / ev_dev, 2),
+                       workspace_bytes=int(ws), groups=int(groups), group_size=int(group_size), reps=args.reps)
+            # the whole call as the loop's caller sees it: results on the host as numpy (one call)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev.predict(pack, kernel=sub if comp else None)
+            rec["predict_numpy_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+            if nloop > 0:
+                walls = []
+                for b in range(nloop + 1):                      # (the first problem warms up and is dropped)
+                    i = b % B
+                    kb = kernel_of(S0[i], w0[i], Q[i], delta)
+                    sb = kernel_of(S0[i], w0[i], Q[i], delta, first) if comp else None
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    gp = gadfly_amd.GaussianProcess(kb, t=t, yerr=30.0, device="cuda:0")
+                    gp.predict(y, kernel=sb)
+                    walls.append(time.perf_counter() - t0)
+                    del gp
+                per = float(np.median(walls[1:])) * 1e3
+                rec.update(loop_problems=nloop, loop_ms_per_problem=round(per, 2), loop_scaled_ms=round(per * B, 1),
+                           speedup_over_loop=round(per * B / rec["predict_numpy_ms"], 2))
+            print(json.dumps(rec), flush=True)
+        del ev
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
