@@ -5958,16 +5958,19 @@ int gf_cross_covariance(int B, int64_t N, int R, int Jr, int Jc,
     if (Jr < 0 || Jc < 0 || Jr + Jc < 1 || Jr + 2 * Jc > GF_MAX_WIDTH) return set_err("gf_cross_covariance: bad term counts%s", "");
     if (!t || !ts || !out || (Jr && (!ar || !cr)) || (Jc && (!ac || !bc || !cc || !dc)))
         return set_err("gf_cross_covariance: null pointer%s", "");
-    // queries per pass (accumulators per lane) so that the table of (term, query) factors fits 48 KB of LDS
+    // queries per pass (accumulators per lane) so that the table of (term, query) factors fits 48 KB of LDS up to
+    // J = 92 and, with the kernel's 88 static bytes, the 64 KB a launch may ask for without the large-LDS attribute
+    // beyond: 8 (36 J + 16) bytes at RT = 16 pass it from J = 227 on (real-term kernels up to J = 256 are within
+    // GF_MAX_WIDTH), so those take RT = 8 (8 (20 J + 8) bytes: 41 KB at J = 256)
     const int J = Jr + Jc;
-    const int RT = (J <= 44) ? 64 : (J <= 92) ? 32 : 16;
+    const int RT = (J <= 44) ? 64 : (J <= 92) ? 32 : (J <= 226) ? 16 : 8;
     const size_t lds = sizeof(double) * ((size_t)4 * J + (size_t)2 * RT * J + RT);
     const int64_t blocks = (N + 255) / 256;
     if (blocks > 0x7fffffffLL) return set_err("gf_cross_covariance: problem too large%s", "");
     const dim3 grid((unsigned)blocks, B);
     hipStream_t st = (hipStream_t)stream;
 #define GF_CX(RTv) hipLaunchKernelGGL((k_cross<RTv>), grid, dim3(256), lds, st, N, R, Jr, Jc, ar, cr, ac, bc, cc, dc, t, t_bs, ts, ts_bs, out)
-    if (RT == 64) GF_CX(64); else if (RT == 32) GF_CX(32); else GF_CX(16);
+    if (RT == 64) GF_CX(64); else if (RT == 32) GF_CX(32); else if (RT == 16) GF_CX(16); else GF_CX(8);
 #undef GF_CX
     return check_launch("gf_cross_covariance");
 }

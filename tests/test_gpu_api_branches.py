@@ -224,6 +224,75 @@ def test_cross_covariance_blocks_against_the_kernel_function(hip, case):
     assert np.max(np.abs(out.cpu().numpy() - want)) <= 1e-12 * scale
 
 
+def _cross_queries(t, R, rng):
+    """R unsorted query times: before the data, inside, after, and exactly on a stamp, in random proportion."""
+    lo, hi = t.min(), t.max()
+    span = max(hi - lo, 60e-6)
+    kind = rng.integers(0, 4, R)
+    u = rng.uniform(0.01, 0.5, R)
+    return np.where(kind == 0, lo - span * u, np.where(kind == 1, lo + (hi - lo) * u, np.where(
+        kind == 2, hi + span * u, t[rng.integers(0, len(t), R)])))
+
+
+def _cross_case(hip, Jr, Jc, N, R, shared):
+    """gf_cross_covariance for the B = 2 problems of tests.grad_cases.edge_problem(Jr, Jc, N) -- on per-problem axes
+    t, ts (strides N and R) or shared ones (stride 0) -- against ``Term.get_value`` of the coefficient form; the output
+    is one problem too long and must keep its sentinel there.  Returns the worst error in units of k(0)."""
+    import torch
+    from gadfly_amd.terms import Term
+    from tests import grad_cases as gc
+    lib, p = hip.load(), hip.ptr
+    B = 2
+    prob = gc.edge_problem(Jr, Jc, N, B)
+    rng = np.random.default_rng([17, Jr, Jc, N, R])
+    t = prob["t"] if shared else np.stack([prob["t"] * (1.0 + b / 64.0) for b in range(B)])
+    ts = _cross_queries(prob["t"], R, rng) if shared else np.stack([_cross_queries(t[b], R, rng) for b in range(B)])
+    cd = [torch.as_tensor(np.ascontiguousarray(prob["real"][i][:, :Jr])).cuda() for i in range(2)]
+    cd += [torch.as_tensor(np.ascontiguousarray(prob["comp"][i][:, :Jc])).cuda() for i in range(4)]
+    td, tsd = torch.as_tensor(np.ascontiguousarray(t)).cuda(), torch.as_tensor(np.ascontiguousarray(ts)).cuda()
+    out = torch.full(((B + 1) * N * R,), -7.25e77, dtype=torch.float64, device="cuda")
+    rc = lib.gf_cross_covariance(B, N, R, Jr, Jc, *[p(v) if v.numel() else None for v in cd], p(td),
+                                 0 if shared else N, p(tsd), 0 if shared else R, p(out), None)
+    hip.check(rc, "gf_cross_covariance")
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert np.all(got[B * N * R:] == -7.25e77)
+    got = got[:B * N * R].reshape(B, N, R)
+    worst = 0.0
+    for b in range(B):
+        co = _Coefficients(gc.coefficients(prob, b))
+        tb, tsb = (t, ts) if shared else (t[b], ts[b])
+        scale = Term.get_value(co, np.zeros(1))[0]
+        worst = max(worst, float(np.max(np.abs(got[b] - Term.get_value(co, tb[:, None] - tsb[None, :]))) / scale))
+    return worst
+
+
+@pytest.mark.parametrize("N", [1, 255, 256, 257])
+def test_cross_covariance_row_and_query_tiles(hip, N):
+    """B = 2 on per-problem and on shared axes; N on both sides of the 256-row workgroup (one row; a last lane idle,
+    none, a second workgroup of one row); R on both sides of the query tiles of RT = 64 (1, 16, 17, 33, 64, 65), and
+    R = 4096, the most a call takes, at N = 257.  1e-12 of k(0)."""
+    worst = 0.0
+    for R in (1, 16, 17, 33, 64, 65) + ((4096,) if N == 257 else ()):
+        for shared in (False, True):
+            err = _cross_case(hip, 1, 8, N, R, shared)
+            worst = max(worst, err)
+            assert err <= 1e-12, (R, shared, err)
+    print(f"gf_cross_covariance N = {N}: worst {worst:.1e} k(0)")
+
+
+@pytest.mark.parametrize("Jr,Jc", [(0, 44), (0, 45), (0, 92), (0, 93), (226, 0), (227, 0), (256, 0)])
+def test_cross_covariance_term_count_tiers(hip, Jr, Jc):
+    """Both sides of every change of the queries per pass: J = 44 | 45 (RT = 64 | 32), 92 | 93 (32 | 16) complex terms,
+    226 | 227 (16 | 8) real terms -- the last tier keeps the table of (term, query) factors within the 64 KB of LDS a
+    launch may ask for: 8 (36 J + 16) + 88 bytes at RT = 16 is 65 304 at J = 226 and 65 592 at J = 227 -- and the widest
+    kernel the header declares, 256 real terms.  N = 257, R = 70 (tiles of every RT, the last one short), B = 2."""
+    for shared in (False, True):
+        err = _cross_case(hip, Jr, Jc, 257, 70, shared)
+        print(f"gf_cross_covariance J = {Jr + Jc} ({Jr}, {Jc}), shared = {shared}: {err:.1e} k(0)")
+        assert err <= 1e-12, (shared, err)
+
+
 class _Coefficients:
     """A term given by its coefficient arrays (the celerite form ``gf_cross_covariance`` evaluates)."""
 
