@@ -61,6 +61,9 @@ SIGNATURES = {
     "gf_fused_state_size": (_i64, [_int, _int]),
     "gf_loglike_fused": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int] + [_vp] * 8
                          + [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_vp]),
+    "gf_steady_size": (_i64, []),
+    "gf_loglike_steady": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int] + [_vp] * 8
+                          + [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_vp, _i64] + [_vp]),
     "gf_sample_fused": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int] + [_vp] * 8
                         + [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_vp]),
     "gf_chunk_sweep": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int] + [_vp] * 8

@@ -226,6 +226,7 @@ class BatchedLogLikelihood:
             self._dt_min, self._t_abs_max = dt_min, tabs
             self._mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), (len(kernels),)).copy()
             self._finish_init(kernels)
+            eng.steady_state = False        # ragged batches: the pad rows' diagonal breaks the steady mode's premise
             return
         t = np.ascontiguousarray(t, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
@@ -272,6 +273,9 @@ class BatchedLogLikelihood:
         self._pack0 = None if eng._complexified else tuple(eng._struct0) + tuple(eng._coeff_host[:3])
         #: evaluations repeated with exact generator rows by the guard so far
         self.guard_reruns = 0
+        #: ... of which: evaluations whose steady-mode tail met a row it cannot take (engine.steady_violations)
+        self.steady_reruns = 0
+        self._viol_flags = {}               # id(out) -> violation flags of the evaluations not yet resolved
         self._last_cond = None
 
     @property
@@ -468,6 +472,10 @@ class BatchedLogLikelihood:
                 # non-finite value (det(I - X G) <= 0) -- repeated with the final pass by resolve()
                 bad = ~torch.isfinite(out)
                 flag = bad if flag is None else (flag | bad)
+            viol = eng.steady_violations() if getattr(eng, "steady_used", False) else None
+            if viol is not None:            # (a new tensor: the engine's buffer belongs to the next evaluation)
+                flag = viol if flag is None else (flag | viol)
+                self._viol_flags[id(out)] = viol
             if flag is not None:
                 self._unresolved.append((out, flag, eng._pack, period))
                 if len(self._unresolved) > 64:      # bound the backlog of a caller that never resolves
@@ -486,9 +494,13 @@ class BatchedLogLikelihood:
         flags = torch.stack([f for _, f, _, _ in pending]).cpu().numpy()      # the sync
         redone = 0
         keep_pack, keep_period, keep_two = eng._pack, eng.generator_period, eng.two_sweep
+        keep_steady, viols, self._viol_flags = eng.steady_state, self._viol_flags, {}
+        eng.steady_state = False            # every repeat is the reference formulation: full rows to the end
         for (out, flag, pack, _), hit in zip(pending, flags):
             if not hit.any():
                 continue
+            if id(out) in viols:
+                self.steady_reruns += int(viols[id(out)].sum().item())
             # (the pack is switched directly: use_coefficients() would also drop the engine's
             # construction-time coefficient list, which the stored-factor classes still need)
             eng._pack = pack
@@ -500,6 +512,7 @@ class BatchedLogLikelihood:
             out.copy_(torch.where(flag, exact, out))
             redone += int(hit.sum())
         eng._pack, eng.generator_period, eng.two_sweep = keep_pack, keep_period, keep_two
+        eng.steady_state = keep_steady
         self.guard_reruns += redone
         return redone
 
@@ -517,7 +530,7 @@ class BatchedLogLikelihood:
             host = torch.cat(parts).cpu().numpy()
             B = out.shape[0]
             if not self._unresolved or not host[B + 2:].any():
-                self._unresolved = []
+                self._unresolved, self._viol_flags = [], {}
                 eng = self.engine
                 cond = host[B + 1] / host[B] if host[B] > 0.0 else float("inf")
                 eng.generator_period = eng.period_for_condition(float(cond), self.generator_target)

@@ -1243,7 +1243,33 @@ __device__ __forceinline__ void sweep7_run(double (&T)[ROWS / 2][2], double2 (&u
 // ROWSTORE = false: no row is stored (r_out, Ut_out, Wt_out, de_out all null: the streamed log-likelihood
 // and the plain final pass) -- their tests, pointer arithmetic and exec-mask switches leave the row loop
 // SAMPLE = true: the sampling sweep, column 63 carries the draw (see k_factor3)
-template <int ROWS, bool ROWSTORE, bool SAMPLE = false>
+//
+// STEADY = true (gf_loglike_steady; ROWSTORE = SAMPLE = false): on a regular cadence with a constant diagonal the
+// recurrence is a time-invariant Riccati iteration, which converges geometrically to a fixed point in the frame
+// that rotates with the terms' phasors: the pivot d and the derotated gains G_k = (w_2k + i w_2k+1) e^{-i d_k t}
+// (w = r / d) become constants, and the W x W state carries nothing new.  At the rows = 0 mod ST_GRID = 64 (block
+// resets whatever the scaling block, a power of two <= 64: rho = 1, exact phasor) from global row arm_from on, the
+// wave compares d and its lanes' gain components with the values of ST_LAG such anchors before -- 1024 ROWS, so
+// that the rule means the same at every block -- (a ring in the per-problem steady buffer); once both have moved
+// by less than ST_THR -- the gains relative to the largest gain -- at ST_COUNT consecutive anchors it freezes them, moves
+// the forward-solve column to one entry per lane and continues in the tail loop: generator step,
+// F~ += w~_{n-1} z_{n-1}, z_n = y_n - u~_n . F~, block decays, d_n = d_inf.  Later tiles enter the tail directly
+// (no state load).  A row the tail cannot take -- a gap reset, a spacing off the frozen cadence -- raises the
+// buffer's violation flag: the caller repeats the evaluation without the mode.
+constexpr int ST_SW = 0;            // first tail row (global) ; 0 = full mode
+constexpr int ST_D = 1;             // frozen pivot
+constexpr int ST_VIOL = 2;          // != 0: the tail met a row it cannot take
+constexpr int ST_CNT = 3;           // consecutive converged anchors so far
+constexpr int ST_FILL = 4;          // anchors in the ring
+constexpr int ST_DT = 6;            // frozen cadence
+constexpr int ST_M1 = 8, ST_M2 = 72;        // [64] gain constants by column: w~ = (m1 cu + m2 su) / rho^2
+constexpr int ST_RING = 136;        // [ST_LAG][64] gain component per lane (lane 63: the pivot)
+constexpr int ST_GRID = 64;         // rows between the anchors the rule looks at
+constexpr int ST_LAG = 16, ST_COUNT = 4;
+constexpr double ST_THR = 1e-10;
+constexpr int ST_SIZE = ST_RING + ST_LAG * 64;
+
+template <int ROWS, bool ROWSTORE, bool SAMPLE = false, bool STEADY = false>
 __global__ void __launch_bounds__(64, 2)
 k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const int nch,
           const int ch0, const int nsel, const int Jr, const int Jc, const int block_sub, const double gap,
@@ -1257,7 +1283,8 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
           double *__restrict__ d_, double *__restrict__ z_, double *__restrict__ r_out,
           double *__restrict__ Ut_out, double *__restrict__ Wt_out, double *__restrict__ de_out,
           double *__restrict__ S_state, double *__restrict__ F_state,
-          int32_t *__restrict__ info) {
+          int32_t *__restrict__ info, double *__restrict__ steady_, const int64_t arm_from) {
+    static_assert(!STEADY || (!ROWSTORE && !SAMPLE), "steady mode: the streamed log-likelihood only");
     const int lane = threadIdx.x;
     const int g = lane >> 5, c = lane & 31;         // row group, column block (columns 2c, 2c + 1)
     const int sel = blockIdx.x;                     // chunks ch0 .. ch0 + nsel - 1 of every problem
@@ -1306,10 +1333,26 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     double *__restrict__ col1 = (f31 ? Fg : Sg + (size_t)(2 * c + 1) * 64) + 2 * g;
     double T[ROWS / 2][2];
     const bool zero_start = (block_sub >> 30) & 1;  // nominal pass: the state slots are outputs only
+    // steady mode: this problem's buffer; the tail's per-lane state (gain constants, F~ of the own column)
+    double *__restrict__ hdr = STEADY ? steady_ + (size_t)pr * ST_SIZE : nullptr;
+    bool tail = false;
+    double m1 = 0.0, m2 = 0.0, Ft = 0.0, dinf = 0.0, dtinf = 0.0;
+    constexpr double thr = ST_THR;
+    int cnt = 0, fill = 0;
+    if constexpr (STEADY) {
+        tail = __builtin_amdgcn_readfirstlane((int)(hdr[ST_SW] > 0.0)) != 0;
+        if (!tail) {
+            cnt = __builtin_amdgcn_readfirstlane((int)hdr[ST_CNT]);
+            fill = __builtin_amdgcn_readfirstlane((int)hdr[ST_FILL]);
+        }
+    }
+    const bool tail0 = tail;                        // a tile that starts in the tail: no state load
+    if (!tail) {
 #pragma unroll
-    for (int m = 0; m < ROWS / 2; ++m) {
-        T[m][0] = zero_start ? 0.0 : col0[4 * (m >> 1) + (m & 1)];
-        T[m][1] = zero_start ? 0.0 : col1[4 * (m >> 1) + (m & 1)];
+        for (int m = 0; m < ROWS / 2; ++m) {
+            T[m][0] = zero_start ? 0.0 : col0[4 * (m >> 1) + (m & 1)];
+            T[m][1] = zero_start ? 0.0 : col1[4 * (m >> 1) + (m & 1)];
+        }
     }
     double q0 = 0.0, q1 = 0.0;
     int32_t fail = 0;
@@ -1327,9 +1370,11 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     wave_lds_fence();
     sweep7_preload<ROWS>(ub, wb, pu, pw);
 
-    for (int64_t n = 0; n < rows; ++n) {
+    int64_t n = 0;
+    for (; n < rows && !tail; ++n) {
         const double a_n = (has_g ? g_n : 0.0) + diag_add, yy = y_n;
         const double ut_c = ut, vt_c = vt;
+        const bool rst_c = rst;
         if constexpr (ROWSTORE) { if (eg && lane == 0) eg[n] = rst ? de : -1.0; }
         if (rst) {                          // wave-uniform: fold the pending update, then decay
             const double el = fm_exp(-cj * de);     // pad columns: cj = 0 -> 1
@@ -1382,6 +1427,100 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
             }
         }
         if (lane == 0) { dg[n] = dn; zg[n] = SAMPLE ? zn + s2 : zn; }
+        if constexpr (STEADY) {
+            // anchor of the 64-row grid (a block reset at every block: rho = 1, exact phasor): the rotated-frame
+            // invariants of this row against those of ST_LAG such anchors (1024 rows) before
+            const int64_t gn = g0 + n;
+            if (rst_c && gn >= arm_from && (gn & (ST_GRID - 1)) == 0) {
+                double cs, sn;
+                both_halves(vt_c, cs, sn);          // v~ at an anchor: (cos, sin) of this lane's term
+                const double Gr = fma(r0, cs, r1 * sn) * inv, Gi = fma(r1, cs, -r0 * sn) * inv;
+                const double x = fl ? dn : (g ? Gi : Gr);       // (lane 63's own gain component is a pad: zero)
+                double *__restrict__ slot = hdr + ST_RING + (size_t)((gn / ST_GRID) & (ST_LAG - 1)) * 64 + lane;
+                const double xo = *slot;
+                *slot = x;
+                const double dx = fl ? 0.0 : fabs(x - xo);
+                const double mdx = wave_max(dx), mx = wave_max(fl ? 0.0 : fabs(x));
+                const double dold = read_lane(xo, 63);
+                const bool ok = fill >= ST_LAG && mdx <= thr * mx && fabs(dn - dold) <= thr * dn && !G.qmode;
+                cnt = ok ? cnt + 1 : 0;
+                fill = fill < ST_LAG ? fill + 1 : fill;
+                if (lane == 0) { hdr[ST_CNT] = (double)cnt; hdr[ST_FILL] = (double)fill; }
+                if (cnt >= ST_COUNT && G.dt_ref > 0.0) {       // (a cached cadence: not on a tile's first row)
+                    // the switch: freeze pivot and gains; the forward-solve column (this row's update folded)
+                    // goes from the tiled layout (block 31, rows split over the half-waves) to one entry per lane
+                    dinf = dn;
+                    dtinf = G.dt_ref;
+                    m1 = g ? Gi : Gr;
+                    m2 = g ? Gr : -Gi;
+                    wave_lds_fence();
+                    if (f31) {
+#pragma unroll
+                        for (int m = 0; m < ROWS / 2; ++m) {
+                            const int i = 2 * g + 4 * (m >> 1) + (m & 1);
+                            s_e[i] = fma(s_w[i], q1, T[m][1]);
+                        }
+                    }
+                    wave_lds_fence();
+                    Ft = (own < ROWS) ? s_e[own] : 0.0;
+                    hdr[ST_M1 + own] = m1;
+                    hdr[ST_M2 + own] = m2;
+                    if (lane == 0) { hdr[ST_SW] = (double)(gn + 1); hdr[ST_D] = dinf; hdr[ST_DT] = dtinf; }
+                    tail = true;                    // (the loop ends here; row n + 1 is the tail's first)
+                }
+            }
+        }
+    }
+    if constexpr (STEADY) {
+        if (tail && !fail) {
+            // the tail: ut / rst / de and the generator stand at row n, as at the top of the full loop
+            if (tail0) {
+                m1 = hdr[ST_M1 + own];
+                m2 = hdr[ST_M2 + own];
+                Ft = Fg[own];
+                dinf = hdr[ST_D];
+                dtinf = hdr[ST_DT];
+            }
+            double wt_p = 0.0, z_p = 0.0;           // pending update w~_{n-1} z_{n-1} (folded at the switch / tile end)
+            // (the tail's first row, then each next row: only the plain step, the sub-anchor and the block reset
+            // keep the frozen gains valid)
+            bool viol = false;
+            if (g0 + n > 0 && n < rows) {
+                const double dt0 = tg[n] - tg[n - 1];
+                viol = (dt0 > G.gthr) || !(fabs(dt0 - dtinf) < G.jthr);
+            }
+            // Rows in chunks of 64: t and y arrive by one coalesced load per chunk, issued a chunk ahead, and are
+            // handed out by readlane; d and z leave by one coalesced store per chunk.  (A scalar load per row, as
+            // in the full loop, is waited for within the row after the one that issued it, and a store per row
+            // holds every later vector-memory wait up: a tail row is too short to hide either.)  The indices are
+            // clamped to what the full loop's own prefetch reads at most.
+            const int64_t t_last = rows + 2, y_last = rows - 1;
+            auto chunk_t = [&](const int64_t cb) { const int64_t i = cb + 1 + lane; return tg[i < t_last ? i : t_last]; };
+            auto chunk_y = [&](const int64_t cb) { const int64_t i = cb + lane; return yg[i < y_last ? i : y_last]; };
+            double tv_n = chunk_t(n), yv_n = chunk_y(n);
+            for (int64_t cb = n; cb < rows; cb += 64) {
+                const double tv = tv_n, yv = yv_n;  // t of rows cb + 1 + lane, y of rows cb + lane
+                tv_n = chunk_t(cb + 64);
+                yv_n = chunk_y(cb + 64);
+                const int lim = (int)(rows - cb < 64 ? rows - cb : 64);
+                double zv = 0.0;
+                for (int k = 0; k < lim; ++k) {
+                    const double yy = read_lane(yv, k), t_nx = read_lane(tv, k);
+                    Ft = fma(wt_p, z_p, Ft);
+                    if (rst) Ft *= fm_exp(-cj * de);        // block reset: decay of the own column (pads: 1)
+                    wt_p = fma(m1, G.cu, m2 * G.su) * G.irho2;
+                    z_p = yy - wave_sum(ut * Ft);
+                    const double dtn = t_nx - G.t_m1;
+                    if (cb + k + 1 < rows) viol |= (dtn > G.gthr) || !(fabs(dtn - dtinf) < G.jthr);
+                    G.next(t_nx, g0 + cb + k + 1, ut, vt, rst, de);
+                    zv = (lane == k) ? z_p : zv;
+                }
+                if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
+            }
+            Fg[own] = fma(wt_p, z_p, Ft);
+            if (viol && lane == 0) hdr[ST_VIOL] = 1.0;
+            return;
+        }
     }
     if (fail) {
         if (lane == 0) info[b] = fail;
@@ -5399,8 +5538,9 @@ static bool sweep_tiled(int variant, int Jr, int Jc) {
 }
 
 #define GF_F3_ARGS dim3(B * chunk_count), dim3(64), 0, st, N, n_first, chunk_len, nch, chunk_first, chunk_count, Jr, Jc, (block | (gen_period << 8) | zero_start), gap, ar, cr, ac, bc, cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, r_out, Ut_out, Wt_out, de_out, S_state, F_state, info
-#define GF_S3_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_factor7<R, false, true>), GF_F3_ARGS); else hipLaunchKernelGGL((k_factor3<R, true>), GF_F3_ARGS); break;
-#define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
+#define GF_F7_NOSTEADY (double *)nullptr, (int64_t)0
+#define GF_S3_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_factor7<R, false, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R, true>), GF_F3_ARGS); break;
+#define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else if (steady) hipLaunchKernelGGL((k_factor7<R, false, false, true>), GF_F3_ARGS, steady, arm_from); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
 
 static int check_sweep_options(const char *who, int gen_period, int variant, int Jr, int Jc) {
     if (gen_period < 1 || gen_period > 64 || (gen_period & (gen_period - 1)))
@@ -5422,7 +5562,8 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
                         const double *y, int64_t y_bs,
                         double *d, double *z, double *r_out, double *Ut_out, double *Wt_out,
                         double *de_out, double *S_state, double *F_state,
-                        int32_t *info, void *stream, bool sample = false) {
+                        int32_t *info, void *stream, bool sample = false,
+                        double *steady = nullptr, int64_t arm_from = 0) {
     const int W = Jr + 2 * Jc;
     if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
     // the sampling sweeps (y = eps, z = the draw by global row with y's batch stride): streamed tiles only
@@ -5452,6 +5593,8 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
     const bool tiled = sweep_tiled(variant, Jr, Jc);
     const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;
     hipStream_t st = (hipStream_t)stream;
+    if (steady && (W > 63 || !tiled || r_out || Ut_out || Wt_out || de_out || sample || zero_start || nch > 1 || arm_from < 0))
+        return set_err("%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%lld)", who, Jc);
     if (W > 63) {                       // wide kernels: one workgroup per (problem, chunk), k_factorw
         FactorWArgs A;
         A.N = N; A.n_first = n_first; A.chunk_len = chunk_len; A.nch = nch; A.ch0 = chunk_first; A.nsel = chunk_count; A.Jc = Jc;
@@ -5497,6 +5640,23 @@ int gf_loglike_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int bloc
     return fused_launch("gf_loglike_fused", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
                         diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
                         nullptr, nullptr, nullptr, S_state, F_state, info, stream);
+}
+
+int64_t gf_steady_size(void) { return ST_SIZE; }
+
+int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                      int gen_period, int variant,
+                      const double *ar, const double *cr, const double *ac,
+                      const double *bc, const double *cc, const double *dc,
+                      const double *diag_add, const double *cmax,
+                      const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                      const double *y, int64_t y_bs,
+                      double *d, double *z, double *S_state, double *F_state,
+                      int32_t *info, double *steady, int64_t arm_from, void *stream) {
+    if (!steady) return set_err("gf_loglike_steady: null pointer%s", "");
+    return fused_launch("gf_loglike_steady", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
+                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from);
 }
 
 int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,

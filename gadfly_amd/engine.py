@@ -867,6 +867,18 @@ class StreamingBatch:
         # the NOMINAL values and a non-positive pivot shows up as NaN, which the caller must resolve with a
         # final pass (BatchedLogLikelihood does, for kernels that are positive semi-definite by construction)
         self.two_sweep = False
+        # steady mode of the streamed lane-tiled sweep: on a regular cadence with a constant diagonal
+        # each problem's pivot and rotated-frame gains converge; the sweep detects it per evaluation and runs only
+        # the forward solve on the rows after (gf_loglike_steady).  Taken only where _steady_arm_from() allows it.
+        self.steady_state = True
+        self.steady_used = False            # the last streamed evaluation went through gf_loglike_steady
+        self._steady = None                 # [B][gf_steady_size()] per-problem buffer of that entry point
+        self._steady_axis = None            # (arm_from, largest spacing deviation behind it): once per evaluator
+        # where the steady instance starts (its full rows cost ~6 % more than the plain instance's, so tiles that end
+        # before any problem can switch run the plain one): learnt from the switch rows of earlier evaluations
+        self._steady_from = 0               # first row whose tile runs the steady instance
+        self._steady_skip = 0               # evaluations left on the plain sweep after one in which nothing armed
+        self._steady_feedback = None        # (pinned host scalar, event): earliest switch row of the last steady one
         T = int(min(max(int(tile_rows), 1), self.N))
         if T < self.N:
             T = max(64, T // 64 * 64)         # tiles start on a reset row (any block <= 64)
@@ -1035,6 +1047,7 @@ class StreamingBatch:
         dev = self._dev
         cmax = np.max(c, axis=1)
         dmax = float(np.max(np.abs(comp[3]))) if comp.size else 0.0
+        wmax = max(float(np.max(cmax)), dmax)          # what the row generator's cadence test divides by
         # rows between forced resets of the scaled coordinates (the spans come from the library: one place)
         x = 1.5 * float(np.max(cmax)) * max(getattr(self, "_dt_med", 0.0), 0.0)
         block = self._scaling_block(x, _scaled_span(False))
@@ -1053,7 +1066,7 @@ class StreamingBatch:
             host[o:o + a.size] = a.reshape(-1)
         buf = dev(host)
         real, comp, diag_add, c, cmax = (buf[o:o + a.size].view(a.shape) for a, o in zip(arrs, offs))
-        return real, comp, diag_add, c, cmax, block, dmax, stream_block
+        return real, comp, diag_add, c, cmax, block, dmax, stream_block, wmax
 
     def pack_coefficients(self, coeffs_list):
         if len(coeffs_list) != self.B:
@@ -1109,6 +1122,7 @@ class StreamingBatch:
         self.info.zero_()
         self._tp_used, self._last_wide_tp = False, False     # (whose `acc` the last evaluation filled)
         self._two_sweep_used = False
+        self.steady_used = False
         if self._fused_ok() or self._wide_ok():
             return self._log_likelihood_fused(main)
         if self.bufs is None:
@@ -1168,11 +1182,18 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         T, N, B = self.tile_rows, self.N, self.B
-        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack
+        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack[:8]
         period, variant = int(self.generator_period), int(self.sweep_variant)
         if stream_block:                    # the long scaling span (one-wave sweeps, amplitudes in range)
             block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
         self.kernel_used = "fused-wide" if self.W > 63 else "fused"
+        arm_from = self._steady_arm_from()
+        start = None if arm_from is None else self._steady_plan(arm_from)
+        self.steady_used = start is not None
+        if self.steady_used:
+            if self._steady is None:
+                self._steady = torch.empty((B, int(lib.gf_steady_size())), dtype=torch.float64, device=self.device)
+            self._steady.zero_()
         for k in range((N + T - 1) // T):
             n0 = k * T
             rows = min(T, N - n0)
@@ -1180,25 +1201,137 @@ class StreamingBatch:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e1 = torch.cuda.Event(enable_timing=True)
                 e0.record(main)
-            st = lib.gf_loglike_fused(
-                B, rows, n0, self.Jr, self.Jc, block, period, variant,
-                p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-                p(diag_add), p(cmax), p(self.t), self._bs(self.t),
-                p(self.diag), 0 if self.diag is None else self._bs(self.diag),
-                p(self.y), self._bs(self.y), p(self.d), p(self.z),
-                p(self.S_state), p(self.F_state), p(self.info), main.cuda_stream)
-            _lib.check(st, "gf_loglike_fused")
+            args = (B, rows, n0, self.Jr, self.Jc, block, period, variant,
+                    p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
+                    p(diag_add), p(cmax), p(self.t), self._bs(self.t),
+                    p(self.diag), 0 if self.diag is None else self._bs(self.diag),
+                    p(self.y), self._bs(self.y), p(self.d), p(self.z),
+                    p(self.S_state), p(self.F_state), p(self.info))
+            if self.steady_used and n0 + rows > start:      # (both instances hand over the same state)
+                st = lib.gf_loglike_steady(*args, p(self._steady), arm_from, main.cuda_stream)
+                _lib.check(st, "gf_loglike_steady")
+            else:
+                st = lib.gf_loglike_fused(*args, main.cuda_stream)
+                _lib.check(st, "gf_loglike_fused")
             if self.time_factor:
                 e1.record(main)
                 self.factor_events.append((e0, e1, rows))
             st = lib.gf_reduce_tile(B, rows, p(self.d), p(self.z), p(self.work), p(self.acc),
                                     1 if k == 0 else 0, main.cuda_stream)
             _lib.check(st, "gf_reduce_tile")
+        if self.steady_used:                # earliest switch row (0: nothing armed) for the next plan: no sync here
+            sw = self._steady[:, 0]
+            first = torch.where(sw > 0.0, sw, torch.full_like(sw, float("inf"))).min()
+            host = torch.zeros((1,), dtype=torch.float64, pin_memory=True)
+            host.copy_(torch.where(torch.isfinite(first), first, torch.zeros_like(first)).reshape(1), non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(main)
+            self._steady_feedback = (host, done)
         out = torch.empty((B,), dtype=torch.float64, device=self.device)
         st = lib.gf_loglike_finish(B, N, p(self.acc), p(self.info), p(out), None,
                                    main.cuda_stream)
         _lib.check(st, "gf_loglike_finish")
         return out
+
+    #: evaluations between two tries of the steady instance while nothing arms (a series too short, a kernel too slow)
+    STEADY_PROBE = 16
+
+    def _steady_plan(self, arm_from):
+        """Row from whose tile on this evaluation runs the steady instance, None for the plain sweep throughout.
+        The steady instance's full rows are ~6 % slower than the plain instance's (its anchors' work and its
+        register budget), so it is started only where a switch can be near: one tile and the rule's look-back before
+        the earliest switch row of the last steady evaluation whose result has arrived (read without waiting; a
+        sampler's proposals move slowly).  A problem that would have switched earlier switches a little later: speed,
+        never values.  After an evaluation in which nothing armed, the next STEADY_PROBE - 1 run the plain sweep."""
+        fb = self._steady_feedback
+        if fb is not None and fb[1].query():
+            first, self._steady_feedback = int(fb[0][0]), None
+            if first > 0:
+                self._steady_from = max(0, first - self.STEADY_MIN_ROWS - self.tile_rows)
+                self._steady_skip = 0
+            else:
+                self._steady_from, self._steady_skip = 0, self.STEADY_PROBE - 1
+        if self._steady_skip > 0:
+            self._steady_skip -= 1
+            return None
+        return max(arm_from, self._steady_from)
+
+    #: rows the steady mode needs behind arm_from to be worth arming: its rule looks back over 16 + 4 anchors
+    STEADY_MIN_ROWS = 20 * 64
+
+    def _steady_axis_scan(self):
+        """(arm_from, jitter), once per evaluator, on the device: the row after the last spacing that deviates
+        from the FINAL cadence by more than the rounding of the time stamps (8 ulp of the largest |t|) -- and, with
+        a per-row diagonal, after the last row whose diagonal differs from the final one -- and the largest
+        deviation of the spacings behind it.  arm_from = N: the axis (or the diagonal) is irregular to its end.
+        (t and diag are fixed at construction -- only y can be replaced, set_y -- so the scan holds for the evaluator's
+        lifetime.  With arm_from from this scan no frozen row can meet a gap: the violation flag guards callers of
+        the C entry point that promise more than their axis keeps, and BatchedLogLikelihood.resolve() reads it.)"""
+        if self._steady_axis is None:
+            torch = self.torch
+            N, arm, jit = self.N, self.N, 0.0
+            if N > self.STEADY_MIN_ROWS:
+                # in column slices of at most ~4M elements (no second copy of a (B, N) axis), three host syncs in all
+                t, Bt = self.t, self.t.shape[0]
+                step = max(1, (1 << 22) // Bt)
+                cad = t[:, -1:] - t[:, -2:-1]                       # final cadence per axis
+                cmax, cmin = (float(v) for v in torch.stack([cad.max(), cad.min()]).cpu())
+                tol = 8.0 * 2.0 ** -52 * max(self._tmax, cmax)
+
+                def spacing_dev(a, b):      # |spacing k - final cadence| for k = a .. b - 1 (spacing k joins rows k, k + 1)
+                    return (t[:, a + 1:b + 1] - t[:, a:b] - cad).abs()
+
+                def after_last(mask_of, n):  # index after the last column of 0 .. n - 1 with any True (device scalar)
+                    last = torch.zeros((), dtype=torch.int64, device=self.device)
+                    for a in range(0, n, step):
+                        b = min(a + step, n)
+                        bad = mask_of(a, b).any(dim=0)
+                        idx = torch.arange(a + 1, b + 1, device=self.device)
+                        last = torch.maximum(last, torch.where(bad, idx, torch.zeros_like(idx)).max())
+                    return last
+
+                arm_t = after_last(lambda a, b: spacing_dev(a, b) > tol, N - 1)
+                if self.diag is not None:
+                    dg = self.diag
+                    arm_t = torch.maximum(arm_t, after_last(lambda a, b: dg[:, a:b] != dg[:, -1:], N))
+                arm = int(arm_t)
+                if cmin <= 0.0 or N - arm < self.STEADY_MIN_ROWS:
+                    arm = N
+                elif arm < N - 1:
+                    jit = float(torch.stack([spacing_dev(a, min(a + step, N - 1)).max()
+                                             for a in range(arm, N - 1, step)]).max())
+            self._steady_axis = (arm, jit)
+        return self._steady_axis
+
+    def _steady_arm_from(self):
+        """First global row at which the streamed sweep may enter its steady mode with the current coefficients,
+        None where the plain sweep (gf_loglike_fused) runs: the lane-tiled one-wave route (Jr = 0, Jc <= 31), the
+        generator off its rounded-phase mode (RowGen::qmode: the oracle's own rows are time-varying at 1e-7 there),
+        an axis that is regular -- well inside the generator's own test |ddt| < 2e-6 / wmax -- and a diagonal that
+        is constant from that row on."""
+        if not (self.steady_state and self._fused_ok() and self.Jr == 0 and self.Jc <= 31
+                and (int(self.sweep_variant) & 0xff) != _lib.GF_SWEEP_COLUMN and len(self._pack) > 8):
+            return None
+        wmax = float(self._pack[8])
+        if not (wmax > 0.0) or wmax * self._tmax > self.QMODE_PHASE:
+            return None
+        arm, jit = self._steady_axis_scan()
+        if arm >= self.N or not (jit < 1e-6 / wmax):
+            return None
+        return arm
+
+    def steady_switch_rows(self):
+        """Per problem, the first row the LAST streamed evaluation ran in steady mode (-1: never); synchronises."""
+        if not self.steady_used:
+            return np.full(self.B, -1, dtype=np.int64)
+        sw = self._steady[:, 0].cpu().numpy()
+        return np.where(sw > 0.0, sw, -1.0).astype(np.int64)
+
+    def steady_violations(self):
+        """(B,) bool device tensor: problems whose frozen rows met a gap or an off-cadence spacing in the last
+        streamed evaluation (their values are invalid: BatchedLogLikelihood.resolve() repeats them); None when
+        the steady mode did not run."""
+        return (self._steady[:, 2] != 0.0) if self.steady_used else None
 
     def _fused_refusal(self):
         """Why neither fused sweep takes this batch (None when one does): what a caller that has no slower
@@ -1234,7 +1367,7 @@ class StreamingBatch:
         if B > 1 and (int(out.stride(0)) != bs or bs < N):
             raise ValueError("eps and out must share one batch stride")
         main = torch.cuda.current_stream(self.device)
-        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack
+        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack[:8]
         period, variant = int(self.generator_period), int(self.sweep_variant)
         if stream_block:                    # the long scaling span (one-wave sweeps, amplitudes in range)
             block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
@@ -1686,6 +1819,7 @@ class StreamingBatch:
         few long series (B * N large per problem, B small) unless told otherwise."""
         auto = time_parallel is None
         force = getattr(self, "force_streaming", False)
+        self.steady_used = False            # (only the streamed sweep sets it)
         if auto:
             # chunking costs ~3.5x the flops: it pays while the batch alone fills less than
             # ~1/8 of the 2048 wave slots (``force_streaming``: benchmarks of the streamed sweep)

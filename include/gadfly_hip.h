@@ -186,6 +186,33 @@ int gf_loglike_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int bloc
                      int32_t *info, void *stream);
 
 /*
+ * gf_loglike_fused with the STEADY MODE of the lane-tiled sweep (Jr = 0, Jc <= 31; an error otherwise).  On a
+ * regular cadence with a constant diagonal the pivot d and the gains w = r / d -- in the frame that rotates with
+ * the terms' phasors -- converge geometrically to constants.  From global row arm_from on (the caller's
+ * promise: regular cadence, constant diagonal, from there to the end of the series; arm_from >= N: never) the
+ * sweep compares both, at the rows = 0 mod 64 (block resets at every block), with their values 16 such rows --
+ * 1024 rows -- before; once they have moved by less than 1e-10 (gains: relative to the largest) at 4 consecutive
+ * ones it freezes them and runs only the
+ * forward solve on all later rows and tiles.  d, z, info, S_state, F_state as for gf_loglike_fused (S_state is
+ * no longer maintained after the switch).
+ *   steady [B][gf_steady_size()] doubles, zeroed by the caller before the FIRST tile of an evaluation and
+ *          handed unchanged to the following tiles.  Per problem: [0] first frozen row (global index; 0 = the
+ *          mode has not been entered), [1] the frozen pivot, [2] != 0: VIOLATION -- a frozen row met a gap or a
+ *          spacing off the frozen cadence, the result is invalid and the evaluation must be repeated with
+ *          gf_loglike_fused; the rest is the sweep's own.
+ */
+int64_t gf_steady_size(void);
+int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                      int gen_period, int variant,
+                      const double *ar, const double *cr, const double *ac,
+                      const double *bc, const double *cc, const double *dc,
+                      const double *diag_add, const double *cmax,
+                      const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                      const double *y, int64_t y_bs,
+                      double *d, double *z, double *S_state, double *F_state,
+                      int32_t *info, double *steady, int64_t arm_from, void *stream);
+
+/*
  * Fused sampling sweep: B draws y = L D^1/2 eps of B different kernels, K = L D L^T, in the sweep that factors
  * -- no factor is stored (24 B read, 16 B written per row: t, diag, eps; d, out).  Replaces celerite2's
  * driver.matmul_lower with V := W after driver.factor (the reference's GaussianProcess.sample, gp.py:391) for

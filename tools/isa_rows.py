@@ -4,6 +4,7 @@
     python tools/isa_rows.py --asm out.s           # count an existing `hipcc --cuda-device-only -S` listing
     python tools/isa_rows.py --kernel k_factor7 --rows 40 --rowstore
     python tools/isa_rows.py --kernel k_factorw --rows 44 --sample   # the sampling instance (gf_sample_fused)
+    python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: the full row loop AND the tail loop
 
 Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
 most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
@@ -28,16 +29,18 @@ def compile_asm(out):
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 
 
-def kernel_tag(kernel, rows, rowstore, sample):
-    # mangled: ..._19k_factor7ILi60ELb0ELb0EEEv...  (template <int ROWS, bool ROWSTORE, bool SAMPLE>); k_factorw has a
+def kernel_tag(kernel, rows, rowstore, sample, steady=False):
+    # mangled: ..._19k_factor7ILi60ELb0ELb0ELb0EEEv...  (template <int ROWS, bool ROWSTORE, bool SAMPLE, bool STEADY>); k_factorw has a
     # second integer (its sweep waves) and k_factor3 / k_factorw no ROWSTORE.  The whole argument list is matched.
     mid = r"Li\d+E" if kernel == "k_factorw" else (f"Lb{int(rowstore)}E" if rowstore is not None else "")
     smp = f"Lb{int(sample)}E" if kernel in ("k_factor3", "k_factor7", "k_factorw") else ""
+    if kernel == "k_factor7":
+        smp += f"Lb{int(steady)}E"
     return re.compile(f"{len(kernel)}{kernel}ILi{rows}E{mid}{smp}E")
 
 
-def kernel_body(lines, kernel, rows, rowstore, sample=False):
-    tag = kernel_tag(kernel, rows, rowstore, sample)
+def kernel_body(lines, kernel, rows, rowstore, sample=False, steady=False):
+    tag = kernel_tag(kernel, rows, rowstore, sample, steady)
     start = None
     for i, ln in enumerate(lines):
         if start is None and re.match(r"^_Z\S+:", ln) and tag.search(ln.split(":")[0]):
@@ -106,6 +109,7 @@ def main():
     ap.add_argument("--rows", type=int, default=60)
     ap.add_argument("--rowstore", action="store_true", help="the ROWSTORE = true instance (k_factor7 only)")
     ap.add_argument("--sample", action="store_true", help="the SAMPLE = true instance (the sampling sweeps)")
+    ap.add_argument("--steady", action="store_true", help="the STEADY = true instance (k_factor7 only): also its tail loop")
     ap.add_argument("--all", action="store_true", help="also print blocks outside loops")
     a = ap.parse_args()
     asm = a.asm
@@ -114,8 +118,8 @@ def main():
         compile_asm(asm)
     lines = open(asm).read().splitlines()
     rowstore = (a.rowstore if a.kernel == "k_factor7" else None)
-    body = kernel_body(lines, a.kernel, a.rows, rowstore, a.sample)
-    tag = kernel_tag(a.kernel, a.rows, rowstore, a.sample)
+    body = kernel_body(lines, a.kernel, a.rows, rowstore, a.sample, a.steady)
+    tag = kernel_tag(a.kernel, a.rows, rowstore, a.sample, a.steady)
     bl = blocks(body)
     vgpr = next((ln.split(",")[-1].strip() for ln in lines
                  if ".num_vgpr," in ln and tag.search(ln)), "?")
@@ -128,14 +132,25 @@ def main():
     print(f"row loop: blocks {bl[i0]['name']} .. {bl[i1]['name']}; `regular` = the block with the mat-vec's FMAs, "
           f"`exp` = a block holding fm_exp / fm_sincos (v_ldexp_f64)")
     print(f"{'block':>14} {'VALU':>5} {'fma':>4} {'LDS':>4} {'SALU':>5} {'br':>3} {'mov64':>5} {'movb32':>6} {'spill':>5}  role")
-    for k in range(i0, i1 + 1):
-        b = bl[k]
-        if not b["ins"]:
-            continue
-        c = counts(b["ins"])
-        role = "regular" if k == reg else ("exp" if c["ldexp"] else "")
-        print(f"{b['name']:>14} {c['valu']:5d} {c['fma']:4d} {c['lds']:4d} {c['salu']:5d} {c['branch']:3d} "
-              f"{c['mov64']:5d} {c['movb32']:6d} {c['scratch']:5d}  {role}")
+    def show(k0, k1, regular):
+        for k in range(k0, k1 + 1):
+            b = bl[k]
+            if not b["ins"]:
+                continue
+            c = counts(b["ins"])
+            role = "regular" if k == regular else ("exp" if c["ldexp"] else "")
+            print(f"{b['name']:>14} {c['valu']:5d} {c['fma']:4d} {c['lds']:4d} {c['salu']:5d} {c['branch']:3d} "
+                  f"{c['mov64']:5d} {c['movb32']:6d} {c['scratch']:5d}  {role}")
+
+    show(i0, i1, reg)
+    if a.steady and not a.all:
+        # the tail loop: the widest range closed by a backward branch behind the row loop
+        idx = {b["name"]: i for i, b in enumerate(bl)}
+        tails = [(idx[t], j) for j, b in enumerate(bl) if j > i1 for t in b["targets"] if i1 < idx.get(t, -1) <= j]
+        if tails:
+            t0, t1 = max(tails, key=lambda r: r[1] - r[0])
+            print(f"tail loop: blocks {bl[t0]['name']} .. {bl[t1]['name']}")
+            show(t0, t1, None)
     return 0
 
 
