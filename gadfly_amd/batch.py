@@ -367,7 +367,81 @@ class BatchedLogLikelihood:
     #: cap on the workspace of one :meth:`predict` call in bytes: larger batches run in groups
     predict_workspace_bytes = _lib.GF_SOLVE_WORKSPACE_BYTES
 
-    def predict_device(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False):
+    def _query_times(self, t):
+        """``t=`` of :meth:`predict_device` -> (stamps (1 or B, M) float64, queries per problem or None, whether the
+        result is a list): an array (M,) shared by all problems or (B, M), or a list / tuple of B 1-D arrays of any
+        lengths (padded at the end with each series' last stamp; the pad is never read)."""
+        B = self.B
+        if _is_ragged(t) or (isinstance(t, (list, tuple)) and len(t) and all(np.ndim(x) == 1 for x in t)):
+            qs = [np.ascontiguousarray(x, dtype=np.float64) for x in t]
+            if len(qs) != B:
+                raise ValueError(f"t= holds {len(qs)} series of query times for a batch of {B} problems")
+            if any(np.any(np.diff(x) < 0.0) for x in qs):
+                raise ValueError("The input coordinates must be sorted")
+            nq = np.array([len(x) for x in qs], dtype=np.int64)
+            T = np.zeros((B, int(nq.max())))
+            for b, x in enumerate(qs):
+                T[b, :len(x)] = x
+                T[b, len(x):] = x[-1] if len(x) else 0.0
+            return T, nq, True
+        T = np.asarray(t, dtype=np.float64)
+        if T.ndim == 1:
+            T = T[None, :]
+        if T.ndim != 2 or T.shape[0] not in (1, B):
+            raise ValueError(f"t= of shape {np.shape(t)} is neither (M,) nor ({B}, M) nor a list of {B} series")
+        if np.any(np.diff(T, axis=-1) < 0.0):
+            raise ValueError("The input coordinates must be sorted")
+        return np.ascontiguousarray(T), None, False
+
+    def _mean_per_problem(self):
+        """The mean of construction as a scalar or a (B, 1) column; ValueError if it varies along the rows (such a
+        mean is known at the observed stamps only)."""
+        m = self._mean
+        if self.rows is not None:           # ragged data: the constructor keeps one value per problem, (B,)
+            assert m.shape == (self.B,)
+            return m[:, None]
+        if m.size == 1:
+            return m.reshape(())
+        m = np.atleast_2d(m)
+        if np.any(m != m[:, :1]):
+            raise ValueError("a mean that varies along the rows cannot be evaluated at new times t; pass "
+                             "include_mean=False and add the mean at t yourself")
+        return m[:, :1]
+
+    def _predict_at(self, pack_or_kernels, kernel, include_mean, return_alpha, t):
+        """:meth:`predict_device` with ``t=``: alpha as without it, then the two sums between the sorted axes."""
+        from .predict import check_width, component_pack, predict_at, solve_batch
+        eng = self.engine
+        torch = eng.torch
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        ts, nq, as_list = self._query_times(t)
+        mean = self._mean_per_problem() if include_mean and np.any(self._mean != 0.0) else None
+        component = None if kernel is None else component_pack(kernel, self.B)
+        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
+        res = solve_batch(eng, Jr, Jc, real, comp, diag_add, None, self.predict_workspace_bytes,
+                          want_alpha=True, want_mu=False)
+        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self._predict_events, self._predict_at_events = res["events"], []
+        self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
+        self.last_predict_info = res["info"]
+        if ts.shape[1] == 0:
+            mu = torch.empty((self.B, 0), dtype=torch.float64, device=eng.device)
+        else:
+            cf = (Jr, Jc, real, comp) if component is None else component
+            at = predict_at(eng, *cf, res["alpha"], ts, nobs=self.rows, nq=nq)
+            self._predict_at_events = at["events"]
+            mu = at["mu"]
+            if mean is not None:
+                mu += torch.as_tensor(np.array(mean), dtype=torch.float64, device=eng.device)
+        if as_list:
+            mu = [mu[b, :int(n)] for b, n in enumerate(nq)]
+        alpha = res["alpha"]
+        if self.rows is not None:
+            alpha = [alpha[b, :int(n)] for b, n in enumerate(self.rows)]
+        return (mu, alpha) if return_alpha else mu
+
+    def predict_device(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None):
         """Conditional means of the B problems at their observed times in one device call: what
         ``GaussianProcess(kernel_b, t, yerr).predict(y)`` gives one kernel at a time -- mu = y - diag alpha with
         alpha = K^-1 (y - mean) -- as a float64 device tensor (B, N); a ragged batch returns a list of B tensors cut
@@ -381,7 +455,18 @@ class BatchedLogLikelihood:
         alpha, ``(mu, alpha)``.  A problem whose matrix is not positive definite gets NaN in all its rows (the
         others are unaffected); :attr:`last_predict_ll` holds the log-likelihoods (-inf there) and
         :attr:`last_predict_info` the failing rows, both on the device.  Kernels or components wider than W = 63
-        raise ``NotImplementedError``."""
+        raise ``NotImplementedError``.
+
+        ``t``: new times t* at which to predict instead (``GaussianProcess.predict(y, t=t*)``) --
+        an array (M,) shared by all problems or (B, M), or a list / tuple of B 1-D arrays of any lengths, ascending
+        per problem, whether the data are ragged or not; the result is (B, M) for an array and a list of B tensors
+        for a list.  It is
+        K(t*, t) alpha with the kernel's coefficients at every lag (no diagonal; an exposure-integrated kernel stays
+        in coefficient form), or K'(t*, t) alpha with ``kernel=component``.  The mean added is a scalar or one value
+        per problem: a mean that varies along the rows raises ``ValueError`` unless ``include_mean=False``.  An
+        empty ``t`` gives an empty result (alpha is still solved for; the second launch is left out)."""
+        if t is not None:
+            return self._predict_at(pack_or_kernels, kernel, include_mean, return_alpha, t)
         from .predict import check_width, component_pack, solve_batch
         eng = self.engine
         Jr0, Jc0 = eng._struct0
@@ -392,7 +477,7 @@ class BatchedLogLikelihood:
                           want_alpha=return_alpha, want_mu=component is None)
         #: (workspace bytes of a group, number of groups, problems per group) and the HIP events of the last call
         self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
-        self._predict_events = res["events"]
+        self._predict_events, self._predict_at_events = res["events"], []
         self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
         self.last_predict_info = res["info"]
         mu = res["mu"] if component is None else res["mu_comp"]
@@ -412,14 +497,24 @@ class BatchedLogLikelihood:
     @property
     def last_predict_device_ms(self):
         """Summed device time of the last :meth:`predict_device` call's launches (synchronises)."""
-        for _, e1 in self._predict_events:
-            e1.synchronize()
-        return sum(a.elapsed_time(b) for a, b in self._predict_events)
+        return self._events_ms(self._predict_events) + self.last_predict_at_ms
 
-    def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False):
-        """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch)."""
+    @property
+    def last_predict_at_ms(self):
+        """The share of :attr:`last_predict_device_ms` spent in the launch that carries alpha to new times ``t``
+        (0 for a call without ``t`` or with an empty one)."""
+        return self._events_ms(self._predict_at_events)
+
+    @staticmethod
+    def _events_ms(events):
+        for _, e1 in events:
+            e1.synchronize()
+        return sum(a.elapsed_time(b) for a, b in events)
+
+    def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None):
+        """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch or a list of query times)."""
         out = self.predict_device(pack_or_kernels, kernel=kernel, include_mean=include_mean,
-                                  return_alpha=return_alpha)
+                                  return_alpha=return_alpha, t=t)
 
         def host(x):
             return [v.cpu().numpy() for v in x] if isinstance(x, list) else x.cpu().numpy()
@@ -568,12 +663,13 @@ def log_likelihood_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, device=N
                                 device=device).evaluate()
 
 
-def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, device=None):
+def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, device=None, t_pred=None):
     """One-shot form of :meth:`BatchedLogLikelihood.predict`: the conditional means of B problems at their observed
     times as numpy, (B, N) or a list of B arrays for ragged ``t``; ``kernel=`` selects the share of one part of the
-    kernel (a list of B components, or one for all)."""
+    kernel (a list of B components, or one for all).  ``t_pred``: new times to predict at instead, what
+    :meth:`BatchedLogLikelihood.predict` takes as ``t=`` (here ``t`` names the observed stamps)."""
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
-                                device=device).predict(kernel=kernel)
+                                device=device).predict(kernel=kernel, t=t_pred)
 
 
 def _is_series_list(x):

@@ -5,6 +5,8 @@ The device computes alpha = K^-1 (y - mean), mu = y - diag alpha and, optionally
 the kernel explains for B problems at once (``gf_solve_batch``: a checkpointed forward sweep and the upper solve
 backwards, no stored factor); this module sizes its workspace, splits a batch into groups under a byte cap (a
 problem's result does not depend on the group it lands in) and stacks the component's coefficients.
+``gf_predict_batch_at`` then carries alpha to new times t* (DESIGN.md 3.11): the two sorted-axis sums of the full
+kernel or of a component, no workspace.
 """
 import numpy as np
 import torch
@@ -12,7 +14,7 @@ import torch
 from . import _lib
 from .grad import check_pack_batch
 
-__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "DEFAULT_WORKSPACE_BYTES"]
+__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "predict_at", "DEFAULT_WORKSPACE_BYTES"]
 
 #: default cap on the workspace of one call (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = _lib.GF_SOLVE_WORKSPACE_BYTES
@@ -123,3 +125,56 @@ def solve_batch(engine, Jr, Jc, real, comp, diag_add, component=None, cap_bytes=
             events.append((e0, e1))
         return dict(alpha=alpha, mu=mu, mu_comp=mu_comp, ll=ll, info=info, workspace_bytes=8 * per * group,
                     groups=ngroups, group_size=group, events=events)
+
+
+def predict_at(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):
+    """Enqueue ``gf_predict_batch_at`` over an engine's time axes: K*(t*, t) alpha of the B problems for stacked host
+    coefficient arrays ``real`` (2, B, max(Jr, 1)), ``comp`` (4, B, max(Jc, 1)) -- the full kernel's or a component's
+    -- and ``alpha`` (B, N) on the device (:func:`solve_batch`).  ``ts``: the query stamps, (M,) or (1, M) shared,
+    or (B, M), ascending per problem (host array or device tensor).  ``nobs`` / ``nq``: (B,) real observed rows and
+    real queries per problem, or None for N / M; result rows from ``nq[b]`` on are never written (the caller cuts them
+    off).  Returns dict(``mu`` (B, M) device tensor, ``events``: one pair of HIP events around the launch).  No host
+    synchronisation."""
+    W = Jr + 2 * Jc
+    if W < 1:
+        raise ValueError("the kernel has no terms")
+    check_width(W)
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, np.zeros(B))
+    if tuple(alpha.shape) != (B, N) or alpha.dtype != torch.float64:
+        raise ValueError(f"alpha of shape {tuple(alpha.shape)} does not hold the batch's ({B}, {N}) rows")
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    lib, p = engine.lib, _lib.ptr
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ts = torch.as_tensor(ts, dtype=torch.float64).to(dev)
+        if ts.ndim == 1:
+            ts = ts[None, :]
+        if ts.ndim != 2 or ts.shape[0] not in (1, B) or ts.shape[1] < 1:
+            raise ValueError(f"query times of shape {tuple(ts.shape)} for a batch of {B} problems")
+        ts = ts.contiguous()
+        alpha = alpha.contiguous()
+        M = int(ts.shape[1])
+        counts = []
+        for cnt, full in ((nobs, N), (nq, M)):
+            if cnt is not None:
+                cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+                if cnt.shape != (B,) or np.any(cnt < 0) or np.any(cnt > full):
+                    raise ValueError("dimension mismatch")
+                cnt = torch.as_tensor(cnt, **i64)
+            counts.append(cnt)
+        mu = torch.empty((B, M), **f64)
+        cr_ = torch.as_tensor(np.ascontiguousarray(real, dtype=np.float64), **f64)
+        cc_ = torch.as_tensor(np.ascontiguousarray(comp, dtype=np.float64), **f64)
+        t = engine.t
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        st = lib.gf_predict_batch_at(
+            B, N, M, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]),
+            p(t), engine._bs(t), p(counts[0]), p(ts), engine._bs(ts), p(counts[1]),
+            p(alpha), N, p(mu), M, stream)
+        _lib.check(st, "gf_predict_batch_at")
+        e1.record()
+    return dict(mu=mu, events=[(e0, e1)])

@@ -653,6 +653,32 @@ int gf_solve_batch(int B, int64_t N, int Jr, int Jc,
                    const double *y, int64_t y_bs, int64_t seg, double *work, int64_t work_bs,
                    double *alpha, double *mu, double *mu_comp, double *ll, int32_t *info, void *stream);
 
+/*
+ * Conditional means of B problems at new times t* (DESIGN.md 3.11): what celerite2's general_matmul_lower +
+ * general_matmul_upper between two sorted axes give one kernel at a time (GaussianProcess.predict(y, t=t*) after
+ * apply_inverse), for alpha = K^-1 (y - mean) already on the device (gf_solve_batch):
+ *     mu[b][m] = sum_{t_n <= t*_m} (U*_m o e^{-c (t*_m - t_n)}) . V_n alpha_n
+ *              + sum_{t_n >  t*_m} (V*_m o e^{-c (t_n - t*_m)}) . U_n alpha_n
+ * an observed stamp that coincides with a query counting in the first sum.  Exact generator rows on every row, made in
+ * registers (no U, V, P arrays, no workspace).  One wave per problem; W = Jr + 2 Jc <= 63 (-3 beyond).
+ *   coefficients as gf_solve_batch: ar, cr [B][max(Jr,1)]; ac, bc, cc, dc [B][max(Jc,1)] -- of the full kernel or
+ *     of one of its parts (the share of that part at t*)
+ *   t [N], ts [M]: observed and query stamps, ascending per problem, batch strides in elements (0 = shared)
+ *   nobs, nq [B] (either may be NULL: N, M): the real observed rows and the real queries of problem b, clamped to
+ *     0 .. N and 0 .. M; t and alpha from nobs[b] on are never read, mu from nq[b] on is never written
+ *   alpha [B][alpha_bs >= N], mu [B][mu_bs >= M] (the strides are not looked at when B = 1)
+ * A problem whose alpha is NaN (a failed gf_solve_batch) gets NaN in all its rows.  No atomics: results are
+ * bit-identical from run to run, do not depend on the other problems of the call, and a query's value does not
+ * depend on the other queries of its problem.
+ */
+int gf_predict_batch_at(int B, int64_t N, int64_t M, int Jr, int Jc,
+                        const double *ar, const double *cr, const double *ac,
+                        const double *bc, const double *cc, const double *dc,
+                        const double *t, int64_t t_bs, const int64_t *nobs,
+                        const double *ts, int64_t ts_bs, const int64_t *nq,
+                        const double *alpha, int64_t alpha_bs,
+                        double *mu, int64_t mu_bs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

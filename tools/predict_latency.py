@@ -10,7 +10,13 @@ predict_numpy_ms: predict(), the results copied to the host as numpy, wall time 
 evaluate_device_ms: HIP events around evaluate_device(pack_parameters(...)) at generator_period = 1 on the same batch;
 loop_ms_per_problem: GaussianProcess(kernel_b, t, yerr).predict(y[, kernel=sub]) one kernel at a time, wall time
 per problem (median over `--loop` problems after one warm-up); loop_scaled_ms = that times B; speedup_over_loop =
-loop_scaled_ms / predict_numpy_ms."""
+loop_scaled_ms / predict_numpy_ms.
+
+`--at a,b` measures prediction at new times instead, one JSON line per leg: (a) the walkers with a query
+at every mid-cadence, M = N; (b) the cfg3-shaped batch on a grid that lost 10 % of its cadences, the queries filling
+them.  solve_device_ms: the gf_solve_batch launches of predict_device(t=...) (HIP events, summed over the groups);
+at_device_ms: the gf_predict_batch_at launch that follows them; at_over_solve their ratio; each a median of `--reps`
+calls, without and with a component."""
 import argparse
 import json
 import os
@@ -57,24 +63,70 @@ def kernel_of(S0, w0, Q, delta, first=None):
                                      for s, w, q in list(zip(S0, w0, Q))[:first]]), delta)
 
 
+def walkers(B, J, rng):
+    """(kernel, S0, w0, Q (B, J), delta): proposals around the solar-like kernel's own parameters (Q untouched: every
+    proposal keeps its overdamped terms)."""
+    kern = gadfly_amd.StellarOscillatorKernel(solar_like_hyperparameters(J), texp=60.0)
+    terms = kern.term.terms
+    base = [np.array([[getattr(tm, k) for tm in terms]]) for k in ("S0", "w0", "Q")]
+    S0, w0 = (np.repeat(b, B, axis=0) * np.exp(0.05 * rng.normal(size=(B, J))) for b in base[:2])
+    return kern, S0, w0, np.repeat(base[2], B, axis=0), float(kern.delta)
+
+
+def at_legs(names, reps, rng):
+    for name in names:
+        B, N, J = SHAPES[name]
+        kern, S0, w0, Q, delta = walkers(B, J, rng)
+        if name == "a":                                 # a query between every two cadences and one past the end
+            t = uniform_times(N, 60.0)
+            ts = t + 30e-6
+        else:                                           # a grid that lost 10 % of its cadences: fill them
+            grid = uniform_times(int(round(N / 0.9)), 60.0)
+            keep = np.zeros(len(grid), dtype=bool)
+            keep[rng.choice(len(grid), size=N, replace=False)] = True
+            t, ts = grid[keep], grid[~keep]
+        y = 100.0 * rng.normal(size=N)
+        first = J // 3
+        ev = gadfly_amd.BatchedLogLikelihood([kern] * B, t, y, yerr=30.0)
+        pack = sho_coefficient_pack(S0, w0, Q, delta)
+        sub = sho_coefficient_pack(S0[:, :first], w0[:, :first], Q[:, :first], delta)
+        for comp in (False, True):
+            solve, at, wall = [], [], []
+            for r in range(reps + 1):                   # (the first call warms up and is dropped)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                mu = ev.predict_device(pack, kernel=sub if comp else None, t=ts)
+                torch.cuda.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e3)
+                at.append(ev.last_predict_at_ms)
+                solve.append(ev.last_predict_device_ms - at[-1])
+                finite = bool(torch.isfinite(mu).all())
+                del mu
+            s_ms, a_ms = float(np.median(solve[1:])), float(np.median(at[1:]))
+            print(json.dumps(dict(leg="at_" + name, B=B, N=N, M=len(ts), J=J, W=2 * J,
+                                  component_W=2 * first if comp else 0, solve_device_ms=round(s_ms, 2),
+                                  at_device_ms=round(a_ms, 2), at_over_solve=round(a_ms / s_ms, 3),
+                                  predict_api_ms=round(float(np.median(wall[1:])), 2), finite=finite,
+                                  groups=int(ev.last_predict_plan[1]), reps=reps)), flush=True)
+        del ev
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="a,b,c")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop", type=int, default=16)
+    ap.add_argument("--at", default="", help="legs of the prediction at new times (a, b) to measure instead")
     args = ap.parse_args()
     rng = np.random.Generator(np.random.PCG64(2024))
+    if args.at:
+        return at_legs(args.at.split(","), args.reps, rng)
     for name in args.shapes.split(","):
         B, N, J = SHAPES[name]
-        kern = gadfly_amd.StellarOscillatorKernel(solar_like_hyperparameters(J), texp=60.0)
-        terms = kern.term.terms
-        base = [np.array([[getattr(tm, k) for tm in terms]]) for k in ("S0", "w0", "Q")]
-        # proposals around the kernel's own parameters (Q untouched: every proposal keeps its overdamped terms)
-        S0, w0 = (np.repeat(b, B, axis=0) * np.exp(0.05 * rng.normal(size=(B, J))) for b in base[:2])
-        Q = np.repeat(base[2], B, axis=0)
+        kern, S0, w0, Q, delta = walkers(B, J, rng)
         t = uniform_times(N, 60.0)
         y = 100.0 * rng.normal(size=N)
-        delta = float(kern.delta)
         first = J // 3
         ev = gadfly_amd.BatchedLogLikelihood([kern] * B, t, y, yerr=30.0)
         ev.auto_generator_period = False
