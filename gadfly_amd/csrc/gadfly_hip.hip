@@ -1251,19 +1251,24 @@ __device__ __forceinline__ void sweep7_run(double (&T)[ROWS / 2][2], double2 (&u
 // resets whatever the scaling block, a power of two <= 64: rho = 1, exact phasor) from global row arm_from on, the
 // wave compares d and its lanes' gain components with the values of ST_LAG such anchors before -- 1024 ROWS, so
 // that the rule means the same at every block -- (a ring in the per-problem steady buffer); once both have moved
-// by less than ST_THR -- the gains relative to the largest gain -- at ST_COUNT consecutive anchors it freezes them, moves
-// the forward-solve column to one entry per lane and continues in the tail loop: generator step,
-// F~ += w~_{n-1} z_{n-1}, z_n = y_n - u~_n . F~, block decays, d_n = d_inf.  Later tiles enter the tail directly
-// (no state load).  A row the tail cannot take -- a gap reset, a spacing off the frozen cadence -- raises the
+// by less than ST_THR -- the gains relative to the largest gain -- at ST_COUNT consecutive anchors it freezes them,
+// leaves the derotated forward-solve state s_k = e^{-i d_k t} (F_2k + i F_2k+1) (this row's update folded), the gains,
+// the pivot and the cadence (over the last 1024 rows) in the buffer and ends.  The rows after belong to k_steady_tail
+// (below), which gf_loglike_steady launches behind this kernel on every tile; on later tiles this kernel returns at
+// once for such a problem.  A row the tail cannot take -- a gap reset, a spacing off the frozen cadence -- raises the
 // buffer's violation flag: the caller repeats the evaluation without the mode.
 constexpr int ST_SW = 0;            // first tail row (global) ; 0 = full mode
 constexpr int ST_D = 1;             // frozen pivot
 constexpr int ST_VIOL = 2;          // != 0: the tail met a row it cannot take
 constexpr int ST_CNT = 3;           // consecutive converged anchors so far
 constexpr int ST_FILL = 4;          // anchors in the ring
-constexpr int ST_DT = 6;            // frozen cadence
-constexpr int ST_M1 = 8, ST_M2 = 72;        // [64] gain constants by column: w~ = (m1 cu + m2 su) / rho^2
+constexpr int ST_HOK = 5;           // != 0: the tail's impulse response is in ST_H
+constexpr int ST_DT = 6;            // frozen cadence: (t_sw - t_{sw - 1024}) / 1024
+constexpr int ST_GR = 8, ST_GI = 40;        // [32] frozen derotated gain G_k by term
+constexpr int ST_SR = 72, ST_SI = 104;      // [32] the tail's state s_k by term, as of the last row done
 constexpr int ST_RING = 136;        // [ST_LAG][64] gain component per lane (lane 63: the pivot)
+constexpr int ST_H = ST_RING;       // [64] the tail's impulse response (the ring is dead after the switch)
+constexpr int ST_DLAG = 1024;       // rows behind the switch row that the cadence is taken over
 constexpr int ST_GRID = 64;         // rows between the anchors the rule looks at
 constexpr int ST_LAG = 16, ST_COUNT = 4;
 constexpr double ST_THR = 1e-10;
@@ -1291,6 +1296,9 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     const int pr = sel / nsel, ch = ch0 + (sel - pr * nsel);
     const int b = pr * nch + ch;                    // state slot = problem * nch + chunk
     if (info[b] != 0) return;
+    // steady mode: this problem's buffer; a problem that has switched is k_steady_tail's from its switch row on
+    double *__restrict__ hdr = STEADY ? steady_ + (size_t)pr * ST_SIZE : nullptr;
+    if constexpr (STEADY) { if (hdr[ST_SW] > 0.0) return; }
     const int64_t c0 = (int64_t)ch * chunk_len;
     const int64_t rows = (N - c0 < chunk_len) ? (N - c0) : chunk_len;
     const int64_t g0 = n_first + c0;
@@ -1333,26 +1341,16 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     double *__restrict__ col1 = (f31 ? Fg : Sg + (size_t)(2 * c + 1) * 64) + 2 * g;
     double T[ROWS / 2][2];
     const bool zero_start = (block_sub >> 30) & 1;  // nominal pass: the state slots are outputs only
-    // steady mode: this problem's buffer; the tail's per-lane state (gain constants, F~ of the own column)
-    double *__restrict__ hdr = STEADY ? steady_ + (size_t)pr * ST_SIZE : nullptr;
-    bool tail = false;
-    double m1 = 0.0, m2 = 0.0, Ft = 0.0, dinf = 0.0, dtinf = 0.0;
     constexpr double thr = ST_THR;
-    int cnt = 0, fill = 0;
+    int cnt = 0, fill = 0;                          // steady mode: the rule's counters
     if constexpr (STEADY) {
-        tail = __builtin_amdgcn_readfirstlane((int)(hdr[ST_SW] > 0.0)) != 0;
-        if (!tail) {
-            cnt = __builtin_amdgcn_readfirstlane((int)hdr[ST_CNT]);
-            fill = __builtin_amdgcn_readfirstlane((int)hdr[ST_FILL]);
-        }
+        cnt = __builtin_amdgcn_readfirstlane((int)hdr[ST_CNT]);
+        fill = __builtin_amdgcn_readfirstlane((int)hdr[ST_FILL]);
     }
-    const bool tail0 = tail;                        // a tile that starts in the tail: no state load
-    if (!tail) {
 #pragma unroll
-        for (int m = 0; m < ROWS / 2; ++m) {
-            T[m][0] = zero_start ? 0.0 : col0[4 * (m >> 1) + (m & 1)];
-            T[m][1] = zero_start ? 0.0 : col1[4 * (m >> 1) + (m & 1)];
-        }
+    for (int m = 0; m < ROWS / 2; ++m) {
+        T[m][0] = zero_start ? 0.0 : col0[4 * (m >> 1) + (m & 1)];
+        T[m][1] = zero_start ? 0.0 : col1[4 * (m >> 1) + (m & 1)];
     }
     double q0 = 0.0, q1 = 0.0;
     int32_t fail = 0;
@@ -1371,7 +1369,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
     sweep7_preload<ROWS>(ub, wb, pu, pw);
 
     int64_t n = 0;
-    for (; n < rows && !tail; ++n) {
+    for (; n < rows; ++n) {
         const double a_n = (has_g ? g_n : 0.0) + diag_add, yy = y_n;
         const double ut_c = ut, vt_c = vt;
         const bool rst_c = rst;
@@ -1447,12 +1445,10 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
                 fill = fill < ST_LAG ? fill + 1 : fill;
                 if (lane == 0) { hdr[ST_CNT] = (double)cnt; hdr[ST_FILL] = (double)fill; }
                 if (cnt >= ST_COUNT && G.dt_ref > 0.0) {       // (a cached cadence: not on a tile's first row)
-                    // the switch: freeze pivot and gains; the forward-solve column (this row's update folded)
-                    // goes from the tiled layout (block 31, rows split over the half-waves) to one entry per lane
-                    dinf = dn;
-                    dtinf = G.dt_ref;
-                    m1 = g ? Gi : Gr;
-                    m2 = g ? Gr : -Gi;
+                    // the switch: freeze pivot and gains and hand the rest of the series to k_steady_tail.  The
+                    // forward-solve column (this row's update folded; rho = 1 at an anchor) goes from the tiled layout
+                    // (block 31, rows split over the half-waves) through LDS to the lanes of its terms, which turn it
+                    // back by the anchor's phase: s = e^{-i d t} (F_2c + i F_2c+1)
                     wave_lds_fence();
                     if (f31) {
 #pragma unroll
@@ -1462,64 +1458,21 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
                         }
                     }
                     wave_lds_fence();
-                    Ft = (own < ROWS) ? s_e[own] : 0.0;
-                    hdr[ST_M1 + own] = m1;
-                    hdr[ST_M2 + own] = m2;
-                    if (lane == 0) { hdr[ST_SW] = (double)(gn + 1); hdr[ST_D] = dinf; hdr[ST_DT] = dtinf; }
-                    tail = true;                    // (the loop ends here; row n + 1 is the tail's first)
+                    const double F0 = (2 * c + 1 < ROWS) ? s_e[2 * c] : 0.0, F1 = (2 * c + 1 < ROWS) ? s_e[2 * c + 1] : 0.0;
+                    if (g == 0) {                   // (pad terms: cs = sn = 0, so their gain and state are zero)
+                        hdr[ST_GR + c] = Gr;
+                        hdr[ST_GI + c] = Gi;
+                        hdr[ST_SR + c] = fma(cs, F0, sn * F1);
+                        hdr[ST_SI + c] = fma(cs, F1, -sn * F0);
+                    }
+                    if (lane == 0) {
+                        hdr[ST_SW] = (double)(gn + 1);
+                        hdr[ST_D] = dn;
+                        hdr[ST_DT] = (tg[n] - tg[n - ST_DLAG]) * (1.0 / ST_DLAG);
+                    }
+                    return;                         // (row n + 1 is the tail's first)
                 }
             }
-        }
-    }
-    if constexpr (STEADY) {
-        if (tail && !fail) {
-            // the tail: ut / rst / de and the generator stand at row n, as at the top of the full loop
-            if (tail0) {
-                m1 = hdr[ST_M1 + own];
-                m2 = hdr[ST_M2 + own];
-                Ft = Fg[own];
-                dinf = hdr[ST_D];
-                dtinf = hdr[ST_DT];
-            }
-            double wt_p = 0.0, z_p = 0.0;           // pending update w~_{n-1} z_{n-1} (folded at the switch / tile end)
-            // (the tail's first row, then each next row: only the plain step, the sub-anchor and the block reset
-            // keep the frozen gains valid)
-            bool viol = false;
-            if (g0 + n > 0 && n < rows) {
-                const double dt0 = tg[n] - tg[n - 1];
-                viol = (dt0 > G.gthr) || !(fabs(dt0 - dtinf) < G.jthr);
-            }
-            // Rows in chunks of 64: t and y arrive by one coalesced load per chunk, issued a chunk ahead, and are
-            // handed out by readlane; d and z leave by one coalesced store per chunk.  (A scalar load per row, as
-            // in the full loop, is waited for within the row after the one that issued it, and a store per row
-            // holds every later vector-memory wait up: a tail row is too short to hide either.)  The indices are
-            // clamped to what the full loop's own prefetch reads at most.
-            const int64_t t_last = rows + 2, y_last = rows - 1;
-            auto chunk_t = [&](const int64_t cb) { const int64_t i = cb + 1 + lane; return tg[i < t_last ? i : t_last]; };
-            auto chunk_y = [&](const int64_t cb) { const int64_t i = cb + lane; return yg[i < y_last ? i : y_last]; };
-            double tv_n = chunk_t(n), yv_n = chunk_y(n);
-            for (int64_t cb = n; cb < rows; cb += 64) {
-                const double tv = tv_n, yv = yv_n;  // t of rows cb + 1 + lane, y of rows cb + lane
-                tv_n = chunk_t(cb + 64);
-                yv_n = chunk_y(cb + 64);
-                const int lim = (int)(rows - cb < 64 ? rows - cb : 64);
-                double zv = 0.0;
-                for (int k = 0; k < lim; ++k) {
-                    const double yy = read_lane(yv, k), t_nx = read_lane(tv, k);
-                    Ft = fma(wt_p, z_p, Ft);
-                    if (rst) Ft *= fm_exp(-cj * de);        // block reset: decay of the own column (pads: 1)
-                    wt_p = fma(m1, G.cu, m2 * G.su) * G.irho2;
-                    z_p = yy - wave_sum(ut * Ft);
-                    const double dtn = t_nx - G.t_m1;
-                    if (cb + k + 1 < rows) viol |= (dtn > G.gthr) || !(fabs(dtn - dtinf) < G.jthr);
-                    G.next(t_nx, g0 + cb + k + 1, ut, vt, rst, de);
-                    zv = (lane == k) ? z_p : zv;
-                }
-                if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
-            }
-            Fg[own] = fma(wt_p, z_p, Ft);
-            if (viol && lane == 0) hdr[ST_VIOL] = 1.0;
-            return;
         }
     }
     if (fail) {
@@ -1549,6 +1502,183 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
         if (f31)                                    // S's own column 63 (these lanes' second column is F~)
             for (int m = 0; m < 32; ++m) Sg[63 * 64 + 2 * g + 4 * (m >> 1) + (m & 1)] = 0.0;
     }
+}
+
+// ------------------------------------------------------------------------------------
+// k_steady_tail: the rows behind the switch of the steady mode, as a time-invariant filter in blocks of 64 rows.
+//
+// With pivot, gains and cadence frozen, a row is  x = lambda o s ;  z_n = y_n - sum_k Re(alpha_k x_k) ;
+// s = x + G z_n  with, per complex term k, alpha = a + i b, lambda = exp(-(c + i d) Delta), G the derotated gain and
+// s the derotated forward-solve state (this row's update folded): no row generator, no block scaling, no resets,
+// and no reduction on the row's chain.  A block of 64 rows from incoming s:
+//   p_i  = y_i - sum_k Re(alpha_k lambda_k^(i+1) s_k)       lane = row; s by LDS broadcast, coefficients in registers
+//   z    = H p,  H lower-triangular Toeplitz of the impulse response h(0 .. 63)     (h(63) ~ 5e-3 on the flagship
+//          kernel: H is not truncated); lane i reads p[i - m] from an LDS image of p with 64 zeros in front
+//   s   <- lambda^2 s + lambda G z_j + G z_j+1              lane = term, two rows per step, z by LDS broadcast
+// h is the row form's answer to a unit impulse, computed at the problem's first tail entry of an evaluation and kept
+// in the steady buffer; the p coefficients are recomputed at every launch (per lane one fm_sincos + fm_exp per term,
+// through an LDS staging area of 8 terms so that the loop over the terms is not unrolled around them).
+// One wave per problem, grid B; rows [max(switch row + 1, tile start), tile end) of a problem that has switched.
+// t and y arrive by one coalesced load per block, issued a block ahead; d (= d_inf) and z leave by one coalesced
+// store per block.  A partial last block runs the same code: H is lower triangular, so the rows beyond the tile
+// (y clamped to the last row) touch no row before them; the s loop is bounded and the stores are masked.
+// Every spacing t_r - t_{r-1} of a tail row r is tested as RowGen tests it (a gap: > gthr; off the frozen cadence:
+// >= jthr): a hit raises ST_VIOL and the rows of that evaluation mean nothing (finite).
+// ------------------------------------------------------------------------------------
+constexpr int STT_STAGE = 8;        // terms per staging pass of the p coefficients
+
+template <int ROWS>
+__global__ void __launch_bounds__(64, 2)
+k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double gap,
+              const double *__restrict__ ac_, const double *__restrict__ bc_,
+              const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
+              const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
+              double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
+              double *__restrict__ steady_) {
+    constexpr int JT = ROWS / 2;                    // term slots (Jc <= JT <= 32; slots from Jc on are zero)
+    const int lane = threadIdx.x, pr = blockIdx.x;
+    if (info[pr] != 0) return;
+    double *__restrict__ hdr = steady_ + (size_t)pr * ST_SIZE;
+    const double swd = hdr[ST_SW];
+    if (!(swd > 0.0)) return;
+    const int64_t sw = (int64_t)swd;                // first tail row (global, >= 1)
+    const int64_t nb = sw > n_first ? sw - n_first : 0;     // first tail row of this tile (local)
+    if (nb >= N) return;
+    const double *__restrict__ tg = t_ + (size_t)pr * t_bs + n_first;
+    const double *__restrict__ yg = y_ + (size_t)pr * y_bs + n_first;
+    double *__restrict__ dg = d_ + (size_t)pr * N;
+    double *__restrict__ zg = z_ + (size_t)pr * N;
+    const double dinf = hdr[ST_D], delta = hdr[ST_DT];
+
+    __shared__ __attribute__((aligned(16))) double s_s[64];         // (s_r, s_i) of term k at [2k], [2k + 1]
+    __shared__ __attribute__((aligned(16))) double s_p[128];        // 64 zeros, then p of the block
+    __shared__ __attribute__((aligned(16))) double s_h[64];         // impulse response
+    __shared__ __attribute__((aligned(16))) double s_z[64];         // z of the block
+    __shared__ double s_c[STT_STAGE][2][64];                        // staging of the p coefficients
+
+    // lane = term: this term's constants and state
+    const bool term = lane < Jc;
+    const size_t ck = (size_t)pr * Jc + (term ? lane : 0);
+    const double ck_c = term ? cc_[ck] : 0.0, ck_d = term ? dc_[ck] : 0.0;
+    const double ck_a = term ? ac_[ck] : 0.0, ck_b = term ? bc_[ck] : 0.0;
+    const double wmax = wave_max(fmax(ck_c, fabs(ck_d)));
+    const double gthr = gap / cmax_[pr], jthr = 2e-6 / wmax;        // RowGen::init's thresholds
+    double lr, li;                                                  // lambda = exp(-c Delta) (cos - i sin)(d Delta)
+    {
+        double sn, cs;
+        fm_sincos(ck_d * delta, &sn, &cs);
+        const double e = fm_exp(-ck_c * delta);
+        lr = e * cs;
+        li = -e * sn;
+    }
+    const double Gr = (lane < 32) ? hdr[ST_GR + (lane & 31)] : 0.0, Gi = (lane < 32) ? hdr[ST_GI + (lane & 31)] : 0.0;
+    double sr = (lane < 32) ? hdr[ST_SR + (lane & 31)] : 0.0, si = (lane < 32) ? hdr[ST_SI + (lane & 31)] : 0.0;
+    const double l2r = fma(lr, lr, -li * li), l2i = 2.0 * lr * li;  // lambda^2
+    const double lgr = fma(lr, Gr, -li * Gi), lgi = fma(lr, Gi, li * Gr);   // lambda G
+
+    // impulse response: the row form on y = (1, 0, 0, ...) from s = 0, once per evaluation
+    if (hdr[ST_HOK] != 0.0) {
+        s_h[lane] = hdr[ST_H + lane];
+    } else {
+        double hr = Gr, hi = Gi, hv = (lane == 0) ? 1.0 : 0.0;      // h(0) = 1, s = G
+        for (int m = 1; m < 64; ++m) {
+            const double xr = fma(lr, hr, -li * hi), xi = fma(lr, hi, li * hr);
+            const double hm = -wave_sum(fma(ck_a, xr, -ck_b * xi));
+            hr = fma(Gr, hm, xr);
+            hi = fma(Gi, hm, xi);
+            hv = (lane == m) ? hm : hv;
+        }
+        s_h[lane] = hv;
+        hdr[ST_H + lane] = hv;
+        if (lane == 0) hdr[ST_HOK] = 1.0;
+    }
+    s_p[lane] = 0.0;
+
+    // lane = row of a block: -alpha_k lambda_k^(i+1) = (pr_k, pi_k) with Re(.) taken against (s_r, s_i):
+    // p = y + sum_k pr_k s_r,k + pi_k s_i,k
+    double pcr[JT], pci[JT];
+    const double di = delta * (double)(lane + 1);
+#pragma unroll
+    for (int k0 = 0; k0 < JT; k0 += STT_STAGE) {
+        wave_lds_fence();
+#pragma unroll 1
+        for (int kk = 0; kk < STT_STAGE; ++kk) {
+            const int k = k0 + kk;
+            double vr = 0.0, vi = 0.0;
+            if (k < Jc) {                           // wave-uniform
+                const size_t uk = (size_t)pr * Jc + k;
+                const double a = ac_[uk], b = bc_[uk];
+                double sn, cs;
+                fm_sincos(dc_[uk] * di, &sn, &cs);
+                const double e = fm_exp(-cc_[uk] * di);
+                vr = -e * fma(a, cs, b * sn);       // Re(alpha lambda^(i+1)), Im = e (b cs - a sn)
+                vi = e * fma(b, cs, -a * sn);
+            }
+            s_c[kk][0][lane] = vr;
+            s_c[kk][1][lane] = vi;
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int kk = 0; kk < STT_STAGE; ++kk) {
+            if (k0 + kk < JT) { pcr[k0 + kk] = s_c[kk][0][lane]; pci[k0 + kk] = s_c[kk][1][lane]; }
+        }
+    }
+
+    const int64_t last = N - 1;
+    auto row_of = [&](const int64_t cb) { const int64_t i = cb + lane; return i < last ? i : last; };
+    bool viol = false;
+    double y_nx = yg[row_of(nb)], t_nx = tg[row_of(nb)], tp_nx = tg[row_of(nb) - 1];
+    for (int64_t cb = nb; cb < N; cb += 64) {
+        const double yv = y_nx, tv = t_nx, tp = tp_nx;              // rows cb + lane (clamped to the tile's last)
+        {
+            const int64_t i = row_of(cb + 64);
+            y_nx = yg[i]; t_nx = tg[i]; tp_nx = tg[i - 1];
+        }
+        const int lim = (int)(N - cb < 64 ? N - cb : 64);
+        const double dt = tv - tp;
+        viol |= (lane < lim) && ((dt > gthr) || !(fabs(dt - delta) < jthr));
+        wave_lds_fence();
+        if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
+        wave_lds_fence();
+        double p0 = yv, p1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < JT; ++k) {
+            const double2 sv = ((const double2 *)s_s)[k];
+            if (k & 1) p1 = fma(pci[k], sv.y, fma(pcr[k], sv.x, p1));
+            else p0 = fma(pci[k], sv.y, fma(pcr[k], sv.x, p0));
+        }
+        s_p[64 + lane] = p0 + p1;
+        wave_lds_fence();
+        double z0 = 0.0, z1 = 0.0;
+        const double *pp = s_p + 64 + lane;
+#pragma unroll
+        for (int m = 0; m < 64; m += 2) {
+            const double2 hv = ((const double2 *)s_h)[m >> 1];
+            z0 = fma(hv.x, pp[-m], z0);
+            z1 = fma(hv.y, pp[-m - 1], z1);
+        }
+        const double zv = z0 + z1;
+        s_z[lane] = zv;
+        wave_lds_fence();
+        if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
+        int j = 0;
+#pragma unroll 4
+        for (; j + 1 < lim; j += 2) {
+            const double2 zz = ((const double2 *)s_z)[j >> 1];
+            const double wr = fma(lgr, zz.x, Gr * zz.y), wi = fma(lgi, zz.x, Gi * zz.y);
+            const double nr = fma(l2r, sr, fma(-l2i, si, wr));
+            si = fma(l2r, si, fma(l2i, sr, wi));
+            sr = nr;
+        }
+        if (j < lim) {
+            const double zj = s_z[j];
+            const double nr = fma(lr, sr, fma(-li, si, Gr * zj));
+            si = fma(lr, si, fma(li, sr, Gi * zj));
+            sr = nr;
+        }
+    }
+    if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
+    if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
 }
 
 #define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -5541,6 +5671,7 @@ static bool sweep_tiled(int variant, int Jr, int Jc) {
 #define GF_F7_NOSTEADY (double *)nullptr, (int64_t)0
 #define GF_S3_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_factor7<R, false, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R, true>), GF_F3_ARGS); break;
 #define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else if (steady) hipLaunchKernelGGL((k_factor7<R, false, false, true>), GF_F3_ARGS, steady, arm_from); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
+#define GF_ST_CASE(R) case R: hipLaunchKernelGGL((k_steady_tail<R>), dim3(B), dim3(64), 0, st, N, n_first, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, d, z, info, steady); break;
 
 static int check_sweep_options(const char *who, int gen_period, int variant, int Jr, int Jc) {
     if (gen_period < 1 || gen_period > 64 || (gen_period & (gen_period - 1)))
@@ -5624,6 +5755,15 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
         GF_F3_CASE(28) GF_F3_CASE(32) GF_F3_CASE(36) GF_F3_CASE(40) GF_F3_CASE(44) GF_F3_CASE(48)
         GF_F3_CASE(52) GF_F3_CASE(56) GF_F3_CASE(60) GF_F3_CASE(64)
         default: return set_err("%s: internal dispatch error", who);
+    }
+    if (steady) {                       // the rows of this tile behind each problem's switch row (same stream)
+        if (const int e = check_launch(who)) return e;
+        switch (rows) {
+            GF_ST_CASE(4) GF_ST_CASE(8) GF_ST_CASE(12) GF_ST_CASE(16) GF_ST_CASE(20) GF_ST_CASE(24)
+            GF_ST_CASE(28) GF_ST_CASE(32) GF_ST_CASE(36) GF_ST_CASE(40) GF_ST_CASE(44) GF_ST_CASE(48)
+            GF_ST_CASE(52) GF_ST_CASE(56) GF_ST_CASE(60) GF_ST_CASE(64)
+            default: return set_err("%s: internal dispatch error", who);
+        }
     }
     return check_launch(who);
 }

@@ -192,9 +192,12 @@ int gf_loglike_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int bloc
  * promise: regular cadence, constant diagonal, from there to the end of the series; arm_from >= N: never) the
  * sweep compares both, at the rows = 0 mod 64 (block resets at every block), with their values 16 such rows --
  * 1024 rows -- before; once they have moved by less than 1e-10 (gains: relative to the largest) at 4 consecutive
- * ones it freezes them and runs only the
- * forward solve on all later rows and tiles.  d, z, info, S_state, F_state as for gf_loglike_fused (S_state is
- * no longer maintained after the switch).
+ * ones it freezes them and ends.  All later rows and tiles of that problem belong to a second kernel, launched
+ * on the same stream behind the sweep on every call: with pivot, gains and cadence (taken over the last 1024 rows)
+ * frozen, the forward solve is a linear time-invariant filter with Jc complex poles, run in blocks of 64 rows
+ * (k_steady_tail in gadfly_hip.hip).  d, z, info, S_state, F_state as for gf_loglike_fused (S_state and F_state
+ * are no longer maintained after the switch: the filter's state lives in `steady`).  t must be readable from
+ * global row 0 on whatever n_first (the cadence looks 1024 rows behind the switch row).
  *   steady [B][gf_steady_size()] doubles, zeroed by the caller before the FIRST tile of an evaluation and
  *          handed unchanged to the following tiles.  Per problem: [0] first frozen row (global index; 0 = the
  *          mode has not been entered), [1] the frozen pivot, [2] != 0: VIOLATION -- a frozen row met a gap or a

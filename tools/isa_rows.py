@@ -4,7 +4,8 @@
     python tools/isa_rows.py --asm out.s           # count an existing `hipcc --cuda-device-only -S` listing
     python tools/isa_rows.py --kernel k_factor7 --rows 40 --rowstore
     python tools/isa_rows.py --kernel k_factorw --rows 44 --sample   # the sampling instance (gf_sample_fused)
-    python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: the full row loop AND the tail loop
+    python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: its full row loop, AND
+                                                   # k_steady_tail<60>: its block loop, per 64-row block and per row
 
 Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
 most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
@@ -102,6 +103,46 @@ def counts(ins):
     return c
 
 
+def steady_tail(lines, rows):
+    """k_steady_tail<rows>: the block loop (the smallest loop around the block with the most FMAs: p and H p) and
+    the loops inside it (the s update, two rows per step, unrolled).  Instructions per 64-row block = the block loop's
+    own instructions + each inner loop's body times its trips for 64 rows."""
+    bl = blocks(kernel_body(lines, "k_steady_tail", rows, None))
+    tag = kernel_tag("k_steady_tail", rows, None, False)
+    vgpr = next((ln.split(",")[-1].strip() for ln in lines if ".num_vgpr," in ln and tag.search(ln)), "?")
+    total = counts([op for b in bl for op in b["ins"]])
+    print(f"k_steady_tail<{rows}>: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, "
+          f"{total['scratch']} scratch (spill) in all; {vgpr} VGPRs")
+    reg = max(range(len(bl)), key=lambda i: counts(bl[i]["ins"])["fma"])
+    i0, i1 = row_loop(bl, reg)
+    idx = {b["name"]: i for i, b in enumerate(bl)}
+    inner = sorted({(idx[t], j) for j in range(i0, i1 + 1) for t in bl[j]["targets"]
+                    if t in idx and i0 <= idx[t] <= j and not (idx[t] <= reg <= j)})
+    inner = [r for r in inner if not any(o != r and o[0] <= r[0] and r[1] <= o[1] for o in inner)]
+    keys = ("valu", "lds", "salu", "branch")
+    dyn = dict.fromkeys(keys, 0.0)
+    in_inner = set()
+    print(f"block loop: blocks {bl[i0]['name']} .. {bl[i1]['name']}")
+    sized = [(counts([op for k in range(a0, a1 + 1) for op in bl[k]["ins"]]), a0, a1) for a0, a1 in inner]
+    main_fma = max((c["fma"] for c, _, _ in sized), default=0)
+    for c, a0, a1 in sized:
+        # a two-row step is 6 FMAs + 2 multiplies; the loop with the most FMAs is the unrolled one, the others are
+        # its remainder (not taken in a full block of 64 rows)
+        rows_per_trip = max(c["fma"] // 3, 1)
+        trips = 64.0 / rows_per_trip if c["fma"] == main_fma else 0.0
+        print(f"  s loop {bl[a0]['name']} .. {bl[a1]['name']}: {c['valu']} VALU ({c['fma']} fma), {c['lds']} LDS, "
+              f"{c['salu']} SALU per trip of {rows_per_trip} rows, {trips:.0f} trips in a full block")
+        for k in keys:
+            dyn[k] += c[k] * trips
+        in_inner.update(range(a0, a1 + 1))
+    c = counts([op for k in range(i0, i1 + 1) if k not in in_inner for op in bl[k]["ins"]])
+    print(f"  outside the s loop: {c['valu']} VALU ({c['fma']} fma), {c['lds']} LDS, {c['salu']} SALU per block")
+    for k in keys:
+        dyn[k] += c[k]
+    print(f"  per full 64-row block: {dyn['valu']:.0f} VALU, {dyn['lds']:.0f} LDS, {dyn['salu']:.0f} SALU, "
+          f"{dyn['branch']:.0f} branches;  per row: {dyn['valu'] / 64:.2f} VALU, {dyn['lds'] / 64:.2f} LDS")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", help="existing device assembly listing (default: compile gadfly_hip.hip)")
@@ -109,7 +150,7 @@ def main():
     ap.add_argument("--rows", type=int, default=60)
     ap.add_argument("--rowstore", action="store_true", help="the ROWSTORE = true instance (k_factor7 only)")
     ap.add_argument("--sample", action="store_true", help="the SAMPLE = true instance (the sampling sweeps)")
-    ap.add_argument("--steady", action="store_true", help="the STEADY = true instance (k_factor7 only): also its tail loop")
+    ap.add_argument("--steady", action="store_true", help="the STEADY = true instance (k_factor7 only), and k_steady_tail's block loop")
     ap.add_argument("--all", action="store_true", help="also print blocks outside loops")
     a = ap.parse_args()
     asm = a.asm
@@ -144,13 +185,7 @@ def main():
 
     show(i0, i1, reg)
     if a.steady and not a.all:
-        # the tail loop: the widest range closed by a backward branch behind the row loop
-        idx = {b["name"]: i for i, b in enumerate(bl)}
-        tails = [(idx[t], j) for j, b in enumerate(bl) if j > i1 for t in b["targets"] if i1 < idx.get(t, -1) <= j]
-        if tails:
-            t0, t1 = max(tails, key=lambda r: r[1] - r[0])
-            print(f"tail loop: blocks {bl[t0]['name']} .. {bl[t1]['name']}")
-            show(t0, t1, None)
+        steady_tail(lines, a.rows)
     return 0
 
 
