@@ -1253,9 +1253,10 @@ __device__ __forceinline__ void sweep7_run(double (&T)[ROWS / 2][2], double2 (&u
 // that the rule means the same at every block -- (a ring in the per-problem steady buffer); once both have moved
 // by less than ST_THR -- the gains relative to the largest gain -- at ST_COUNT consecutive anchors it freezes them,
 // leaves the derotated forward-solve state s_k = e^{-i d_k t} (F_2k + i F_2k+1) (this row's update folded), the gains,
-// the pivot and the cadence (over the last 1024 rows) in the buffer and ends.  The rows after belong to k_steady_tail
-// (below), which gf_loglike_steady launches behind this kernel on every tile; on later tiles this kernel returns at
-// once for such a problem.  A row the tail cannot take -- a gap reset, a spacing off the frozen cadence -- raises the
+// the pivot and the cadence (over the last 1024 rows) in the buffer and ends.  The rows after belong to the block
+// filter below: k_steady_tail, which gf_loglike_steady launches behind this kernel on every tile, or k_steady_finish,
+// once per evaluation behind the last tile of gf_steady_sweep; on later tiles this kernel returns at once for such
+// a problem.  A row the tail cannot take -- a gap reset, a spacing off the frozen cadence -- raises the
 // buffer's violation flag: the caller repeats the evaluation without the mode.
 constexpr int ST_SW = 0;            // first tail row (global) ; 0 = full mode
 constexpr int ST_D = 1;             // frozen pivot
@@ -1520,21 +1521,26 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
 // through an LDS staging area of 8 terms so that the loop over the terms is not unrolled around them).
 // One wave per problem, grid B; rows [max(switch row + 1, tile start), tile end) of a problem that has switched.
 // t and y arrive by one coalesced load per block, issued a block ahead; d (= d_inf) and z leave by one coalesced
-// store per block.  A partial last block runs the same code: H is lower triangular, so the rows beyond the tile
-// (y clamped to the last row) touch no row before them; the s loop is bounded and the stores are masked.
+// store per block (k_steady_tail; k_steady_finish, the streamed log-likelihood's instance, stores no row: below).
+// A partial last block runs the same code: H is lower triangular, so the rows beyond the tile (y clamped to the
+// last row) touch no row before them; the s loop is bounded and the stores are masked.
 // Every spacing t_r - t_{r-1} of a tail row r is tested as RowGen tests it (a gap: > gthr; off the frozen cadence:
 // >= jthr): a hit raises ST_VIOL and the rows of that evaluation mean nothing (finite).
 // ------------------------------------------------------------------------------------
 constexpr int STT_STAGE = 8;        // terms per staging pass of the p coefficients
+constexpr int RED_NACC = 3;         // the reductions' accumulators per problem: sum log d, sum z^2/d, min d
 
-template <int ROWS>
-__global__ void __launch_bounds__(64, 2)
-k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double gap,
-              const double *__restrict__ ac_, const double *__restrict__ bc_,
-              const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
-              const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
-              double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
-              double *__restrict__ steady_) {
+// STORE = true: the rows leave as d and z (k_steady_tail, tile by tile); STORE = false: no row is stored, every lane
+// keeps the running sum of z^2 of its row slot over all blocks, and the wave adds the problem's tail to acc
+// (k_steady_finish: rows [switch row, N) of the whole series in one launch).
+template <int ROWS, bool STORE>
+__device__ __forceinline__ void
+steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const double gap,
+                 const double *__restrict__ ac_, const double *__restrict__ bc_,
+                 const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
+                 const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
+                 double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
+                 double *__restrict__ steady_, double *__restrict__ acc_) {
     constexpr int JT = ROWS / 2;                    // term slots (Jc <= JT <= 32; slots from Jc on are zero)
     const int lane = threadIdx.x, pr = blockIdx.x;
     if (info[pr] != 0) return;
@@ -1546,9 +1552,10 @@ k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double
     if (nb >= N) return;
     const double *__restrict__ tg = t_ + (size_t)pr * t_bs + n_first;
     const double *__restrict__ yg = y_ + (size_t)pr * y_bs + n_first;
-    double *__restrict__ dg = d_ + (size_t)pr * N;
-    double *__restrict__ zg = z_ + (size_t)pr * N;
+    double *__restrict__ dg = STORE ? d_ + (size_t)pr * N : nullptr;
+    double *__restrict__ zg = STORE ? z_ + (size_t)pr * N : nullptr;
     const double dinf = hdr[ST_D], delta = hdr[ST_DT];
+    double zsq = 0.0;                               // STORE = false: sum of z^2 over this lane's rows
 
     __shared__ __attribute__((aligned(16))) double s_s[64];         // (s_r, s_i) of term k at [2k], [2k + 1]
     __shared__ __attribute__((aligned(16))) double s_p[128];        // 64 zeros, then p of the block
@@ -1660,7 +1667,11 @@ k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double
         const double zv = z0 + z1;
         s_z[lane] = zv;
         wave_lds_fence();
-        if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
+        if constexpr (STORE) {
+            if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
+        } else {
+            zsq = (lane < lim) ? fma(zv, zv, zsq) : zsq;
+        }
         int j = 0;
 #pragma unroll 4
         for (; j + 1 < lim; j += 2) {
@@ -1679,6 +1690,42 @@ k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double
     }
     if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
     if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
+    if constexpr (!STORE) {
+        // d = d_inf on every tail row: sum log d = rows * log d_inf, sum z^2 / d = (sum z^2) / d_inf
+        const double q = wave_sum(zsq);             // fixed order: the same bits for the same launch shape
+        if (lane == 0) {
+            double *__restrict__ a = acc_ + (size_t)pr * RED_NACC;
+            a[0] += (double)(N - nb) * log(dinf);
+            a[1] += q / dinf;
+            a[2] = fmin(a[2], dinf);
+        }
+    }
+}
+
+template <int ROWS>
+__global__ void __launch_bounds__(64, 2)
+k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double gap,
+              const double *__restrict__ ac_, const double *__restrict__ bc_,
+              const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
+              const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
+              double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
+              double *__restrict__ steady_) {
+    steady_tail_rows<ROWS, true>(N, n_first, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, d_, z_, info,
+                                 steady_, nullptr);
+}
+
+// The finishing instance: the rows [switch row, N) of the WHOLE series (N rows from global row 0) of every switched
+// problem in one launch behind the last tile's reduction -- one set-up per evaluation, blocks from the switch row on
+// across the tiles' boundaries, no row stored; acc[b] = {sum log d, sum z^2 / d, min d} takes the tail's share.
+template <int ROWS>
+__global__ void __launch_bounds__(64, 2)
+k_steady_finish(const int64_t N, const int Jc, const double gap,
+                const double *__restrict__ ac_, const double *__restrict__ bc_,
+                const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
+                const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
+                const int32_t *__restrict__ info, double *__restrict__ steady_, double *__restrict__ acc_) {
+    steady_tail_rows<ROWS, false>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr, info,
+                                  steady_, acc_);
 }
 
 #define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -4181,15 +4228,27 @@ __host__ __device__ inline int red_groups(int64_t N) {
     return (int)g;
 }
 
-constexpr int RED_NACC = 3;         // sum log d, sum z^2/d, min d
+// Rows of a tile (first global row n_first) that the steady mode's sweep instance stored for problem b: those in
+// front of the problem's switch row, all N of a problem that has not switched (the bounded reductions).
+__device__ inline int64_t steady_rows_stored(const double *steady, int b, int64_t N, int64_t n_first) {
+    const double swd = steady[(size_t)b * ST_SIZE + ST_SW];
+    if (!(swd > 0.0)) return N;
+    const int64_t r = (int64_t)swd - n_first;
+    return r < 0 ? 0 : (r < N ? r : N);
+}
 
+// BOUNDED: the rows [0, steady_rows_stored) only, in the order the plain instance takes them; a group with no such row
+// ends at once and leaves its slot of `work` alone (k_reduce2<true> does not read it)
+template <bool BOUNDED>
 __global__ void __launch_bounds__(RED_BLOCK) k_reduce1(int64_t N, const double *d, const double *z,
-                                                       double *work) {
+                                                       double *work, const double *steady, int64_t n_first) {
     const int b = blockIdx.y, g = blockIdx.x, G = gridDim.x;
     const double *dp = d + (size_t)b * N;
     const double *zp = z ? z + (size_t)b * N : nullptr;
+    const int64_t lim = BOUNDED ? steady_rows_stored(steady, b, N, n_first) : N;
+    if (BOUNDED && (int64_t)g * RED_BLOCK >= lim) return;
     double s1 = 0.0, s2 = 0.0, mn = INFINITY;
-    for (int64_t n = (int64_t)g * RED_BLOCK + threadIdx.x; n < N; n += (int64_t)G * RED_BLOCK) {
+    for (int64_t n = (int64_t)g * RED_BLOCK + threadIdx.x; n < lim; n += (int64_t)G * RED_BLOCK) {
         const double dn = dp[n];
         s1 += log(dn);
         mn = fmin(mn, dn);
@@ -4210,11 +4269,21 @@ __global__ void __launch_bounds__(RED_BLOCK) k_reduce1(int64_t N, const double *
 }
 
 // acc[b] = {sum log d, sum z^2/d, min d}; init != 0 overwrites, else accumulates (tile streaming,
-// fixed order)
-__global__ void __launch_bounds__(64) k_reduce2(int G, const double *work, double *acc, int init) {
+// fixed order).  BOUNDED: the groups that k_reduce1<true> filled (a problem that has not switched: all of them, in the
+// same order)
+template <bool BOUNDED>
+__global__ void __launch_bounds__(64) k_reduce2(int G, const double *work, double *acc, int init,
+                                                const double *steady, int64_t N, int64_t n_first) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    int Gn = G;                                     // groups with rows
+    if constexpr (BOUNDED) {
+        const int64_t lim = steady_rows_stored(steady, b, N, n_first);
+        if (lim == 0 && !init) return;
+        const int64_t gl = (lim + RED_BLOCK - 1) / RED_BLOCK;
+        Gn = gl < G ? (int)gl : G;
+    }
     double s1 = 0.0, s2 = 0.0, mn = INFINITY;
-    for (int g = lane; g < G; g += 64) {
+    for (int g = lane; g < Gn; g += 64) {
         const double *w = work + ((size_t)b * G + g) * RED_NACC;
         s1 += w[0];
         s2 += w[1];
@@ -5694,7 +5763,7 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
                         double *d, double *z, double *r_out, double *Ut_out, double *Wt_out,
                         double *de_out, double *S_state, double *F_state,
                         int32_t *info, void *stream, bool sample = false,
-                        double *steady = nullptr, int64_t arm_from = 0) {
+                        double *steady = nullptr, int64_t arm_from = 0, bool tail = true) {
     const int W = Jr + 2 * Jc;
     if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
     // the sampling sweeps (y = eps, z = the draw by global row with y's batch stride): streamed tiles only
@@ -5756,7 +5825,7 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
         GF_F3_CASE(52) GF_F3_CASE(56) GF_F3_CASE(60) GF_F3_CASE(64)
         default: return set_err("%s: internal dispatch error", who);
     }
-    if (steady) {                       // the rows of this tile behind each problem's switch row (same stream)
+    if (steady && tail) {               // the rows of this tile behind each problem's switch row (same stream)
         if (const int e = check_launch(who)) return e;
         switch (rows) {
             GF_ST_CASE(4) GF_ST_CASE(8) GF_ST_CASE(12) GF_ST_CASE(16) GF_ST_CASE(20) GF_ST_CASE(24)
@@ -5797,6 +5866,46 @@ int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int blo
     return fused_launch("gf_loglike_steady", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
                         diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
                         nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from);
+}
+
+int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                    int gen_period, int variant,
+                    const double *ar, const double *cr, const double *ac,
+                    const double *bc, const double *cc, const double *dc,
+                    const double *diag_add, const double *cmax,
+                    const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                    const double *y, int64_t y_bs,
+                    double *d, double *z, double *S_state, double *F_state,
+                    int32_t *info, double *steady, int64_t arm_from, void *stream) {
+    if (!steady) return set_err("gf_steady_sweep: null pointer%s", "");
+    return fused_launch("gf_steady_sweep", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
+                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false);
+}
+
+#define GF_SF_CASE(R) case R: hipLaunchKernelGGL((k_steady_finish<R>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc); break;
+
+int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                     const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                     const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                     const int32_t *info, double *steady, double *acc, void *stream) {
+    if (B < 1 || N < 1) return set_err("gf_steady_finish: empty problem (B=%s%lld, N=%lld)", "", B, N);
+    if (Jr != 0 || Jc < 1 || Jc > 31)
+        return set_err("gf_steady_finish: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%s%lld, Jc=%lld)", "", Jr, Jc);
+    if (block < 1 || block > 64 || (block & (block - 1)))
+        return set_err("gf_steady_finish: block=%s%lld must be a power of two in 1..64", "", block);
+    if (!ac || !bc || !cc || !dc || !cmax || !t || !y || !info || !steady || !acc)
+        return set_err("gf_steady_finish: null pointer%s", "");
+    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
+    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
+    hipStream_t st = (hipStream_t)stream;
+    switch ((2 * Jc + 3) / 4 * 4) {
+        GF_SF_CASE(4) GF_SF_CASE(8) GF_SF_CASE(12) GF_SF_CASE(16) GF_SF_CASE(20) GF_SF_CASE(24)
+        GF_SF_CASE(28) GF_SF_CASE(32) GF_SF_CASE(36) GF_SF_CASE(40) GF_SF_CASE(44) GF_SF_CASE(48)
+        GF_SF_CASE(52) GF_SF_CASE(56) GF_SF_CASE(60) GF_SF_CASE(64)
+        default: return set_err("gf_steady_finish: internal dispatch error%s", "");
+    }
+    return check_launch("gf_steady_finish");
 }
 
 int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
@@ -6126,9 +6235,22 @@ int gf_reduce_tile(int B, int64_t N, const double *d, const double *z,
     if (B < 1 || N < 1) return set_err("gf_reduce_tile: empty problem (B=%s%lld, N=%lld)", "", B, N);
     if (!d || !work || !acc) return set_err("gf_reduce_tile: null pointer%s", "");
     const int G = red_groups(N);
-    hipLaunchKernelGGL(k_reduce1, dim3(G, B), dim3(RED_BLOCK), 0, (hipStream_t)stream, N, d, z, work);
-    hipLaunchKernelGGL(k_reduce2, dim3(B), dim3(64), 0, (hipStream_t)stream, G, work, acc, init);
+    hipLaunchKernelGGL(k_reduce1<false>, dim3(G, B), dim3(RED_BLOCK), 0, (hipStream_t)stream, N, d, z, work,
+                       (const double *)nullptr, (int64_t)0);
+    hipLaunchKernelGGL(k_reduce2<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, G, work, acc, init,
+                       (const double *)nullptr, N, (int64_t)0);
     return check_launch("gf_reduce_tile");
+}
+
+int gf_reduce_tile_steady(int B, int64_t N, int64_t n_first, const double *d, const double *z,
+                          const double *steady, double *work, double *acc, int init, void *stream) {
+    if (B < 1 || N < 1 || n_first < 0)
+        return set_err("gf_reduce_tile_steady: empty problem or negative n_first (N=%s%lld, n_first=%lld)", "", N, n_first);
+    if (!d || !steady || !work || !acc) return set_err("gf_reduce_tile_steady: null pointer%s", "");
+    const int G = red_groups(N);
+    hipLaunchKernelGGL(k_reduce1<true>, dim3(G, B), dim3(RED_BLOCK), 0, (hipStream_t)stream, N, d, z, work, steady, n_first);
+    hipLaunchKernelGGL(k_reduce2<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, G, work, acc, init, steady, N, n_first);
+    return check_launch("gf_reduce_tile_steady");
 }
 
 int gf_loglike_finish(int B, int64_t N, const double *acc, const int32_t *info,

@@ -879,6 +879,7 @@ class StreamingBatch:
         self._steady_from = 0               # first row whose tile runs the steady instance
         self._steady_skip = 0               # evaluations left on the plain sweep after one in which nothing armed
         self._steady_feedback = None        # (pinned host scalar, event): earliest switch row of the last steady one
+        self.finish_events = []             # time_factor: (start, end) of each gf_steady_finish launch (not in factor_events)
         T = int(min(max(int(tile_rows), 1), self.N))
         if T < self.N:
             T = max(64, T // 64 * 64)         # tiles start on a reset row (any block <= 64)
@@ -1207,19 +1208,39 @@ class StreamingBatch:
                     p(self.diag), 0 if self.diag is None else self._bs(self.diag),
                     p(self.y), self._bs(self.y), p(self.d), p(self.z),
                     p(self.S_state), p(self.F_state), p(self.info))
-            if self.steady_used and n0 + rows > start:      # (both instances hand over the same state)
-                st = lib.gf_loglike_steady(*args, p(self._steady), arm_from, main.cuda_stream)
-                _lib.check(st, "gf_loglike_steady")
+            steady_tile = self.steady_used and n0 + rows > start    # (both instances hand over the same state)
+            if steady_tile:
+                st = lib.gf_steady_sweep(*args, p(self._steady), arm_from, main.cuda_stream)
+                _lib.check(st, "gf_steady_sweep")
             else:
                 st = lib.gf_loglike_fused(*args, main.cuda_stream)
                 _lib.check(st, "gf_loglike_fused")
             if self.time_factor:
                 e1.record(main)
                 self.factor_events.append((e0, e1, rows))
-            st = lib.gf_reduce_tile(B, rows, p(self.d), p(self.z), p(self.work), p(self.acc),
-                                    1 if k == 0 else 0, main.cuda_stream)
-            _lib.check(st, "gf_reduce_tile")
-        if self.steady_used:                # earliest switch row (0: nothing armed) for the next plan: no sync here
+            if steady_tile:                 # the rows in front of each problem's switch row: the others were not stored
+                st = lib.gf_reduce_tile_steady(B, rows, n0, p(self.d), p(self.z), p(self._steady), p(self.work),
+                                               p(self.acc), 1 if k == 0 else 0, main.cuda_stream)
+                _lib.check(st, "gf_reduce_tile_steady")
+            else:
+                st = lib.gf_reduce_tile(B, rows, p(self.d), p(self.z), p(self.work), p(self.acc),
+                                        1 if k == 0 else 0, main.cuda_stream)
+                _lib.check(st, "gf_reduce_tile")
+        if self.steady_used:
+            # every switched problem's rows from its switch row to the end of the series, in one launch: no row is
+            # stored, acc takes their sums (its own event pair: factor_events stays one entry per tile)
+            if self.time_factor:
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record(main)
+            st = lib.gf_steady_finish(B, N, self.Jr, self.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]),
+                                      p(comp[3]), p(cmax), p(self.t), self._bs(self.t), p(self.y), self._bs(self.y),
+                                      p(self.info), p(self._steady), p(self.acc), main.cuda_stream)
+            _lib.check(st, "gf_steady_finish")
+            if self.time_factor:
+                e1.record(main)
+                self.finish_events.append((e0, e1))
+            # earliest switch row (0: nothing armed) for the next plan: no sync here
             sw = self._steady[:, 0]
             first = torch.where(sw > 0.0, sw, torch.full_like(sw, float("inf"))).min()
             host = torch.zeros((1,), dtype=torch.float64, pin_memory=True)

@@ -216,6 +216,44 @@ int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int blo
                       int32_t *info, double *steady, int64_t arm_from, void *stream);
 
 /*
+ * The steady mode without stored tail rows: the route of a streamed log-likelihood.  Per tile
+ *   gf_steady_sweep       : gf_loglike_steady's sweep instance alone -- arguments, `steady` and its slots [0], [1],
+ *                           [2] as there.  A problem's rows of the tile in front of its switch row are stored in d
+ *                           and z; the rows behind it are NOT computed (d, z keep whatever they held);
+ *   gf_reduce_tile_steady : gf_reduce_tile over the rows that gf_steady_sweep stored -- per problem the rows of the
+ *                           tile (N rows from global row n_first) in front of its switch row, all of them for a
+ *                           problem that has not switched (then the same tree in the same order: the same bits as
+ *                           gf_reduce_tile).  No other row of d, z is read.  work, acc, init as for gf_reduce_tile;
+ * and once per evaluation, behind the last tile's reduction on the same stream,
+ *   gf_steady_finish      : the rows [switch row, N) of the WHOLE series (N rows; t, y from global row 0) of every
+ *                           problem that has switched, in one launch of one wave per problem: the block filter of
+ *                           gf_loglike_steady's second kernel with one set-up, blocks of 64 rows from the switch
+ *                           row on, no row stored.  With d = steady[b][1] on all of them,
+ *                               acc[b][0] += (N - switch row) log d,  acc[b][1] += (sum z^2) / d,
+ *                               acc[b][2]  = min(acc[b][2], d)
+ *                           (sums in a fixed order: deterministic for given B, N and switch rows).  Every spacing is
+ *                           tested as gf_loglike_steady tests it (steady[b][2]).  Problems with info != 0 or
+ *                           without a switch are left alone.  block, variant: the sweep's (they set its gap test);
+ *                           ac .. dc, cmax, t, y and their batch strides: the sweep's.
+ * Then gf_loglike_finish.  The values agree with gf_loglike_steady + gf_reduce_tile to the rounding of the sums.
+ */
+int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                    int gen_period, int variant,
+                    const double *ar, const double *cr, const double *ac,
+                    const double *bc, const double *cc, const double *dc,
+                    const double *diag_add, const double *cmax,
+                    const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                    const double *y, int64_t y_bs,
+                    double *d, double *z, double *S_state, double *F_state,
+                    int32_t *info, double *steady, int64_t arm_from, void *stream);
+int gf_reduce_tile_steady(int B, int64_t N, int64_t n_first, const double *d, const double *z,
+                          const double *steady, double *work, double *acc, int init, void *stream);
+int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                     const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                     const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                     const int32_t *info, double *steady, double *acc, void *stream);
+
+/*
  * Fused sampling sweep: B draws y = L D^1/2 eps of B different kernels, K = L D L^T, in the sweep that factors
  * -- no factor is stored (24 B read, 16 B written per row: t, diag, eps; d, out).  Replaces celerite2's
  * driver.matmul_lower with V := W after driver.factor (the reference's GaussianProcess.sample, gp.py:391) for

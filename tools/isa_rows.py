@@ -5,7 +5,8 @@
     python tools/isa_rows.py --kernel k_factor7 --rows 40 --rowstore
     python tools/isa_rows.py --kernel k_factorw --rows 44 --sample   # the sampling instance (gf_sample_fused)
     python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: its full row loop, AND
-                                                   # k_steady_tail<60>: its block loop, per 64-row block and per row
+                                                   # k_steady_tail<60>, k_steady_finish<60>: the block loop, per 64-row
+                                                   # block and per row
 
 Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
 most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
@@ -103,15 +104,15 @@ def counts(ins):
     return c
 
 
-def steady_tail(lines, rows):
-    """k_steady_tail<rows>: the block loop (the smallest loop around the block with the most FMAs: p and H p) and
+def steady_tail(lines, rows, kernel="k_steady_tail"):
+    """k_steady_tail<rows> / k_steady_finish<rows>: the block loop (the smallest loop around the block with the most FMAs: p and H p) and
     the loops inside it (the s update, two rows per step, unrolled).  Instructions per 64-row block = the block loop's
     own instructions + each inner loop's body times its trips for 64 rows."""
-    bl = blocks(kernel_body(lines, "k_steady_tail", rows, None))
-    tag = kernel_tag("k_steady_tail", rows, None, False)
+    bl = blocks(kernel_body(lines, kernel, rows, None))
+    tag = kernel_tag(kernel, rows, None, False)
     vgpr = next((ln.split(",")[-1].strip() for ln in lines if ".num_vgpr," in ln and tag.search(ln)), "?")
     total = counts([op for b in bl for op in b["ins"]])
-    print(f"k_steady_tail<{rows}>: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, "
+    print(f"{kernel}<{rows}>: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, "
           f"{total['scratch']} scratch (spill) in all; {vgpr} VGPRs")
     reg = max(range(len(bl)), key=lambda i: counts(bl[i]["ins"])["fma"])
     i0, i1 = row_loop(bl, reg)
@@ -150,7 +151,7 @@ def main():
     ap.add_argument("--rows", type=int, default=60)
     ap.add_argument("--rowstore", action="store_true", help="the ROWSTORE = true instance (k_factor7 only)")
     ap.add_argument("--sample", action="store_true", help="the SAMPLE = true instance (the sampling sweeps)")
-    ap.add_argument("--steady", action="store_true", help="the STEADY = true instance (k_factor7 only), and k_steady_tail's block loop")
+    ap.add_argument("--steady", action="store_true", help="the STEADY = true instance (k_factor7 only), and the block loops of k_steady_tail / k_steady_finish")
     ap.add_argument("--all", action="store_true", help="also print blocks outside loops")
     a = ap.parse_args()
     asm = a.asm
@@ -186,6 +187,7 @@ def main():
     show(i0, i1, reg)
     if a.steady and not a.all:
         steady_tail(lines, a.rows)
+        steady_tail(lines, a.rows, "k_steady_finish")
     return 0
 
 
