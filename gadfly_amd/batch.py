@@ -441,7 +441,104 @@ class BatchedLogLikelihood:
             alpha = [alpha[b, :int(n)] for b, n in enumerate(self.rows)]
         return (mu, alpha) if return_alpha else mu
 
-    def predict_device(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None):
+    def _variance_call(self, pack_or_kernels, ts=None, nq=None, **want):
+        """One ``gf_var_batch`` call over the batch (:func:`gadfly_amd.predict.variance_batch`), the ``last_predict_*``
+        attributes filled as :meth:`predict_device` fills them."""
+        from .predict import check_width, variance_batch
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
+        res = variance_batch(eng, Jr, Jc, real, comp, diag_add, ts=ts, nobs=self.rows, nq=nq,
+                             cap_bytes=self.predict_workspace_bytes, **want)
+        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self._predict_events, self._predict_at_events = res["events"], []
+        self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
+        self.last_predict_info = res["info"]
+        return (Jr, Jc, real, comp), res
+
+    def _cut_rows(self, x):
+        """(B, N) -> the list of each series' real rows for a ragged batch."""
+        if x is None or self.rows is None:
+            return x
+        return [x[b, :int(n)] for b, n in enumerate(self.rows)]
+
+    def _predict_var(self, pack_or_kernels, kernel, include_mean, return_alpha, t):
+        """:meth:`predict_device` with ``return_var=True``."""
+        if kernel is not None:
+            raise NotImplementedError(
+                "return_var with kernel=component is not supported: the component's conditional variance "
+                "K'(0) - K' Sigma^-1 K'^T does not reduce to the inverse diagonal of Sigma")
+        eng = self.engine
+        torch = eng.torch
+        if t is None:
+            _, res = self._variance_call(pack_or_kernels, want_alpha=return_alpha, want_mu=True, want_h=False,
+                                         want_var=True)
+            mu = res["mu"]
+            if include_mean and np.any(self._mean != 0.0):
+                m = self._mean[:, None] if self.rows is not None else self._mean
+                m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
+                mu += torch.as_tensor(m, dtype=torch.float64, device=eng.device)
+            mu, var, alpha = self._cut_rows(mu), self._cut_rows(res["var"]), self._cut_rows(res["alpha"])
+            return (mu, var, alpha) if return_alpha else (mu, var)
+        from .predict import predict_at
+        ts, nq, as_list = self._query_times(t)
+        mean = self._mean_per_problem() if include_mean and np.any(self._mean != 0.0) else None
+        M = ts.shape[1]
+        cf, res = self._variance_call(pack_or_kernels, ts=ts if M else None, nq=nq if M else None, want_alpha=True,
+                                      want_mu=False, want_h=False, want_var=False)
+        if M == 0:
+            mu = torch.empty((self.B, 0), dtype=torch.float64, device=eng.device)
+            var = torch.empty((self.B, 0), dtype=torch.float64, device=eng.device)
+        else:
+            at = predict_at(eng, *cf, res["alpha"], ts, nobs=self.rows, nq=nq)
+            self._predict_at_events = at["events"]
+            mu, var = at["mu"], res["var_at"]
+            if mean is not None:
+                mu += torch.as_tensor(np.array(mean), dtype=torch.float64, device=eng.device)
+        if as_list:
+            mu = [mu[b, :int(n)] for b, n in enumerate(nq)]
+            var = [var[b, :int(n)] for b, n in enumerate(nq)]
+        alpha = self._cut_rows(res["alpha"])
+        return (mu, var, alpha) if return_alpha else (mu, var)
+
+    def inverse_diagonal_device(self, pack_or_kernels=None):
+        """h_n = (Sigma^-1)_nn of the B problems, Sigma = K + diag, as a float64 device tensor (B, N)
+        (a list of B tensors for a ragged batch): the quantity the conditional variances and the leave-one-out
+        residuals are made of, with no cancellation in it.  ``pack_or_kernels`` as :meth:`predict_device`; NaN rows
+        where the matrix is not positive definite.  No host synchronisation."""
+        _, res = self._variance_call(pack_or_kernels, want_alpha=False, want_mu=False, want_h=True, want_var=False)
+        return self._cut_rows(res["hdiag"])
+
+    def leave_one_out_device(self, pack_or_kernels=None, include_mean=True):
+        """``(mean, var)`` of every observation given all the others of its series, E[y_n | y_-n] = y_n - alpha_n / h_n
+        and Var[y_n | y_-n] = 1 / h_n (the observation's own noise included), from one device call: float64 device
+        tensors (B, N), lists for a ragged batch.  (y_n - mean_n)^2 / var_n flags outliers.  No host synchronisation."""
+        _, res = self._variance_call(pack_or_kernels, want_alpha=True, want_mu=False, want_h=True, want_var=False)
+        eng = self.engine
+        torch = eng.torch
+        var = 1.0 / res["hdiag"]
+        mean = eng.y.reshape(-1, eng.N) - res["alpha"] * var
+        if include_mean and np.any(self._mean != 0.0):
+            m = self._mean[:, None] if self.rows is not None else self._mean
+            m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
+            mean += torch.as_tensor(m, dtype=torch.float64, device=eng.device)
+        return self._cut_rows(mean), self._cut_rows(var)
+
+    @staticmethod
+    def _to_host(x):
+        return [v.cpu().numpy() for v in x] if isinstance(x, list) else x.cpu().numpy()
+
+    def inverse_diagonal(self, pack_or_kernels=None):
+        """:meth:`inverse_diagonal_device`, returned as numpy."""
+        return self._to_host(self.inverse_diagonal_device(pack_or_kernels))
+
+    def leave_one_out(self, pack_or_kernels=None, include_mean=True):
+        """:meth:`leave_one_out_device`, returned as numpy."""
+        return tuple(self._to_host(x) for x in self.leave_one_out_device(pack_or_kernels, include_mean=include_mean))
+
+    def predict_device(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None,
+                       return_var=False):
         """Conditional means of the B problems at their observed times in one device call: what
         ``GaussianProcess(kernel_b, t, yerr).predict(y)`` gives one kernel at a time -- mu = y - diag alpha with
         alpha = K^-1 (y - mean) -- as a float64 device tensor (B, N); a ragged batch returns a list of B tensors cut
@@ -464,7 +561,16 @@ class BatchedLogLikelihood:
         K(t*, t) alpha with the kernel's coefficients at every lag (no diagonal; an exposure-integrated kernel stays
         in coefficient form), or K'(t*, t) alpha with ``kernel=component``.  The mean added is a scalar or one value
         per problem: a mean that varies along the rows raises ``ValueError`` unless ``include_mean=False``.  An
-        empty ``t`` gives an empty result (alpha is still solved for; the second launch is left out)."""
+        empty ``t`` gives an empty result (alpha is still solved for; the second launch is left out).
+
+        ``return_var``: also the conditional variances (``predict(y, t, return_var=True)``), ``(mu,
+        var)`` or ``(mu, var, alpha)`` -- at the observed times diag_n - diag_n^2 h_n, the variance of the noise-free
+        process (exactly 0 where diag_n = 0), at new times K(0) - K(t*, t) Sigma^-1 K(t, t*) with the kernel in its
+        coefficient form at every lag (an exposure-integrated kernel is exact for queries at least its exposure time
+        from every stamp).  One ``gf_var_batch`` launch takes the place of ``gf_solve_batch``: the means keep their
+        bits.  With ``kernel=component`` it raises ``NotImplementedError``."""
+        if return_var:
+            return self._predict_var(pack_or_kernels, kernel, include_mean, return_alpha, t)
         if t is not None:
             return self._predict_at(pack_or_kernels, kernel, include_mean, return_alpha, t)
         from .predict import check_width, component_pack, solve_batch
@@ -511,15 +617,16 @@ class BatchedLogLikelihood:
             e1.synchronize()
         return sum(a.elapsed_time(b) for a, b in events)
 
-    def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None):
+    def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None,
+                return_var=False):
         """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch or a list of query times)."""
         out = self.predict_device(pack_or_kernels, kernel=kernel, include_mean=include_mean,
-                                  return_alpha=return_alpha, t=t)
+                                  return_alpha=return_alpha, t=t, return_var=return_var)
 
         def host(x):
             return [v.cpu().numpy() for v in x] if isinstance(x, list) else x.cpu().numpy()
 
-        return tuple(host(x) for x in out) if return_alpha else host(out)
+        return tuple(host(x) for x in out) if (return_alpha or return_var) else host(out)
 
     def evaluate_device(self, pack=None):
         """Enqueue one evaluation per problem; returns the (B,) device tensor (no host sync).
@@ -663,13 +770,15 @@ def log_likelihood_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, device=N
                                 device=device).evaluate()
 
 
-def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, device=None, t_pred=None):
+def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, device=None, t_pred=None,
+                  return_var=False):
     """One-shot form of :meth:`BatchedLogLikelihood.predict`: the conditional means of B problems at their observed
     times as numpy, (B, N) or a list of B arrays for ragged ``t``; ``kernel=`` selects the share of one part of the
     kernel (a list of B components, or one for all).  ``t_pred``: new times to predict at instead, what
-    :meth:`BatchedLogLikelihood.predict` takes as ``t=`` (here ``t`` names the observed stamps)."""
+    :meth:`BatchedLogLikelihood.predict` takes as ``t=`` (here ``t`` names the observed stamps).  ``return_var``: also
+    the conditional variances, ``(mu, var)``."""
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
-                                device=device).predict(kernel=kernel, t=t_pred)
+                                device=device).predict(kernel=kernel, t=t_pred, return_var=return_var)
 
 
 def _is_series_list(x):

@@ -6,7 +6,9 @@ the kernel explains for B problems at once (``gf_solve_batch``: a checkpointed f
 backwards, no stored factor); this module sizes its workspace, splits a batch into groups under a byte cap (a
 problem's result does not depend on the group it lands in) and stacks the component's coefficients.
 ``gf_predict_batch_at`` then carries alpha to new times t* (DESIGN.md 3.11): the two sorted-axis sums of the full
-kernel or of a component, no workspace.
+kernel or of a component, no workspace.  ``gf_var_batch`` is ``gf_solve_batch`` with one more backward
+recurrence: the inverse diagonal h, the conditional variances at the observed times and at new ones, grouped the same
+way under the same cap with the staged queries counted.
 """
 import numpy as np
 import torch
@@ -14,7 +16,8 @@ import torch
 from . import _lib
 from .grad import check_pack_batch
 
-__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "predict_at", "DEFAULT_WORKSPACE_BYTES"]
+__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "predict_at", "variance_plan",
+           "variance_batch", "DEFAULT_WORKSPACE_BYTES"]
 
 #: default cap on the workspace of one call (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = _lib.GF_SOLVE_WORKSPACE_BYTES
@@ -178,3 +181,94 @@ def predict_at(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):
         _lib.check(st, "gf_predict_batch_at")
         e1.record()
     return dict(mu=mu, events=[(e0, e1)])
+
+
+def variance_plan(N, W, B, M=0, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0):
+    """(doubles per problem, problems per group, number of groups) of a gf_var_batch call with M queries per problem:
+    the solve's workspace, one slot for Y and 64 doubles per staged query (at M = N the queries dominate and the groups
+    shrink)."""
+    check_width(W)
+    per = int(_lib.load().gf_var_batch_work(int(N), int(W), int(M), int(seg)))
+    if per <= 0:
+        raise ValueError(f"no variance workspace for N = {N}, W = {W}, M = {M}, seg = {seg}")
+    group = int(max(1, min(B, int(cap_bytes) // (8 * per))))
+    return per, group, (B + group - 1) // group
+
+
+def variance_batch(engine, Jr, Jc, real, comp, diag_add, ts=None, nobs=None, nq=None,
+                   cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0, want_alpha=True, want_mu=True, want_h=True,
+                   want_var=True):
+    """Enqueue ``gf_var_batch`` over an engine's data for stacked host coefficient arrays of its ORIGINAL term
+    structure (as :func:`solve_batch`, no component).  ``ts``: query stamps (M,), (1, M) or (B, M), ascending per
+    problem (host array or device tensor), or None; ``nobs`` / ``nq``: (B,) real observed rows and real queries per
+    problem, or None for N / M.  Returns a dict of device tensors -- ``alpha``, ``mu``, ``hdiag``, ``var`` ((B, N)
+    each, None where not asked for), ``var_at`` ((B, M), None without queries; rows from ``nq[b]`` on are never
+    written), ``ll``, ``info`` (B,) -- with the plan and ``events`` as :func:`solve_batch`.  No host synchronisation."""
+    W = Jr + 2 * Jc
+    if (Jr, Jc) != engine._struct0:
+        raise ValueError("coefficient pack does not match the batch structure")
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, diag_add)
+    lib, p = engine.lib, _lib.ptr
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        M = 0
+        if ts is not None:
+            ts = torch.as_tensor(ts, dtype=torch.float64).to(dev)
+            if ts.ndim == 1:
+                ts = ts[None, :]
+            if ts.ndim != 2 or ts.shape[0] not in (1, B):
+                raise ValueError(f"query times of shape {tuple(ts.shape)} for a batch of {B} problems")
+            ts = ts.contiguous()
+            M = int(ts.shape[1])
+            if M == 0:
+                ts = None
+        counts = []
+        for cnt, full in ((nobs, N), (nq, M)):
+            if cnt is not None:
+                cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+                if cnt.shape != (B,) or np.any(cnt < 0) or np.any(cnt > full):
+                    raise ValueError("dimension mismatch")
+                cnt = torch.as_tensor(cnt, **i64)
+            counts.append(cnt)
+        per, group, ngroups = variance_plan(N, W, B, M, cap_bytes, seg)
+        work = torch.empty((group * per,), **f64)
+        ll = torch.empty((B,), **f64)
+        info = torch.zeros((B,), dtype=torch.int32, device=dev)
+        outs = {k: (torch.empty((B, N), **f64) if want else None) for k, want in
+                (("alpha", want_alpha), ("mu", want_mu), ("hdiag", want_h), ("var", want_var))}
+        var_at = torch.empty((B, M), **f64) if M else None
+        real = np.ascontiguousarray(real, dtype=np.float64)
+        comp = np.ascontiguousarray(comp, dtype=np.float64)
+        diag_add = np.ascontiguousarray(diag_add, dtype=np.float64)
+        t, y, dg = engine.t, engine.y, engine.diag
+        tbs, ybs = engine._bs(t), engine._bs(y)
+        dbs = 0 if dg is None else engine._bs(dg)
+        qbs = 0 if ts is None else engine._bs(ts)
+        at = lambda x, off: None if x is None else x.data_ptr() + off      # noqa: E731
+        events = []
+        for b0 in range(0, B, group):
+            nb = min(group, B - b0)
+            cr_ = torch.as_tensor(np.ascontiguousarray(real[:, b0:b0 + nb]), **f64)
+            cc_ = torch.as_tensor(np.ascontiguousarray(comp[:, b0:b0 + nb]), **f64)
+            da = torch.as_tensor(diag_add[b0:b0 + nb], **f64)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            st = lib.gf_var_batch(
+                nb, N, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]), p(da),
+                t.data_ptr() + 8 * b0 * tbs, tbs,
+                None if dg is None else dg.data_ptr() + 8 * b0 * dbs, dbs,
+                y.data_ptr() + 8 * b0 * ybs, ybs,
+                at(ts, 8 * b0 * qbs), qbs, M, at(counts[0], 8 * b0), at(counts[1], 8 * b0),
+                int(seg), p(work), per,
+                at(outs["alpha"], 8 * b0 * N), at(outs["mu"], 8 * b0 * N), at(outs["hdiag"], 8 * b0 * N),
+                at(outs["var"], 8 * b0 * N), at(var_at, 8 * b0 * M),
+                ll.data_ptr() + 8 * b0, info.data_ptr() + 4 * b0, stream)
+            _lib.check(st, "gf_var_batch")
+            e1.record()
+            events.append((e0, e1))
+        return dict(ll=ll, info=info, var_at=var_at, workspace_bytes=8 * per * group, groups=ngroups,
+                    group_size=group, events=events, **outs)

@@ -19,6 +19,9 @@
  *                                                      (no gadfly call site: gradients for samplers)
  *   gf_solve_batch      driver.factor + solve_lower + solve_upper + general_matmul_lower / _upper at t* = t
  *                                                      <- gp.py:370, :232 for B kernels at once
+ *   gf_var_batch        the same plus the diagonal of K* - K*^T (K + diag)^-1 K* (celerite2's
+ *                       ConditionalDistribution.variance)   <- gp.py:241-306 (predict(..., return_var=True)) for B
+ *                                                      kernels at once
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HIP) unless marked "host"; float64 throughout;
@@ -719,6 +722,42 @@ int gf_predict_batch_at(int B, int64_t N, int64_t M, int Jr, int Jc,
                         const double *ts, int64_t ts_bs, const int64_t *nq,
                         const double *alpha, int64_t alpha_bs,
                         double *mu, int64_t mu_bs, void *stream);
+
+/*
+ * Conditional variances of B problems: the second half of celerite2's
+ * GaussianProcess.predict(y, t, return_var=True) -- the diagonal of K* - K*^T Sigma^-1 K*, one right-hand side per query
+ * through the stored factor there -- for B kernels at once and with no stored factor: gf_solve_batch's two passes with
+ * one more, matrix-valued, backward recurrence Y over the rows they stage, O((N + M) W^2) per problem.  One wave per
+ * problem; W = Jr + 2 Jc <= 63 (-3 beyond).
+ *   coefficients, diag_add, t, diag, y, their strides and seg as gf_solve_batch (A_n = diag[n] + diag_add: diag is
+ *     the observational noise, diag_add the kernel's value at lag 0; diag may be NULL), no component
+ *   ts [M], ts_bs, nobs, nq [B] as gf_predict_batch_at: ascending query stamps, the real observed rows (the rows from
+ *     nobs[b] on are missing-data rows at the end: they own no query) and the real queries of problem b (either count
+ *     may be NULL: N, M).  M = 0: no queries, ts and var_at NULL
+ *   work: work_bs >= gf_var_batch_work(N, W, M, seg) doubles per problem (gf_solve_batch's workspace, one slot of
+ *     64 max(16, 32, 64 >= W) doubles for Y, 64 per query); B * work_bs in all
+ *   alpha, mu [B][N]  as gf_solve_batch, with its bits                           (each may be NULL)
+ *   hdiag [B][N]      h_n = (Sigma^-1)_nn, Sigma = K + diag: the leave-one-out variance is 1 / h_n and the
+ *                     leave-one-out mean y_n - alpha_n / h_n                     (may be NULL)
+ *   var [B][N]        diag_n - diag_n^2 h_n = K(0) - K_n Sigma^-1 K_n^T: the conditional variance of the noise-free
+ *                     process at t_n, exactly 0 where diag_n = 0 (and with diag = NULL)   (may be NULL)
+ *   var_at [B][M]     K(0) - K(t*, t) Sigma^-1 K(t, t*) at the queries, K(0) = diag_add and the kernel in its
+ *                     coefficient form at every lag; a query that coincides with an observed stamp belongs to the
+ *                     interval after it.  Rows from nq[b] on are never written.  Required iff M > 0 (-1 otherwise)
+ *   ll, info [B]      as gf_solve_batch; a problem whose pivot fails gets NaN in every row of every output
+ * No atomics: results are bit-identical from run to run, for every seg, and do not depend on the other problems of
+ * the call.
+ */
+int64_t gf_var_batch_work(int64_t N, int W, int64_t M, int64_t seg);
+int gf_var_batch(int B, int64_t N, int Jr, int Jc,
+                 const double *ar, const double *cr, const double *ac, const double *bc,
+                 const double *cc, const double *dc, const double *diag_add,
+                 const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                 const double *y, int64_t y_bs,
+                 const double *ts, int64_t ts_bs, int64_t M, const int64_t *nobs, const int64_t *nq,
+                 int64_t seg, double *work, int64_t work_bs,
+                 double *alpha, double *mu, double *hdiag, double *var, double *var_at,
+                 double *ll, int32_t *info, void *stream);
 
 #ifdef __cplusplus
 }
