@@ -1516,6 +1516,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
 //   z    = H p,  H lower-triangular Toeplitz of the impulse response h(0 .. 63)     (h(63) ~ 5e-3 on the flagship
 //          kernel: H is not truncated); lane i reads p[i - m] from an LDS image of p with 64 zeros in front
 //   s   <- lambda^2 s + lambda G z_j + G z_j+1              lane = term, two rows per step, z by LDS broadcast
+//          (k_steady_finish: on both half-waves, rows 32 .. 63 from a zero state, joined by lambda^32 -- SPLIT below)
 // h is the row form's answer to a unit impulse, computed at the problem's first tail entry of an evaluation and kept
 // in the steady buffer; the p coefficients are recomputed at every launch (per lane one fm_sincos + fm_exp per term,
 // through an LDS staging area of 8 terms so that the loop over the terms is not unrolled around them).
@@ -1540,14 +1541,20 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
                  const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
                  const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
                  double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
-                 double *__restrict__ steady_, double *__restrict__ acc_) {
+                 double *__restrict__ steady_, double *__restrict__ acc_,
+                 const int64_t sw_lo, const int64_t sw_hi) {
     constexpr int JT = ROWS / 2;                    // term slots (Jc <= JT <= 32; slots from Jc on are zero)
+    // the finishing instance runs the state update on both half-waves (lane 32 h + k: term k, rows 32 h .. 32 h + 31 of
+    // a block; below); k_steady_tail keeps it on the lower one
+    constexpr bool SPLIT = !STORE;
     const int lane = threadIdx.x, pr = blockIdx.x;
+    const int half = lane >> 5, tk = SPLIT ? (lane & 31) : lane;    // tk: the term whose constants this lane holds
     if (info[pr] != 0) return;
     double *__restrict__ hdr = steady_ + (size_t)pr * ST_SIZE;
     const double swd = hdr[ST_SW];
     if (!(swd > 0.0)) return;
     const int64_t sw = (int64_t)swd;                // first tail row (global, >= 1)
+    if constexpr (!STORE) { if (sw < sw_lo || sw >= sw_hi) return; }    // another launch's problem: nothing touched
     const int64_t nb = sw > n_first ? sw - n_first : 0;     // first tail row of this tile (local)
     if (nb >= N) return;
     const double *__restrict__ tg = t_ + (size_t)pr * t_bs + n_first;
@@ -1564,8 +1571,8 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     __shared__ double s_c[STT_STAGE][2][64];                        // staging of the p coefficients
 
     // lane = term: this term's constants and state
-    const bool term = lane < Jc;
-    const size_t ck = (size_t)pr * Jc + (term ? lane : 0);
+    const bool term = tk < Jc;
+    const size_t ck = (size_t)pr * Jc + (term ? tk : 0);
     const double ck_c = term ? cc_[ck] : 0.0, ck_d = term ? dc_[ck] : 0.0;
     const double ck_a = term ? ac_[ck] : 0.0, ck_b = term ? bc_[ck] : 0.0;
     const double wmax = wave_max(fmax(ck_c, fabs(ck_d)));
@@ -1578,19 +1585,30 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         lr = e * cs;
         li = -e * sn;
     }
-    const double Gr = (lane < 32) ? hdr[ST_GR + (lane & 31)] : 0.0, Gi = (lane < 32) ? hdr[ST_GI + (lane & 31)] : 0.0;
+    const bool gain = SPLIT || lane < 32;
+    const double Gr = gain ? hdr[ST_GR + (lane & 31)] : 0.0, Gi = gain ? hdr[ST_GI + (lane & 31)] : 0.0;
     double sr = (lane < 32) ? hdr[ST_SR + (lane & 31)] : 0.0, si = (lane < 32) ? hdr[ST_SI + (lane & 31)] : 0.0;
     const double l2r = fma(lr, lr, -li * li), l2i = 2.0 * lr * li;  // lambda^2
     const double lgr = fma(lr, Gr, -li * Gi), lgi = fma(lr, Gi, li * Gr);   // lambda G
+    double l32r = l2r, l32i = l2i;                                  // SPLIT: lambda^32 joins the two half-blocks
+    if constexpr (SPLIT) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const double xr = fma(l32r, l32r, -l32i * l32i);
+            l32i = 2.0 * l32r * l32i;
+            l32r = xr;
+        }
+    }
 
     // impulse response: the row form on y = (1, 0, 0, ...) from s = 0, once per evaluation
     if (hdr[ST_HOK] != 0.0) {
         s_h[lane] = hdr[ST_H + lane];
     } else {
         double hr = Gr, hi = Gi, hv = (lane == 0) ? 1.0 : 0.0;      // h(0) = 1, s = G
+        const double ha = (lane < 32) ? ck_a : 0.0, hb = (lane < 32) ? ck_b : 0.0;  // (each term once in the sum)
         for (int m = 1; m < 64; ++m) {
             const double xr = fma(lr, hr, -li * hi), xi = fma(lr, hi, li * hr);
-            const double hm = -wave_sum(fma(ck_a, xr, -ck_b * xi));
+            const double hm = -wave_sum(fma(ha, xr, -hb * xi));
             hr = fma(Gr, hm, xr);
             hi = fma(Gi, hm, xi);
             hv = (lane == m) ? hm : hv;
@@ -1672,20 +1690,49 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         } else {
             zsq = (lane < lim) ? fma(zv, zv, zsq) : zsq;
         }
-        int j = 0;
-#pragma unroll 4
-        for (; j + 1 < lim; j += 2) {
-            const double2 zz = ((const double2 *)s_z)[j >> 1];
+        // the state update.  SPLIT: the lower half-wave takes the block's rows 0 .. 31 from the incoming state, the
+        // upper one the rows 32 .. 63 from a zero state -- half the chain --, and s <- lambda^(rows of the upper
+        // half) s_low + s_high joins them (the update is linear in the state); the upper half starts the next block
+        // from zero again.  A partial block (the series' last) splits the same way with the rows it has.
+        const int first = SPLIT ? 32 * half : 0;                    // this lane's first row of the block
+        const int mine = !SPLIT ? lim : half ? (lim > 32 ? lim - 32 : 0) : (lim < 32 ? lim : 32);
+        const double *zb = s_z + first;
+        auto two_rows = [&](const int j2) {
+            const double2 zz = ((const double2 *)zb)[j2];
             const double wr = fma(lgr, zz.x, Gr * zz.y), wi = fma(lgi, zz.x, Gi * zz.y);
             const double nr = fma(l2r, sr, fma(-l2i, si, wr));
             si = fma(l2r, si, fma(l2i, sr, wi));
             sr = nr;
+        };
+        int j = 0;
+        if (SPLIT && lim == 64) {                                   // (wave-uniform: every block but the last)
+#pragma unroll 4
+            for (; j < 32; j += 2) two_rows(j >> 1);
+        } else {
+#pragma unroll 4
+            for (; j + 1 < mine; j += 2) two_rows(j >> 1);
         }
-        if (j < lim) {
-            const double zj = s_z[j];
+        if (j < mine) {
+            const double zj = zb[j];
             const double nr = fma(lr, sr, fma(-li, si, Gr * zj));
             si = fma(lr, si, fma(li, sr, Gi * zj));
             sr = nr;
+        }
+        if constexpr (SPLIT) {
+            double jr = l32r, ji = l32i;                            // lambda^(lim - 32): a full block's is at hand
+            if (lim < 64) {
+                jr = 1.0; ji = 0.0;
+                for (int q = 32; q < lim; ++q) {
+                    const double xr = fma(jr, lr, -ji * li);
+                    ji = fma(jr, li, ji * lr);
+                    jr = xr;
+                }
+            }
+            double slr, sur, sli, sui;
+            both_halves(sr, slr, sur);
+            both_halves(si, sli, sui);
+            sr = half ? 0.0 : fma(jr, slr, fma(-ji, sli, sur));
+            si = half ? 0.0 : fma(jr, sli, fma(ji, slr, sui));
         }
     }
     if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
@@ -1711,21 +1758,33 @@ k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double
               double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
               double *__restrict__ steady_) {
     steady_tail_rows<ROWS, true>(N, n_first, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, d_, z_, info,
-                                 steady_, nullptr);
+                                 steady_, nullptr, 0, 0);
 }
 
 // The finishing instance: the rows [switch row, N) of the WHOLE series (N rows from global row 0) of every switched
 // problem in one launch behind the last tile's reduction -- one set-up per evaluation, blocks from the switch row on
 // across the tiles' boundaries, no row stored; acc[b] = {sum log d, sum z^2 / d, min d} takes the tail's share.
+// A launch takes the problems whose switch row lies in [sw_lo, sw_hi) and returns at once for every other one, before
+// it reads or writes anything else of theirs: launches over disjoint windows that cover [1, N] finish every switched
+// problem exactly once, with no flag in the buffer.  Such a launch may run BESIDE later tiles of the same evaluation
+// (gf_steady_sweep + gf_reduce_tile_steady on another stream), without atomics, once the reduction of the tile that
+// holds the window's last switch row is behind it (an event):
+//   - it reads and writes only its own problems' header and acc[b] (and reads their t, y, coefficients and info);
+//   - the sweep wave of a switched problem returns at its test of hdr[ST_SW], which nothing writes after the switch;
+//   - k_reduce1<true> / k_reduce2<true> of a later tile find steady_rows_stored == 0 for such a problem and return
+//     without touching `work` or acc[b] (init is set on the series' first tile only, which cannot lie behind a
+//     switch): the last write of acc[b] on the sweep's stream is the reduction of the tile that holds the switch;
+//   - the problems that have not switched are not this launch's: it leaves at the window test above.
 template <int ROWS>
 __global__ void __launch_bounds__(64, 2)
 k_steady_finish(const int64_t N, const int Jc, const double gap,
                 const double *__restrict__ ac_, const double *__restrict__ bc_,
                 const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
                 const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
-                const int32_t *__restrict__ info, double *__restrict__ steady_, double *__restrict__ acc_) {
+                const int32_t *__restrict__ info, double *__restrict__ steady_, double *__restrict__ acc_,
+                const int64_t sw_lo, const int64_t sw_hi) {
     steady_tail_rows<ROWS, false>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr, info,
-                                  steady_, acc_);
+                                  steady_, acc_, sw_lo, sw_hi);
 }
 
 #define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -5883,19 +5942,23 @@ int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block
                         nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false);
 }
 
-#define GF_SF_CASE(R) case R: hipLaunchKernelGGL((k_steady_finish<R>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc); break;
+#define GF_SF_CASE(R) case R: hipLaunchKernelGGL((k_steady_finish<R>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc, sw_lo, sw_hi); break;
 
-int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
-                     const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
-                     const double *t, int64_t t_bs, const double *y, int64_t y_bs,
-                     const int32_t *info, double *steady, double *acc, void *stream) {
-    if (B < 1 || N < 1) return set_err("gf_steady_finish: empty problem (B=%s%lld, N=%lld)", "", B, N);
+static int steady_finish_launch(const char *who, int B, int64_t N, int Jr, int Jc, int block, int variant,
+                                const double *ac, const double *bc, const double *cc, const double *dc,
+                                const double *cmax, const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                                const int32_t *info, double *steady, double *acc, int64_t sw_lo, int64_t sw_hi,
+                                void *stream) {
+    if (B < 1 || N < 1) return set_err("%s: empty problem (B=%lld, N=%lld)", who, B, N);
     if (Jr != 0 || Jc < 1 || Jc > 31)
-        return set_err("gf_steady_finish: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%s%lld, Jc=%lld)", "", Jr, Jc);
+        return set_err("%s: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%lld, Jc=%lld)", who, Jr, Jc);
     if (block < 1 || block > 64 || (block & (block - 1)))
-        return set_err("gf_steady_finish: block=%s%lld must be a power of two in 1..64", "", block);
+        return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
     if (!ac || !bc || !cc || !dc || !cmax || !t || !y || !info || !steady || !acc)
-        return set_err("gf_steady_finish: null pointer%s", "");
+        return set_err("%s: null pointer", who);
+    if (sw_lo < 0 || sw_hi < sw_lo)
+        return set_err("%s: the window of switch rows needs 0 <= sw_lo <= sw_hi (sw_lo=%lld, sw_hi=%lld)", who, sw_lo, sw_hi);
+    if (sw_lo == sw_hi) return 0;       // an empty window: no launch
     const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
     const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
     hipStream_t st = (hipStream_t)stream;
@@ -5903,9 +5966,26 @@ int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
         GF_SF_CASE(4) GF_SF_CASE(8) GF_SF_CASE(12) GF_SF_CASE(16) GF_SF_CASE(20) GF_SF_CASE(24)
         GF_SF_CASE(28) GF_SF_CASE(32) GF_SF_CASE(36) GF_SF_CASE(40) GF_SF_CASE(44) GF_SF_CASE(48)
         GF_SF_CASE(52) GF_SF_CASE(56) GF_SF_CASE(60) GF_SF_CASE(64)
-        default: return set_err("gf_steady_finish: internal dispatch error%s", "");
+        default: return set_err("%s: internal dispatch error", who);
     }
-    return check_launch("gf_steady_finish");
+    return check_launch(who);
+}
+
+int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                     const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                     const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                     const int32_t *info, double *steady, double *acc, void *stream) {
+    return steady_finish_launch("gf_steady_finish", B, N, Jr, Jc, block, variant, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs,
+                                info, steady, acc, 0, INT64_MAX, stream);
+}
+
+int gf_steady_finish_window(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                            const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                            const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                            const int32_t *info, double *steady, double *acc,
+                            int64_t sw_lo, int64_t sw_hi, void *stream) {
+    return steady_finish_launch("gf_steady_finish_window", B, N, Jr, Jc, block, variant, ac, bc, cc, dc, cmax, t, t_bs,
+                                y, y_bs, info, steady, acc, sw_lo, sw_hi, stream);
 }
 
 int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,

@@ -238,6 +238,15 @@ int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int blo
  *                           tested as gf_loglike_steady tests it (steady[b][2]).  Problems with info != 0 or
  *                           without a switch are left alone.  block, variant: the sweep's (they set its gap test);
  *                           ac .. dc, cmax, t, y and their batch strides: the sweep's.
+ *   gf_steady_finish_window : gf_steady_finish for the problems whose switch row steady[b][0] lies in [sw_lo, sw_hi)
+ *                           (0 <= sw_lo <= sw_hi; switch rows are 1 .. N); every other problem is left alone, nothing
+ *                           of it read or written beyond info[b] and steady[b][0].  A problem runs the code and takes
+ *                           the additions it takes in gf_steady_finish: launches over disjoint windows that cover
+ *                           [1, N + 1) give gf_steady_finish's bits, in any order.  An empty window launches nothing.
+ *                           A window may run on ANOTHER stream beside later tiles of the same evaluation, once the
+ *                           gf_reduce_tile_steady of the tile that holds row sw_hi - 2 has ended (an event): a
+ *                           switched problem's header and acc[b] are touched by nothing else after that reduction.
+ *                           The caller joins the streams before it reads acc or steady.
  * Then gf_loglike_finish.  The values agree with gf_loglike_steady + gf_reduce_tile to the rounding of the sums.
  */
 int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
@@ -255,6 +264,11 @@ int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
                      const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
                      const double *t, int64_t t_bs, const double *y, int64_t y_bs,
                      const int32_t *info, double *steady, double *acc, void *stream);
+int gf_steady_finish_window(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                            const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                            const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                            const int32_t *info, double *steady, double *acc,
+                            int64_t sw_lo, int64_t sw_hi, void *stream);
 
 /*
  * Fused sampling sweep: B draws y = L D^1/2 eps of B different kernels, K = L D L^T, in the sweep that factors
