@@ -1516,7 +1516,12 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
 //   z    = H p,  H lower-triangular Toeplitz of the impulse response h(0 .. 63)     (h(63) ~ 5e-3 on the flagship
 //          kernel: H is not truncated); lane i reads p[i - m] from an LDS image of p with 64 zeros in front
 //   s   <- lambda^2 s + lambda G z_j + G z_j+1              lane = term, two rows per step, z by LDS broadcast
-//          (k_steady_finish: on both half-waves, rows 32 .. 63 from a zero state, joined by lambda^32 -- SPLIT below)
+//          (k_steady_finish: on both half-waves, rows 32 .. 63 from a zero state, joined by lambda^32 -- FOLD below)
+// k_steady_finish folds the first two lines (FOLD below): with p = y + C s,  z = H y + Q s,  Q = H C.  Q takes C's
+// registers (one row per lane; the set-up applies H to each of C's columns), u = H y depends on the data alone and is
+// formed one block ahead, and the chain from a block's state to the next is  s -> LDS -> z = u + Q s -> LDS -> state
+// update -> join: H's 64 reads and its 32-deep FMA chains are off it.  H y needs no LDS image: y lies one row per lane
+// and moves up one lane per tap (DPP wave_shr:1), h by broadcast.
 // h is the row form's answer to a unit impulse, computed at the problem's first tail entry of an evaluation and kept
 // in the steady buffer; the p coefficients are recomputed at every launch (per lane one fm_sincos + fm_exp per term,
 // through an LDS staging area of 8 terms so that the loop over the terms is not unrolled around them).
@@ -1524,11 +1529,21 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
 // t and y arrive by one coalesced load per block, issued a block ahead; d (= d_inf) and z leave by one coalesced
 // store per block (k_steady_tail; k_steady_finish, the streamed log-likelihood's instance, stores no row: below).
 // A partial last block runs the same code: H is lower triangular, so the rows beyond the tile (y clamped to the
-// last row) touch no row before them; the s loop is bounded and the stores are masked.
+// last row) touch no row before them; the s loop is bounded and the stores are masked.  (k_steady_finish: behind its
+// loop of full blocks, with the u the block before it formed.)
 // Every spacing t_r - t_{r-1} of a tail row r is tested as RowGen tests it (a gap: > gthr; off the frozen cadence:
 // >= jthr): a hit raises ST_VIOL and the rows of that evaluation mean nothing (finite).
 // ------------------------------------------------------------------------------------
 constexpr int STT_STAGE = 8;        // terms per staging pass of the p coefficients
+constexpr int FG = 6;               // terms per group of s broadcasts in the folded block's z phase
+// lane i <- lane i - 1, lane 0 <- 0 (DPP wave_shr:1, one move per half of the double)
+__device__ __forceinline__ double wave_shr1(const double v) { return dpp_get<0x138, 0xf>(v); }
+// closes a stage of a hand-staged basic block: the LDS reads behind it are issued behind it (the fence orders them
+// where the block is laid out, the scheduling barrier where it is scheduled); no instruction of its own
+__device__ __forceinline__ void stage_end() {
+    wave_lds_fence();
+    __builtin_amdgcn_sched_barrier(0);
+}
 constexpr int RED_NACC = 3;         // the reductions' accumulators per problem: sum log d, sum z^2/d, min d
 
 // STORE = true: the rows leave as d and z (k_steady_tail, tile by tile); STORE = false: no row is stored, every lane
@@ -1544,11 +1559,12 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
                  double *__restrict__ steady_, double *__restrict__ acc_,
                  const int64_t sw_lo, const int64_t sw_hi) {
     constexpr int JT = ROWS / 2;                    // term slots (Jc <= JT <= 32; slots from Jc on are zero)
-    // the finishing instance runs the state update on both half-waves (lane 32 h + k: term k, rows 32 h .. 32 h + 31 of
-    // a block; below); k_steady_tail keeps it on the lower one
-    constexpr bool SPLIT = !STORE;
+    // the finishing instance's form of a block: the state update on both half-waves (lane 32 h + k: term k, rows 32 h ..
+    // 32 h + 31 of a block), and H off the chain from one block's state to the next, z = H (y + C s) = H y + Q s with
+    // Q = H C (both below); k_steady_tail keeps the update on the lower half-wave and the three phases in series
+    constexpr bool FOLD = !STORE;
     const int lane = threadIdx.x, pr = blockIdx.x;
-    const int half = lane >> 5, tk = SPLIT ? (lane & 31) : lane;    // tk: the term whose constants this lane holds
+    const int half = lane >> 5, tk = FOLD ? (lane & 31) : lane;    // tk: the term whose constants this lane holds
     if (info[pr] != 0) return;
     double *__restrict__ hdr = steady_ + (size_t)pr * ST_SIZE;
     const double swd = hdr[ST_SW];
@@ -1569,6 +1585,35 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     __shared__ __attribute__((aligned(16))) double s_h[64];         // impulse response
     __shared__ __attribute__((aligned(16))) double s_z[64];         // z of the block
     __shared__ double s_c[STT_STAGE][2][64];                        // staging of the p coefficients
+    // 64 rows of H against an image: lane i adds h(m) v[i - m], m in [0, 64), even m to a0 and odd m to a1
+    auto taps = [&](const double *pp, double &a0, double &a1) {
+#pragma unroll
+        for (int m = 0; m < 64; m += 2) {
+            const double2 hv = ((const double2 *)s_h)[m >> 1];
+            a0 = fma(hv.x, pp[-m], a0);
+            a1 = fma(hv.y, pp[-m - 1], a1);
+        }
+    };
+    // the same on a vector that lies one row per lane, without an image: lane i adds h(m) v[i - m] with v moved up one
+    // lane per tap (a DPP wave shift; zeros come in at lane 0).  Two vectors against one read of h, in a loop that stays
+    // rolled: the set-up's form, which runs with Q in the registers
+    auto shifted_taps = [&](double va, double vb, double &ra, double &rb) {
+        double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
+#pragma unroll 1
+        for (int m = 0; m < 64; m += 2) {
+            const double2 hv = ((const double2 *)s_h)[m >> 1];
+            a0 = fma(hv.x, va, a0);
+            b0 = fma(hv.x, vb, b0);
+            va = wave_shr1(va);
+            vb = wave_shr1(vb);
+            a1 = fma(hv.y, va, a1);
+            b1 = fma(hv.y, vb, b1);
+            va = wave_shr1(va);
+            vb = wave_shr1(vb);
+        }
+        ra = a0 + a1;
+        rb = b0 + b1;
+    };
 
     // lane = term: this term's constants and state
     const bool term = tk < Jc;
@@ -1585,13 +1630,13 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         lr = e * cs;
         li = -e * sn;
     }
-    const bool gain = SPLIT || lane < 32;
+    const bool gain = FOLD || lane < 32;
     const double Gr = gain ? hdr[ST_GR + (lane & 31)] : 0.0, Gi = gain ? hdr[ST_GI + (lane & 31)] : 0.0;
     double sr = (lane < 32) ? hdr[ST_SR + (lane & 31)] : 0.0, si = (lane < 32) ? hdr[ST_SI + (lane & 31)] : 0.0;
     const double l2r = fma(lr, lr, -li * li), l2i = 2.0 * lr * li;  // lambda^2
     const double lgr = fma(lr, Gr, -li * Gi), lgi = fma(lr, Gi, li * Gr);   // lambda G
-    double l32r = l2r, l32i = l2i;                                  // SPLIT: lambda^32 joins the two half-blocks
-    if constexpr (SPLIT) {
+    double l32r = l2r, l32i = l2i;                                  // FOLD: lambda^32 joins the two half-blocks
+    if constexpr (FOLD) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const double xr = fma(l32r, l32r, -l32i * l32i);
@@ -1617,10 +1662,11 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         hdr[ST_H + lane] = hv;
         if (lane == 0) hdr[ST_HOK] = 1.0;
     }
-    s_p[lane] = 0.0;
+    if constexpr (!FOLD) s_p[lane] = 0.0;
 
     // lane = row of a block: -alpha_k lambda_k^(i+1) = (pr_k, pi_k) with Re(.) taken against (s_r, s_i):
-    // p = y + sum_k pr_k s_r,k + pi_k s_i,k
+    // p = y + sum_k pr_k s_r,k + pi_k s_i,k.  FOLD: H applied to each of these 2 JT columns where they are
+    // computed (shifted_taps): pcr, pci hold the rows of Q, z = H y + sum_k pr_k s_r,k + pi_k s_i,k
     double pcr[JT], pci[JT];
     const double di = delta * (double)(lane + 1);
 #pragma unroll
@@ -1638,6 +1684,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
                 const double e = fm_exp(-cc_[uk] * di);
                 vr = -e * fma(a, cs, b * sn);       // Re(alpha lambda^(i+1)), Im = e (b cs - a sn)
                 vi = e * fma(b, cs, -a * sn);
+                if constexpr (FOLD) shifted_taps(vr, vi, vr, vi);
             }
             s_c[kk][0][lane] = vr;
             s_c[kk][1][lane] = vi;
@@ -1652,7 +1699,26 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     const int64_t last = N - 1;
     auto row_of = [&](const int64_t cb) { const int64_t i = cb + lane; return i < last ? i : last; };
     bool viol = false;
-    double y_nx = yg[row_of(nb)], t_nx = tg[row_of(nb)], tp_nx = tg[row_of(nb) - 1];
+    double t_nx = tg[row_of(nb)], tp_nx = tg[row_of(nb) - 1];
+    // the pieces every form of a block shares: term k of p (or of Q s) against the broadcast (s_r, s_i), even terms to
+    // x0 and odd ones to x1; the state over two rows z_j, z_j+1, and over one
+    auto add_term = [&](const int k, const double2 sv, double &x0, double &x1) {
+        if (k & 1) x1 = fma(pci[k], sv.y, fma(pcr[k], sv.x, x1));
+        else x0 = fma(pci[k], sv.y, fma(pcr[k], sv.x, x0));
+    };
+    auto two_rows = [&](const double2 zz) {
+        const double wr = fma(lgr, zz.x, Gr * zz.y), wi = fma(lgi, zz.x, Gi * zz.y);
+        const double nr = fma(l2r, sr, fma(-l2i, si, wr));
+        si = fma(l2r, si, fma(l2i, sr, wi));
+        sr = nr;
+    };
+    auto one_row = [&](const double zj) {
+        const double nr = fma(lr, sr, fma(-li, si, Gr * zj));
+        si = fma(lr, si, fma(li, sr, Gi * zj));
+        sr = nr;
+    };
+    if constexpr (!FOLD) {
+    double y_nx = yg[row_of(nb)];
     for (int64_t cb = nb; cb < N; cb += 64) {
         const double yv = y_nx, tv = t_nx, tp = tp_nx;              // rows cb + lane (clamped to the tile's last)
         {
@@ -1667,73 +1733,150 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         wave_lds_fence();
         double p0 = yv, p1 = 0.0;
 #pragma unroll
-        for (int k = 0; k < JT; ++k) {
-            const double2 sv = ((const double2 *)s_s)[k];
-            if (k & 1) p1 = fma(pci[k], sv.y, fma(pcr[k], sv.x, p1));
-            else p0 = fma(pci[k], sv.y, fma(pcr[k], sv.x, p0));
-        }
+        for (int k = 0; k < JT; ++k) add_term(k, ((const double2 *)s_s)[k], p0, p1);
         s_p[64 + lane] = p0 + p1;
         wave_lds_fence();
         double z0 = 0.0, z1 = 0.0;
-        const double *pp = s_p + 64 + lane;
+        taps(s_p + 64 + lane, z0, z1);
+        const double zv = z0 + z1;
+        s_z[lane] = zv;
+        wave_lds_fence();
+        if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
+        // the state update, two rows per step
+        int j = 0;
+#pragma unroll 4
+        for (; j + 1 < lim; j += 2) two_rows(((const double2 *)s_z)[j >> 1]);
+        if (j < lim) one_row(s_z[j]);
+    }
+    } else {
+    // The folded block.  u = H y of a block depends on the data alone: it is formed a block ahead, in pieces between
+    // the phases of the chain  s -> LDS -> z = u + Q s -> LDS -> state update -> join,  whose waits it fills.  y is
+    // loaded a block ahead, one row per lane, and moves up a lane per tap.  The series' last block has no successor:
+    // its u comes from rows clamped as row_of clamps them, and nothing reads it.
+    double u, y_nx = yg[row_of(nb + 64)];
+    {
+        double unused;
+        shifted_taps(yg[row_of(nb)], 0.0, u, unused);
+    }
+    // the state update: the lower half-wave takes the block's rows 0 .. 31 from the incoming state, the upper one the
+    // rows 32 .. 63 from a zero state -- half the chain --, and s <- lambda^(rows of the upper half) s_low + s_high
+    // joins them (the update is linear in the state); the upper half starts the next block from zero again.  A
+    // partial block (the series' last) splits the same way with the rows it has.
+    const double *zb = s_z + 32 * half;
+    auto join = [&](const double jr, const double ji) {
+        double slr, sur, sli, sui;
+        both_halves(sr, slr, sur);
+        both_halves(si, sli, sui);
+        sr = half ? 0.0 : fma(jr, slr, fma(-ji, sli, sur));
+        si = half ? 0.0 : fma(jr, sli, fma(ji, slr, sui));
+    };
+    int64_t cb = nb;
+    // The full blocks: one basic block each, in stages.  A stage ends in a scheduling barrier, so that its LDS reads
+    // are issued a stage before the FMAs that take them and no further ahead (the registers hold Q): the s broadcasts
+    // in groups of FG terms, z of the state update eight rows ahead, and in every stage four taps of the next
+    // block's u -- their reads in one stage, their FMAs in the next.
+    for (; cb + 64 <= N; cb += 64) {
+        double ys = y_nx;                           // y of the rows cb + 64 + lane: moves up a lane per tap of u
+        const double tv = t_nx, tp = tp_nx;         // t of the rows cb + lane
+        {
+            const int64_t i = row_of(cb + 64);
+            t_nx = tg[i]; tp_nx = tg[i - 1];
+            y_nx = yg[row_of(cb + 128)];
+        }
+        const double dt = tv - tp;
+        viol |= (dt > gthr) || !(fabs(dt - delta) < jthr);
+        wave_lds_fence();
+        if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
+        wave_lds_fence();
+        constexpr int NG = (JT + FG - 1) / FG;
+        // u_stage reads four taps' h in one call and takes them in the next: 16 reading calls and one more
+        static_assert(NG + 16 >= 17, "the stages of a full block must call u_stage at least 17 times");
+        double a0 = 0.0, a1 = 0.0, z0 = u, z1 = 0.0;
+        double2 sv[2][FG], uh[2], zz[16];
+        int uq = 0;                                 // (a constant in every stage once the stages are unrolled)
+        auto u_stage = [&]() {
+            if (uq > 0 && uq <= 16) {
+                a0 = fma(uh[0].x, ys, a0);
+                ys = wave_shr1(ys);
+                a1 = fma(uh[0].y, ys, a1);
+                ys = wave_shr1(ys);
+                a0 = fma(uh[1].x, ys, a0);
+                ys = wave_shr1(ys);
+                a1 = fma(uh[1].y, ys, a1);
+                ys = wave_shr1(ys);
+            }
+            if (uq < 16) {
+                uh[0] = ((const double2 *)s_h)[2 * uq];
+                uh[1] = ((const double2 *)s_h)[2 * uq + 1];
+            }
+            ++uq;
+        };
+        auto s_ld = [&](const int g) {
 #pragma unroll
-        for (int m = 0; m < 64; m += 2) {
-            const double2 hv = ((const double2 *)s_h)[m >> 1];
-            z0 = fma(hv.x, pp[-m], z0);
-            z1 = fma(hv.y, pp[-m - 1], z1);
+            for (int i = 0; i < FG; ++i)
+                if (g * FG + i < JT) sv[g & 1][i] = ((const double2 *)s_s)[g * FG + i];
+        };
+        s_ld(0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g + 1 < NG) s_ld(g + 1);
+            u_stage();
+            stage_end();
+#pragma unroll
+            for (int i = 0; i < FG; ++i) {
+                const int k = g * FG + i;
+                if (k < JT) add_term(k, sv[g & 1][i], z0, z1);
+            }
         }
         const double zv = z0 + z1;
         s_z[lane] = zv;
         wave_lds_fence();
-        if constexpr (STORE) {
-            if (lane < lim) { dg[cb + lane] = dinf; zg[cb + lane] = zv; }
-        } else {
-            zsq = (lane < lim) ? fma(zv, zv, zsq) : zsq;
-        }
-        // the state update.  SPLIT: the lower half-wave takes the block's rows 0 .. 31 from the incoming state, the
-        // upper one the rows 32 .. 63 from a zero state -- half the chain --, and s <- lambda^(rows of the upper
-        // half) s_low + s_high joins them (the update is linear in the state); the upper half starts the next block
-        // from zero again.  A partial block (the series' last) splits the same way with the rows it has.
-        const int first = SPLIT ? 32 * half : 0;                    // this lane's first row of the block
-        const int mine = !SPLIT ? lim : half ? (lim > 32 ? lim - 32 : 0) : (lim < 32 ? lim : 32);
-        const double *zb = s_z + first;
-        auto two_rows = [&](const int j2) {
-            const double2 zz = ((const double2 *)zb)[j2];
-            const double wr = fma(lgr, zz.x, Gr * zz.y), wi = fma(lgi, zz.x, Gi * zz.y);
-            const double nr = fma(l2r, sr, fma(-l2i, si, wr));
-            si = fma(l2r, si, fma(l2i, sr, wi));
-            sr = nr;
-        };
-        int j = 0;
-        if (SPLIT && lim == 64) {                                   // (wave-uniform: every block but the last)
-#pragma unroll 4
-            for (; j < 32; j += 2) two_rows(j >> 1);
-        } else {
-#pragma unroll 4
-            for (; j + 1 < mine; j += 2) two_rows(j >> 1);
-        }
-        if (j < mine) {
-            const double zj = zb[j];
-            const double nr = fma(lr, sr, fma(-li, si, Gr * zj));
-            si = fma(lr, si, fma(li, sr, Gi * zj));
-            sr = nr;
-        }
-        if constexpr (SPLIT) {
-            double jr = l32r, ji = l32i;                            // lambda^(lim - 32): a full block's is at hand
-            if (lim < 64) {
-                jr = 1.0; ji = 0.0;
-                for (int q = 32; q < lim; ++q) {
-                    const double xr = fma(jr, lr, -ji * li);
-                    ji = fma(jr, li, ji * lr);
-                    jr = xr;
-                }
+        zsq = fma(zv, zv, zsq);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) zz[i] = ((const double2 *)zb)[i];
+#pragma unroll
+        for (int j2 = 0; j2 < 16; ++j2) {
+            if (j2 >= 4 && j2 < 12 && (j2 & 3) == 0) {
+#pragma unroll
+                for (int i = j2 + 4; i < j2 + 8; ++i) zz[i] = ((const double2 *)zb)[i];
             }
-            double slr, sur, sli, sui;
-            both_halves(sr, slr, sur);
-            both_halves(si, sli, sui);
-            sr = half ? 0.0 : fma(jr, slr, fma(-ji, sli, sur));
-            si = half ? 0.0 : fma(jr, sli, fma(ji, slr, sui));
+            u_stage();
+            stage_end();
+            two_rows(zz[j2]);
         }
+        join(l32r, l32i);
+        u = a0 + a1;
+    }
+    if (cb < N) {                                   // a partial last block: lim rows, u from the block before
+        const int lim = (int)(N - cb);
+        const double dt = t_nx - tp_nx;
+        viol |= (lane < lim) && ((dt > gthr) || !(fabs(dt - delta) < jthr));
+        wave_lds_fence();
+        if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
+        wave_lds_fence();
+        double z0 = u, z1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < JT; ++k) {
+            add_term(k, ((const double2 *)s_s)[k], z0, z1);
+            if (k % FG == FG - 1) stage_end();
+        }
+        const double zv = z0 + z1;
+        s_z[lane] = zv;
+        wave_lds_fence();
+        zsq = (lane < lim) ? fma(zv, zv, zsq) : zsq;
+        const int mine = half ? (lim > 32 ? lim - 32 : 0) : (lim < 32 ? lim : 32);
+        int j = 0;
+#pragma unroll 1
+        for (; j + 1 < mine; j += 2) two_rows(((const double2 *)zb)[j >> 1]);
+        if (j < mine) one_row(zb[j]);
+        double jr = 1.0, ji = 0.0;                  // lambda^(lim - 32)
+        for (int q = 32; q < lim; ++q) {
+            const double xr = fma(jr, lr, -ji * li);
+            ji = fma(jr, li, ji * lr);
+            jr = xr;
+        }
+        join(jr, ji);
+    }
     }
     if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
     if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
