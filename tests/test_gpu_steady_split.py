@@ -1,7 +1,9 @@
 """GPU: the finishing launch's state update on both half-waves (restated in numpy in
 tests/test_steady_finish_host.py): tails of 1, 2, 31, 32, 33, 63, 64 and 65 rows behind a forced switch -- a last block
 of every shape the split has: the lower half-wave alone (even, odd, exactly full), one and two rows on the upper one,
-both full, and a second block of one row -- against the oracle and the plain sweep."""
+both full, and a second block of one row -- against the oracle and the plain sweep.  What is compared are whole-series
+totals: the ~3969 swept rows in front of the switch dilute whatever the tail adds (a tail of one row is 1/4000 of both
+sums).  The tail's own sums, per finishing launch and at every instance: tests/test_gpu_steady_instances.py."""
 import numpy as np
 import pytest
 
