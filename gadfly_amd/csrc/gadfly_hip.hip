@@ -2401,9 +2401,12 @@ k_factorw(const FactorWArgs A,
             b2 = (b2 == 2) ? 0 : b2 + 1;
             a_0 = a_1; y_0 = y_1; a_1 = a_2; y_1 = y_2;
             t_2 = t_3; y_2 = y_3; g_2 = g_3;
-            t_3 = tg[n + 4 + vz];
-            y_3 = yg[n + 4 + vz];
-            g_3 = gg[n + 4 + vz];
+            // (row n + 4 is used only while n + 4 <= rows + 1: the index stops at the third element past the last
+            // row, the padding that the entry points ask for)
+            const int64_t n4 = (n + 4 < rows + 2) ? n + 4 : rows + 2;
+            t_3 = tg[n4 + vz];
+            y_3 = yg[n4 + vz];
+            g_3 = gg[n4 + vz];
             wg_lds_barrier();
             double s1 = 0.0;
 #pragma unroll

@@ -1,7 +1,7 @@
 """Device side of the sweep edge tests (test_gpu_sweep_edges.py, test_gpu_solve_chunk_edges.py,
-test_gpu_general_matmul_edges.py): the oracle's factor of tests/sweep_cases.reference on the device, and raw calls of
-gf_solve / gf_solve_chunk[_rhs] whose outputs are one problem too long and pre-filled with a sentinel that must
-survive past the end."""
+test_gpu_general_matmul_edges.py, test_gpu_fused_rows.py): the oracle's factor of tests/sweep_cases.reference on the
+device, and raw calls of gf_solve / gf_solve_chunk[_rhs] whose outputs are one problem too long and pre-filled with a
+sentinel that must survive past the end."""
 import numpy as np
 import torch
 
@@ -17,6 +17,26 @@ def dev(x, dtype=np.float64):
 
 def sentinel(n):
     return torch.full((int(n),), SENTINEL, dtype=torch.float64, device="cuda")
+
+
+def zeroed_with_sentinel(n, extra):
+    """n zeros (a state the caller must zero) with ``extra`` sentinel elements behind them."""
+    buf = sentinel(n + extra)
+    buf[:n] = 0.0
+    return buf
+
+
+def info_with_sentinel(B):
+    """B zeroed info entries and one more that holds INFO_SENTINEL."""
+    info = torch.full((B + 1,), INFO_SENTINEL, dtype=torch.int32, device="cuda")
+    info[:B] = 0
+    return info
+
+
+def take_info(info, B, what=""):
+    x = info.cpu().numpy()
+    assert x[B] == INFO_SENTINEL, f"{what}: info written past the end"
+    return x[:B].copy()
 
 
 def take(buf, n, what=""):
