@@ -142,7 +142,7 @@ class GadflyHipError(RuntimeError):
 
 
 HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC"]
-_DEPS = [HEADER] + [os.path.join(CSRC, h) for h in ("fastmath.h", "gf_internal.h", "gf_wave.h")]
+_DEPS = [HEADER] + [os.path.join(CSRC, h) for h in ("fastmath.h", "gf_internal.h", "gf_wave.h", "gf_rows.h")]
 
 
 def hipcc_command(out=SO_PATH):

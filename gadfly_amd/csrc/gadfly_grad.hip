@@ -25,13 +25,9 @@
 
 #include "../../include/gadfly_hip.h"
 #include "gf_internal.h"
+#include "gf_rows.h"
 
 namespace {
-
-constexpr int GR_LANES = 64;
-constexpr int GR_MAX_W = 63;
-
-__host__ __device__ inline int grad_wm(int W) { return W <= 16 ? 16 : W <= 32 ? 32 : 64; }
 
 // rows per segment: the smallest K with K^2 >= N
 inline int64_t grad_seg(int64_t N) {
@@ -44,11 +40,11 @@ inline int64_t grad_seg(int64_t N) {
 // doubles per checkpoint (S rows, G, W, D, z; a lane's row of S contiguous) and per staged row (S, G, W, f, U, V, p,
 // D, z; S column-major, element (j, k) at k * 64 + j, so that every load and store of the wave is one contiguous
 // 512-byte run), the vectors one element per lane
-__host__ __device__ inline int64_t grad_ck(int WM) { return (int64_t)(WM + 4) * GR_LANES; }
-__host__ __device__ inline int64_t grad_rs(int WM) { return (int64_t)(WM + 8) * GR_LANES; }
+__host__ __device__ inline int64_t grad_ck(int WM) { return (int64_t)(WM + 4) * ROW_LANES; }
+__host__ __device__ inline int64_t grad_rs(int WM) { return (int64_t)(WM + 8) * ROW_LANES; }
 
 inline int64_t grad_work(int64_t N, int W) {
-    const int WM = grad_wm(W);
+    const int WM = row_wm(W);
     const int64_t K = grad_seg(N), nseg = (N + K - 1) / K;
     return nseg * grad_ck(WM) + K * grad_rs(WM);
 }
@@ -58,20 +54,9 @@ inline int64_t grad_work(int64_t N, int W) {
 // in those loops; the reverse step's staged S is loaded whole before them (one memory wait per row).
 #define GR_PACE(k) do { if (((k) & 7) == 7) __builtin_amdgcn_sched_barrier(0); } while (0)
 
-__device__ __forceinline__ double wsum(double x) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, GR_LANES);
-    return x;        // (a + b == b + a: every lane ends with the same bits)
-}
-
-// one state column of the celerite form: a real term (U = a, V = 1) or one half of a complex term
-struct Col {
-    double a, b, c, d;
-    int kind;        // 0 inactive lane, 1 real, 2 complex
-    int half;        // complex: 0 = cosine column, 1 = sine column
-};
-
-__device__ __forceinline__ void gen_row(const Col &q, double tn, double &u, double &v) {
+// gf_rows.h's gen_row and fwd_row with plain products and sums (this unit contracts them; no explicit fma) and with
+// f and v as further outputs: separate on purpose, sharing them would change this kernel's bits
+__device__ __forceinline__ void grad_gen_row(const Col &q, double tn, double &u, double &v) {
     if (q.kind == 2) {
         double s, co;
         sincos(q.d * tn, &s, &co);        // theta = fl(d t), as celerite2
@@ -86,22 +71,22 @@ __device__ __forceinline__ void gen_row(const Col &q, double tn, double &u, doub
 
 // one forward row: (S, G, w, D, z) of row n-1 in, of row n out; f, u, v, p of row n out
 template <int WM>
-__device__ __forceinline__ void fwd_row(double (&S)[WM], double &G, double &w, double &D, double &z,
-                                        const Col &q, double tprev, double tn, double An, double yn,
-                                        double *sh, int lane, double &f, double &u, double &v, double &p) {
-    gen_row(q, tn, u, v);
+__device__ __forceinline__ void grad_fwd_row(double (&S)[WM], double &G, double &w, double &D, double &z,
+                                             const Col &q, double tprev, double tn, double An, double yn,
+                                             double *sh, int lane, double &f, double &u, double &v, double &p) {
+    grad_gen_row(q, tn, u, v);
     p = exp(q.c * (tprev - tn));
     const double wi = D * w;
     sh[lane] = w;
-    sh[GR_LANES + lane] = p;
-    sh[2 * GR_LANES + lane] = u;
+    sh[ROW_LANES + lane] = p;
+    sh[2 * ROW_LANES + lane] = u;
     __syncthreads();
     f = 0.0;
 #pragma unroll
     for (int k = 0; k < WM; ++k) {
-        const double s = (p * sh[GR_LANES + k]) * (S[k] + wi * sh[k]);
+        const double s = (p * sh[ROW_LANES + k]) * (S[k] + wi * sh[k]);
         S[k] = s;
-        f += s * sh[2 * GR_LANES + k];
+        f += s * sh[2 * ROW_LANES + k];
         GR_PACE(k);
     }
     G = p * (G + w * z);
@@ -112,7 +97,7 @@ __device__ __forceinline__ void fwd_row(double (&S)[WM], double &G, double &w, d
 }
 
 template <int WM>
-__global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_grad(
+__global__ __launch_bounds__(ROW_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_grad(
     int64_t N, int64_t K, int64_t nseg, int Jr, int Jc,
     const double *__restrict__ ar, const double *__restrict__ cr, const double *__restrict__ ac,
     const double *__restrict__ bc, const double *__restrict__ cc, const double *__restrict__ dc,
@@ -121,8 +106,8 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
     double *__restrict__ work, int64_t work_bs, double *__restrict__ ll, double *__restrict__ g_real,
     double *__restrict__ g_comp, double *__restrict__ g_diag, double *__restrict__ g_mean,
     int32_t *__restrict__ info) {
-    __shared__ double sh[2][4 * GR_LANES];
-    __shared__ double Sb[WM * GR_LANES];           // Sbar, element (j, k) at k * 64 + j: lane j's row, conflict-free
+    __shared__ double sh[2][4 * ROW_LANES];
+    __shared__ double Sb[WM * ROW_LANES];           // Sbar, element (j, k) at k * 64 + j: lane j's row, conflict-free
     const int B = (int)gridDim.x, b = (int)blockIdx.x, lane = (int)threadIdx.x;
     const int lr = Jr > 0 ? Jr : 1, lc = Jc > 0 ? Jc : 1, W = Jr + 2 * Jc;
     Col q{0.0, 0.0, 0.0, 0.0, 0, 0};
@@ -158,14 +143,14 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
             double *c = ck + (n / K) * grad_ck(WM);
 #pragma unroll
             for (int k = 0; k < WM; ++k) c[lane * WM + k] = S[k];
-            c[(WM + 0) * GR_LANES + lane] = G;
-            c[(WM + 1) * GR_LANES + lane] = w;
-            c[(WM + 2) * GR_LANES + lane] = D;
-            c[(WM + 3) * GR_LANES + lane] = z;
+            c[(WM + 0) * ROW_LANES + lane] = G;
+            c[(WM + 1) * ROW_LANES + lane] = w;
+            c[(WM + 2) * ROW_LANES + lane] = D;
+            c[(WM + 3) * ROW_LANES + lane] = z;
         }
         const double tn = t[n], tp = n ? t[n - 1] : tn;
         const double An = (dg ? dg[n] : 0.0) + dadd;
-        fwd_row<WM>(S, G, w, D, z, q, tp, tn, An, y[n], sh[n & 1], lane, f, u, v, p);
+        grad_fwd_row<WM>(S, G, w, D, z, q, tp, tn, An, y[n], sh[n & 1], lane, f, u, v, p);
         if (!(D > 0.0)) { bad = n + 1; break; }
         logdet += log(D);
         quad += z * z / D;
@@ -184,7 +169,7 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     // ---- reverse: segments last first, each recomputed from its checkpoint and staged row by row
 #pragma unroll
-    for (int k = 0; k < WM; ++k) Sb[k * GR_LANES + lane] = 0.0;
+    for (int k = 0; k < WM; ++k) Sb[k * ROW_LANES + lane] = 0.0;
     double Hb = 0.0;                                   // adjoint of G_{n} + W_{n} z_{n}, i.e. of P^-1 G_{n+1}
     double ga = 0.0, gb = 0.0, gc = 0.0, gtht = 0.0, gA = 0.0, gy = 0.0;
     #pragma unroll 1
@@ -193,26 +178,26 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
         const double *c = ck + s * grad_ck(WM);
 #pragma unroll
         for (int k = 0; k < WM; ++k) S[k] = c[lane * WM + k];
-        G = c[(WM + 0) * GR_LANES + lane];
-        w = c[(WM + 1) * GR_LANES + lane];
-        D = c[(WM + 2) * GR_LANES + lane];
-        z = c[(WM + 3) * GR_LANES + lane];
+        G = c[(WM + 0) * ROW_LANES + lane];
+        w = c[(WM + 1) * ROW_LANES + lane];
+        D = c[(WM + 2) * ROW_LANES + lane];
+        z = c[(WM + 3) * ROW_LANES + lane];
         #pragma unroll 1
         for (int64_t n = n0; n < n1; ++n) {
             const double tn = t[n], tp = n ? t[n - 1] : tn;
             const double An = (dg ? dg[n] : 0.0) + dadd;
-            fwd_row<WM>(S, G, w, D, z, q, tp, tn, An, y[n], sh[n & 1], lane, f, u, v, p);
+            grad_fwd_row<WM>(S, G, w, D, z, q, tp, tn, An, y[n], sh[n & 1], lane, f, u, v, p);
             double *r = rows + (n - n0) * grad_rs(WM);
 #pragma unroll
-            for (int k = 0; k < WM; ++k) r[k * GR_LANES + lane] = S[k];
-            r[(WM + 0) * GR_LANES + lane] = G;
-            r[(WM + 1) * GR_LANES + lane] = w;
-            r[(WM + 2) * GR_LANES + lane] = f;
-            r[(WM + 3) * GR_LANES + lane] = u;
-            r[(WM + 4) * GR_LANES + lane] = v;
-            r[(WM + 5) * GR_LANES + lane] = p;
-            r[(WM + 6) * GR_LANES + lane] = D;
-            r[(WM + 7) * GR_LANES + lane] = z;
+            for (int k = 0; k < WM; ++k) r[k * ROW_LANES + lane] = S[k];
+            r[(WM + 0) * ROW_LANES + lane] = G;
+            r[(WM + 1) * ROW_LANES + lane] = w;
+            r[(WM + 2) * ROW_LANES + lane] = f;
+            r[(WM + 3) * ROW_LANES + lane] = u;
+            r[(WM + 4) * ROW_LANES + lane] = v;
+            r[(WM + 5) * ROW_LANES + lane] = p;
+            r[(WM + 6) * ROW_LANES + lane] = D;
+            r[(WM + 7) * ROW_LANES + lane] = z;
         }
         #pragma unroll 1
         for (int64_t n = n1 - 1; n >= n0; --n) {
@@ -221,26 +206,26 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
             // retires in order: waiting for the vectors does not wait for S).  S's HBM latency then runs under the
             // first half of the step -- the LDS contraction with Sbar and three reductions -- one wait per row.
             const double tn = t[n], tq = t[n ? n - 1 : 0];
-            const double Gn = r[(WM + 0) * GR_LANES + lane], wn = r[(WM + 1) * GR_LANES + lane];
-            const double fn = r[(WM + 2) * GR_LANES + lane], un = r[(WM + 3) * GR_LANES + lane];
-            const double vn = r[(WM + 4) * GR_LANES + lane], pn = r[(WM + 5) * GR_LANES + lane];
-            const double Dn = r[(WM + 6) * GR_LANES + lane], zn = r[(WM + 7) * GR_LANES + lane];
+            const double Gn = r[(WM + 0) * ROW_LANES + lane], wn = r[(WM + 1) * ROW_LANES + lane];
+            const double fn = r[(WM + 2) * ROW_LANES + lane], un = r[(WM + 3) * ROW_LANES + lane];
+            const double vn = r[(WM + 4) * ROW_LANES + lane], pn = r[(WM + 5) * ROW_LANES + lane];
+            const double Dn = r[(WM + 6) * ROW_LANES + lane], zn = r[(WM + 7) * ROW_LANES + lane];
             __builtin_amdgcn_sched_barrier(0);
             double sn[WM];
 #pragma unroll
-            for (int k = 0; k < WM; ++k) sn[k] = r[k * GR_LANES + lane];
+            for (int k = 0; k < WM; ++k) sn[k] = r[k * ROW_LANES + lane];
             __builtin_amdgcn_sched_barrier(0);
             const double dtn = tq - tn;                    // 0 at row 0
             double *x = sh[n & 1];
             x[lane] = wn;
-            x[GR_LANES + lane] = pn;
-            x[2 * GR_LANES + lane] = un;
+            x[ROW_LANES + lane] = pn;
+            x[2 * ROW_LANES + lane] = un;
             __syncthreads();
             // M_{n+1} = S_n + D_n W_n W_n^T and H_{n+1} = G_n + W_n z_n
             double qv = 0.0;
 #pragma unroll
             for (int k = 0; k < WM; ++k) {
-                qv += Sb[k * GR_LANES + lane] * x[k];
+                qv += Sb[k * ROW_LANES + lane] * x[k];
                 GR_PACE(k);
             }
             double Db = wsum(wn * qv);
@@ -261,17 +246,17 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
             // D_n = A_n - U_n^T f_n
             Ub -= Db * fn;
             fb -= Db * un;
-            x[3 * GR_LANES + lane] = fb;
+            x[3 * ROW_LANES + lane] = fb;
             __syncthreads();
             // f_n = S_n U_n: Ubar += S_n fbar, Sbar += sym(fbar U^T); then P's adjoint and Mbar_n = P Sbar P
             double sf = 0.0, ss = 0.0;
 #pragma unroll
             for (int k = 0; k < WM; ++k) {
                 const double snk = sn[k];
-                sf += snk * x[3 * GR_LANES + k];
-                const double sb = Sb[k * GR_LANES + lane] + 0.5 * (fb * x[2 * GR_LANES + k] + un * x[3 * GR_LANES + k]);
+                sf += snk * x[3 * ROW_LANES + k];
+                const double sb = Sb[k * ROW_LANES + lane] + 0.5 * (fb * x[2 * ROW_LANES + k] + un * x[3 * ROW_LANES + k]);
                 ss += sb * snk;
-                Sb[k * GR_LANES + lane] = sb * (pn * x[GR_LANES + k]);
+                Sb[k * ROW_LANES + lane] = sb * (pn * x[ROW_LANES + k]);
             }
             Ub += sf;
             gc += dtn * (2.0 * ss + Gb * Gn);          // p_j Pbar_j dp/dc / p = dt (t_{n-1} - t_n)
@@ -279,8 +264,8 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
             gA += Db;
             gy += zb;
             // coefficient adjoints of this row's U, V
-            const double pUb = __shfl(Ub, partner, GR_LANES), pU = __shfl(un, partner, GR_LANES);
-            const double pV = __shfl(vn, partner, GR_LANES), pVb = __shfl(Vb, partner, GR_LANES);
+            const double pUb = __shfl(Ub, partner, ROW_LANES), pU = __shfl(un, partner, ROW_LANES);
+            const double pV = __shfl(vn, partner, ROW_LANES), pVb = __shfl(Vb, partner, ROW_LANES);
             if (q.kind == 1) {
                 ga += Ub;
             } else if (q.kind == 2 && q.half == 0) {
@@ -295,7 +280,7 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
             }
         }
     }
-    const double gcp = __shfl(gc, partner, GR_LANES);
+    const double gcp = __shfl(gc, partner, ROW_LANES);
     if (q.kind == 1) {
         g_real[(int64_t)b * lr + term] = ga;
         g_real[(int64_t)B * lr + (int64_t)b * lr + term] = gc;
@@ -319,7 +304,7 @@ __global__ __launch_bounds__(GR_LANES) __attribute__((amdgpu_waves_per_eu(1, 1))
 extern "C" {
 
 int64_t gf_grad_work(int64_t N, int W) {
-    if (N < 1 || W < 1 || W > GR_MAX_W) return 0;
+    if (N < 1 || W < 1 || W > ROW_MAX_W) return 0;
     return grad_work(N, W);
 }
 
@@ -334,8 +319,8 @@ int gf_loglike_grad(int B, int64_t N, int Jr, int Jc,
     if (B < 1 || N < 1 || Jr < 0 || Jc < 0 || W < 1)
         return gf_internal_error(-1, "gf_loglike_grad: bad shape (B=%d, N=%lld, Jr=%d, Jc=%d)", B, (long long)N,
                                  Jr, Jc);
-    if (W > GR_MAX_W)
-        return gf_internal_error(-3, "gf_loglike_grad: width W=%d exceeds the one-wave limit %d", W, GR_MAX_W);
+    if (W > ROW_MAX_W)
+        return gf_internal_error(-3, "gf_loglike_grad: width W=%d exceeds the one-wave limit %d", W, ROW_MAX_W);
     if (work_bs < grad_work(N, W))
         return gf_internal_error(-1, "gf_loglike_grad: work_bs=%lld < gf_grad_work(N, W)=%lld", (long long)work_bs,
                                  (long long)grad_work(N, W));
@@ -344,9 +329,9 @@ int gf_loglike_grad(int B, int64_t N, int Jr, int Jc,
         return gf_internal_error(-1, "gf_loglike_grad: null pointer");
     const int64_t K = grad_seg(N), nseg = (N + K - 1) / K;
     hipStream_t st = (hipStream_t)stream;
-    const int WM = grad_wm(W);
+    const int WM = row_wm(W);
 #define GR_LAUNCH(WMV)                                                                                          \
-    hipLaunchKernelGGL(k_grad<WMV>, dim3((unsigned)B), dim3(GR_LANES), 0, st, N, K, nseg, Jr, Jc, ar, cr, ac, bc, \
+    hipLaunchKernelGGL(k_grad<WMV>, dim3((unsigned)B), dim3(ROW_LANES), 0, st, N, K, nseg, Jr, Jc, ar, cr, ac, bc, \
                        cc, dc, diag_add, t, t_bs, diag, diag_bs, y, y_bs, work, work_bs, ll, g_real, g_comp,     \
                        g_diag, g_mean, info)
     if (WM == 16) GR_LAUNCH(16);

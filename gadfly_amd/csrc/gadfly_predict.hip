@@ -14,7 +14,8 @@
 //              mu*_m = lo_m + V*_m^T (e^{c (t*_m - last)} o H).
 // The state steps from observed stamp to observed stamp only and a query reads it without touching it: a query's value
 // does not depend on which other queries the call holds.  Generator rows are exact on every row, observed or queried
-// (theta = fl(d t), as celerite2), made in registers as in gadfly_solve.hip: nothing of size N W or M W exists.
+// (theta = fl(d t), as celerite2), made in registers by gadfly_solve.hip's gen_row (gf_rows.h): nothing of size N W or
+// M W exists.
 // Stamps, alpha and results live in lane i mod 64 and move 64 at a time: every load and store of the wave is one
 // contiguous 512-byte run, the next run of each input is in flight while the current one is consumed, and a lane reads
 // back only the results it wrote itself.  No workspace, no LDS, no atomics: results are bit-identical from run to run
@@ -27,53 +28,11 @@
 #include "../../include/gadfly_hip.h"
 #include "gf_internal.h"
 #include "gf_wave.h"
+#include "gf_rows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int PR_LANES = 64;
-constexpr int PR_MAX_W = 63;
-
-__device__ __forceinline__ double wsum(double x) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, PR_LANES);
-    return x;        // (a + b == b + a: every lane ends with the same bits)
-}
-
-// one state column of the celerite form: a real term (U = a, V = 1) or one half of a complex term
-struct Col {
-    double a, b, c, d;
-    int kind;        // 0 inactive lane, 1 real, 2 complex
-    int half;        // complex: 0 = cosine column, 1 = sine column
-};
-
-__device__ __forceinline__ Col load_col(int b, int lane, int Jr, int Jc, const double *ar, const double *cr,
-                                        const double *ac, const double *bc, const double *cc, const double *dc) {
-    const int lr = Jr > 0 ? Jr : 1, lc = Jc > 0 ? Jc : 1;
-    Col q{0.0, 0.0, 0.0, 0.0, 0, 0};
-    if (lane < Jr) {
-        q.kind = 1; q.a = ar[(int64_t)b * lr + lane]; q.c = cr[(int64_t)b * lr + lane];
-    } else if (lane < Jr + 2 * Jc) {
-        const int64_t o = (int64_t)b * lc + ((lane - Jr) >> 1);
-        q.kind = 2; q.half = (lane - Jr) & 1;
-        q.a = ac[o]; q.b = bc[o]; q.c = cc[o]; q.d = dc[o];
-    }
-    return q;
-}
-
-__device__ __forceinline__ void gen_row(const Col &q, double tn, double &u, double &v) {
-    if (q.kind == 2) {
-        double s, co;
-        sincos(q.d * tn, &s, &co);        // theta = fl(d t), as celerite2
-        if (q.half == 0) { u = fma(q.a, co, q.b * s); v = co; }
-        else             { u = fma(q.a, s, -(q.b * co)); v = s; }
-    } else if (q.kind == 1) {
-        u = q.a; v = 1.0;
-    } else {
-        u = 0.0; v = 0.0;
-    }
-}
 
 // x[0 .. n) read one element at a time, in steps of DIR = +1 or -1, by the whole wave: lane l holds x[64 blk + l], the
 // block after it in the direction of travel is already loaded
@@ -84,7 +43,7 @@ struct Run {
     double cur, nxt;
 
     __device__ __forceinline__ double block(int64_t b, int lane) const {
-        const int64_t i = b * PR_LANES + lane;
+        const int64_t i = b * ROW_LANES + lane;
         return (b >= 0 && i < n) ? x[i] : 0.0;
     }
     // (n >= 1, 0 <= first < n)
@@ -104,13 +63,7 @@ struct Run {
     }
 };
 
-__device__ __forceinline__ int64_t clamp_count(const int64_t *cnt, int b, int64_t full) {
-    if (!cnt) return full;
-    const int64_t v = cnt[b];
-    return v < 0 ? 0 : v > full ? full : v;
-}
-
-__global__ __launch_bounds__(PR_LANES) void k_predict_at(
+__global__ __launch_bounds__(ROW_LANES) void k_predict_at(
     int64_t N, int64_t M, int Jr, int Jc,
     const double *__restrict__ ar, const double *__restrict__ cr, const double *__restrict__ ac,
     const double *__restrict__ bc, const double *__restrict__ cc, const double *__restrict__ dc,
@@ -219,15 +172,15 @@ int gf_predict_batch_at(int B, int64_t N, int64_t M, int Jr, int Jc,
     if (B < 1 || N < 1 || M < 1 || Jr < 0 || Jc < 0 || W < 1)
         return gf_internal_error(-1, "gf_predict_batch_at: bad shape (B=%d, N=%lld, M=%lld, Jr=%d, Jc=%d)", B,
                                  (long long)N, (long long)M, Jr, Jc);
-    if (W > PR_MAX_W)
-        return gf_internal_error(-3, "gf_predict_batch_at: width W=%d exceeds the one-wave limit %d", W, PR_MAX_W);
+    if (W > ROW_MAX_W)
+        return gf_internal_error(-3, "gf_predict_batch_at: width W=%d exceeds the one-wave limit %d", W, ROW_MAX_W);
     if ((Jr && (!ar || !cr)) || (Jc && (!ac || !bc || !cc || !dc)) || !t || !ts || !alpha || !mu)
         return gf_internal_error(-1, "gf_predict_batch_at: null pointer");
     if (t_bs < 0 || ts_bs < 0 || (B > 1 && (alpha_bs < N || mu_bs < M)))
         return gf_internal_error(-1, "gf_predict_batch_at: bad stride (t_bs=%lld, ts_bs=%lld, alpha_bs=%lld < N=%lld "
                                  "or mu_bs=%lld < M=%lld)", (long long)t_bs, (long long)ts_bs, (long long)alpha_bs,
                                  (long long)N, (long long)mu_bs, (long long)M);
-    hipLaunchKernelGGL(k_predict_at, dim3((unsigned)B), dim3(PR_LANES), 0, (hipStream_t)stream, N, M, Jr, Jc, ar, cr,
+    hipLaunchKernelGGL(k_predict_at, dim3((unsigned)B), dim3(ROW_LANES), 0, (hipStream_t)stream, N, M, Jr, Jc, ar, cr,
                        ac, bc, cc, dc, t, t_bs, nobs, ts, ts_bs, nq, alpha, alpha_bs, mu, mu_bs);
     return gf_internal_check_launch("gf_predict_batch_at");
 }

@@ -27,20 +27,11 @@
 #include "../../include/gadfly_hip.h"
 #include "gf_internal.h"
 #include "gf_wave.h"
+#include "gf_rows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int SV_LANES = 64;
-constexpr int SV_MAX_W = 63;
-
-__host__ __device__ inline int solve_wm(int W) { return W <= 16 ? 16 : W <= 32 ? 32 : 64; }
-
-// doubles per checkpoint (S rows, G, W, D, z; a lane's row of S contiguous) and per staged row (W, U, P)
-__host__ __device__ inline int64_t solve_ck(int WM) { return (int64_t)(WM + 4) * SV_LANES; }
-__host__ __device__ inline int64_t solve_rs() { return (int64_t)3 * SV_LANES; }
-__host__ __device__ inline int64_t solve_n64(int64_t N) { return (N + 63) / 64 * 64; }
 
 // rows per segment that balance nseg checkpoints against K staged rows: the smallest K with 3 K^2 >= N (WM + 4)
 inline int64_t solve_seg(int64_t N, int WM) {
@@ -63,78 +54,8 @@ inline int64_t solve_work(int64_t N, int WM, int64_t K) {
     return nseg * solve_ck(WM) + K * solve_rs() + 2 * solve_n64(N);
 }
 
-#define SV_PACE(k) do { if (((k) & 7) == 7) __builtin_amdgcn_sched_barrier(0); } while (0)
-
-__device__ __forceinline__ double wsum(double x) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, SV_LANES);
-    return x;        // (a + b == b + a: every lane ends with the same bits)
-}
-
-// one state column of the celerite form: a real term (U = a, V = 1) or one half of a complex term
-struct Col {
-    double a, b, c, d;
-    int kind;        // 0 inactive lane, 1 real, 2 complex
-    int half;        // complex: 0 = cosine column, 1 = sine column
-};
-
-__device__ __forceinline__ Col load_col(int b, int lane, int Jr, int Jc, const double *ar, const double *cr,
-                                        const double *ac, const double *bc, const double *cc, const double *dc) {
-    const int lr = Jr > 0 ? Jr : 1, lc = Jc > 0 ? Jc : 1;
-    Col q{0.0, 0.0, 0.0, 0.0, 0, 0};
-    if (lane < Jr) {
-        q.kind = 1; q.a = ar[(int64_t)b * lr + lane]; q.c = cr[(int64_t)b * lr + lane];
-    } else if (lane < Jr + 2 * Jc) {
-        const int64_t o = (int64_t)b * lc + ((lane - Jr) >> 1);
-        q.kind = 2; q.half = (lane - Jr) & 1;
-        q.a = ac[o]; q.b = bc[o]; q.c = cc[o]; q.d = dc[o];
-    }
-    return q;
-}
-
-__device__ __forceinline__ void gen_row(const Col &q, double tn, double &u, double &v) {
-    if (q.kind == 2) {
-        double s, co;
-        sincos(q.d * tn, &s, &co);        // theta = fl(d t), as celerite2
-        if (q.half == 0) { u = fma(q.a, co, q.b * s); v = co; }
-        else             { u = fma(q.a, s, -(q.b * co)); v = s; }
-    } else if (q.kind == 1) {
-        u = q.a; v = 1.0;
-    } else {
-        u = 0.0; v = 0.0;
-    }
-}
-
-// one forward row: (S, G, w, D, z) of row n-1 in, of row n out; u, p of row n out
-template <int WM>
-__device__ __forceinline__ void fwd_row(double (&S)[WM], double &G, double &w, double &D, double &z,
-                                        const Col &q, double tprev, double tn, double An, double yn,
-                                        double *sh, int lane, double &u, double &p) {
-    double v;
-    gen_row(q, tn, u, v);
-    p = exp(q.c * (tprev - tn));
-    const double wi = D * w;
-    sh[lane] = w;
-    sh[SV_LANES + lane] = p;
-    sh[2 * SV_LANES + lane] = u;
-    __syncthreads();
-    double f = 0.0;
-#pragma unroll
-    for (int k = 0; k < WM; ++k) {
-        const double s = (p * sh[SV_LANES + k]) * fma(wi, sh[k], S[k]);
-        S[k] = s;
-        f = fma(s, sh[2 * SV_LANES + k], f);
-        SV_PACE(k);
-    }
-    G = p * fma(w, z, G);
-    const double uf = wsum(u * f), ug = wsum(u * G);
-    D = An - uf;
-    z = yn - ug;
-    w = (v - f) / D;
-}
-
 template <int WM, bool COMP>
-__global__ __launch_bounds__(SV_LANES) void k_solve(
+__global__ __launch_bounds__(ROW_LANES) void k_solve(
     int64_t N, int64_t K, int64_t nseg, int Jr, int Jc,
     const double *__restrict__ ar, const double *__restrict__ cr, const double *__restrict__ ac,
     const double *__restrict__ bc, const double *__restrict__ cc, const double *__restrict__ dc,
@@ -144,7 +65,7 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
     const double *__restrict__ t, int64_t t_bs, const double *__restrict__ dg, int64_t d_bs,
     const double *__restrict__ y, int64_t y_bs, double *__restrict__ work, int64_t work_bs,
     double *alpha, double *mu, double *mu_comp, double *__restrict__ ll, int32_t *__restrict__ info) {
-    __shared__ double sh[2][3 * SV_LANES];
+    __shared__ double sh[2][3 * ROW_LANES];
     const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
     const Col q = load_col(b, lane, Jr, Jc, ar, cr, ac, bc, cc, dc);
     t += (int64_t)b * t_bs;
@@ -169,13 +90,7 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
     #pragma unroll 1
     for (int64_t n = 0; n < N; ++n) {
         if (left == 0) {
-            double *c = ck + seg * solve_ck(WM);
-#pragma unroll
-            for (int k = 0; k < WM; ++k) c[lane * WM + k] = S[k];
-            c[(WM + 0) * SV_LANES + lane] = G;
-            c[(WM + 1) * SV_LANES + lane] = w;
-            c[(WM + 2) * SV_LANES + lane] = D;
-            c[(WM + 3) * SV_LANES + lane] = z;
+            ck_store<WM>(ck + seg * solve_ck(WM), lane, S, G, w, D, z);
             left = K;
             ++seg;
         }
@@ -196,7 +111,7 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
     if (bad) {
         const double nan = __builtin_nan("");
         if (lane == 0) { ll[b] = -INFINITY; info[b] = (int32_t)bad; }
-        for (int64_t i = lane; i < N; i += SV_LANES) {
+        for (int64_t i = lane; i < N; i += ROW_LANES) {
             if (alpha) alpha[i] = nan;
             if (mu) mu[i] = nan;
             if (COMP) mu_comp[i] = nan;
@@ -220,10 +135,10 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
         const double *c = ck + s * solve_ck(WM);
 #pragma unroll
         for (int k = 0; k < WM; ++k) S[k] = c[lane * WM + k];
-        G = c[(WM + 0) * SV_LANES + lane];
-        w = c[(WM + 1) * SV_LANES + lane];
-        D = c[(WM + 2) * SV_LANES + lane];
-        z = c[(WM + 3) * SV_LANES + lane];
+        G = c[(WM + 0) * ROW_LANES + lane];
+        w = c[(WM + 1) * ROW_LANES + lane];
+        D = c[(WM + 2) * ROW_LANES + lane];
+        z = c[(WM + 3) * ROW_LANES + lane];
         #pragma unroll 1
         for (int64_t n = n0; n < n1; ++n) {
             const double tn = t[n], tp = n ? t[n - 1] : tn;
@@ -231,13 +146,13 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
             fwd_row<WM>(S, G, w, D, z, q, tp, tn, An, y[n], sh[n & 1], lane, u, p);
             double *r = rows + (n - n0) * solve_rs();
             r[lane] = w;
-            r[SV_LANES + lane] = u;
-            r[2 * SV_LANES + lane] = p;
+            r[ROW_LANES + lane] = u;
+            r[2 * ROW_LANES + lane] = p;
         }
         #pragma unroll 1
         for (int64_t n = n1 - 1; n >= n0; --n) {
             const double *r = rows + (n - n0) * solve_rs();
-            const double wn = r[lane], un = r[SV_LANES + lane], pn = r[2 * SV_LANES + lane];
+            const double wn = r[lane], un = r[ROW_LANES + lane], pn = r[2 * ROW_LANES + lane];
             const int slot = (int)(n & 63);
             if (slot == 63 || n == N - 1) {
                 const int64_t i = (n - slot) + lane;
@@ -263,9 +178,7 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
             if (slot == 0) {
                 const int64_t i = n + lane;
                 if (i < N) {
-                    zw[i] = abuf;
-                    if (alpha) alpha[i] = abuf;
-                    if (mu) mu[i] = dg ? y[i] - dg[i] * abuf : y[i];
+                    stage_alpha(i, abuf, zw, alpha, mu, dg, y);
                     if (COMP) mu_comp[i] = ubuf;
                 }
             }
@@ -299,20 +212,18 @@ __global__ __launch_bounds__(SV_LANES) void k_solve(
     }
 }
 
-inline bool solve_shape_ok(int64_t N, int W) { return N >= 1 && W >= 1 && W <= SV_MAX_W; }
-
 }  // namespace
 
 extern "C" {
 
 int64_t gf_solve_batch_seg(int64_t N, int W) {
-    if (!solve_shape_ok(N, W)) return 0;
-    return solve_seg(N, solve_wm(W));
+    if (!row_shape_ok(N, W)) return 0;
+    return solve_seg(N, row_wm(W));
 }
 
 int64_t gf_solve_batch_work(int64_t N, int W, int64_t seg) {
-    if (!solve_shape_ok(N, W) || seg < 0) return 0;
-    const int WM = solve_wm(W);
+    if (!row_shape_ok(N, W) || seg < 0) return 0;
+    const int WM = row_wm(W);
     return solve_work(N, WM, solve_pick_seg(N, WM, seg));
 }
 
@@ -329,15 +240,15 @@ int gf_solve_batch(int B, int64_t N, int Jr, int Jc,
     if (B < 1 || N < 1 || Jr < 0 || Jc < 0 || W < 1 || Jr2 < 0 || Jc2 < 0 || seg < 0)
         return gf_internal_error(-1, "gf_solve_batch: bad shape (B=%d, N=%lld, Jr=%d, Jc=%d, Jr'=%d, Jc'=%d, seg=%lld)",
                                  B, (long long)N, Jr, Jc, Jr2, Jc2, (long long)seg);
-    if (W > SV_MAX_W)
-        return gf_internal_error(-3, "gf_solve_batch: width W=%d exceeds the one-wave limit %d", W, SV_MAX_W);
-    if (W2 > SV_MAX_W)
+    if (W > ROW_MAX_W)
+        return gf_internal_error(-3, "gf_solve_batch: width W=%d exceeds the one-wave limit %d", W, ROW_MAX_W);
+    if (W2 > ROW_MAX_W)
         return gf_internal_error(-3, "gf_solve_batch: component width W'=%d exceeds the one-wave limit %d", W2,
-                                 SV_MAX_W);
+                                 ROW_MAX_W);
     const bool comp = mu_comp != nullptr;
     if (comp != (W2 > 0))
         return gf_internal_error(-1, "gf_solve_batch: mu_comp and a component (W'=%d) go together", W2);
-    const int WM = solve_wm(W);
+    const int WM = row_wm(W);
     const int64_t K = solve_pick_seg(N, WM, seg), nseg = (N + K - 1) / K;
     if (work_bs < solve_work(N, WM, K))
         return gf_internal_error(-1, "gf_solve_batch: work_bs=%lld < gf_solve_batch_work(N, W, seg)=%lld",
@@ -347,7 +258,7 @@ int gf_solve_batch(int B, int64_t N, int Jr, int Jc,
         return gf_internal_error(-1, "gf_solve_batch: null pointer");
     hipStream_t st = (hipStream_t)stream;
 #define SV_LAUNCH(WMV, CV)                                                                                        \
-    hipLaunchKernelGGL((k_solve<WMV, CV>), dim3((unsigned)B), dim3(SV_LANES), 0, st, N, K, nseg, Jr, Jc, ar, cr,  \
+    hipLaunchKernelGGL((k_solve<WMV, CV>), dim3((unsigned)B), dim3(ROW_LANES), 0, st, N, K, nseg, Jr, Jc, ar, cr,  \
                        ac, bc, cc, dc, diag_add, Jr2, Jc2, ar2, cr2, ac2, bc2, cc2, dc2, t, t_bs, diag, diag_bs, \
                        y, y_bs, work, work_bs, alpha, mu, mu_comp, ll, info)
     if (comp) {

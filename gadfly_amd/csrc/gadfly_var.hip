@@ -20,8 +20,8 @@
 //            staging (W_n, U_n, P_n), Y comes back into the registers that held S, and the backward loop carries the
 //            vector H (alpha, mu) and the matrix Y: two LDS broadcast loops per row (q = Z W, then the rank-two
 //            update) with one wave sum between them; the queries between row n - 1 and row n follow row n's update.
-// S and Y are one register array: never live in the same loop.  fwd_row, Col, load_col, gen_row and wsum are
-// gadfly_solve.hip's, copied (as gadfly_predict.hip copies them): alpha, mu, log L and info have gf_solve_batch's bits.
+// S and Y are one register array: never live in the same loop.  fwd_row, Col, load_col, gen_row, wsum and the
+// checkpoint layout are the ones gadfly_solve.hip runs (gf_rows.h): alpha, mu, log L and info have gf_solve_batch's bits.
 // The recompute replays pass 1's arithmetic (explicitly fused operations, contraction off), Y travels through the
 // workspace unrounded: every output is bit-identical whatever the segment length and the batch.  No atomics.
 
@@ -32,20 +32,11 @@
 #include "../../include/gadfly_hip.h"
 #include "gf_internal.h"
 #include "gf_wave.h"
+#include "gf_rows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int SV_LANES = 64;
-constexpr int SV_MAX_W = 63;
-
-__host__ __device__ inline int solve_wm(int W) { return W <= 16 ? 16 : W <= 32 ? 32 : 64; }
-
-// doubles per checkpoint (S rows, G, W, D, z; a lane's row of S contiguous) and per staged row (W, U, P)
-__host__ __device__ inline int64_t solve_ck(int WM) { return (int64_t)(WM + 4) * SV_LANES; }
-__host__ __device__ inline int64_t solve_rs() { return (int64_t)3 * SV_LANES; }
-__host__ __device__ inline int64_t solve_n64(int64_t N) { return (N + 63) / 64 * 64; }
 
 inline int64_t solve_pick_seg(int64_t N, int W, int64_t seg) {
     if (seg == 0) return gf_solve_batch_seg(N, W);            // (one segment rule for both kernels)
@@ -56,77 +47,7 @@ inline int64_t solve_pick_seg(int64_t N, int W, int64_t seg) {
 // parked in while a segment is recomputed (a lane's row contiguous), R* of every query
 inline int64_t var_work(int64_t N, int WM, int64_t K, int64_t M) {
     const int64_t nseg = (N + K - 1) / K;
-    return nseg * solve_ck(WM) + K * solve_rs() + 2 * solve_n64(N) + (int64_t)WM * SV_LANES + M * SV_LANES;
-}
-
-#define SV_PACE(k) do { if (((k) & 7) == 7) __builtin_amdgcn_sched_barrier(0); } while (0)
-
-__device__ __forceinline__ double wsum(double x) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, SV_LANES);
-    return x;        // (a + b == b + a: every lane ends with the same bits)
-}
-
-// one state column of the celerite form: a real term (U = a, V = 1) or one half of a complex term
-struct Col {
-    double a, b, c, d;
-    int kind;        // 0 inactive lane, 1 real, 2 complex
-    int half;        // complex: 0 = cosine column, 1 = sine column
-};
-
-__device__ __forceinline__ Col load_col(int b, int lane, int Jr, int Jc, const double *ar, const double *cr,
-                                        const double *ac, const double *bc, const double *cc, const double *dc) {
-    const int lr = Jr > 0 ? Jr : 1, lc = Jc > 0 ? Jc : 1;
-    Col q{0.0, 0.0, 0.0, 0.0, 0, 0};
-    if (lane < Jr) {
-        q.kind = 1; q.a = ar[(int64_t)b * lr + lane]; q.c = cr[(int64_t)b * lr + lane];
-    } else if (lane < Jr + 2 * Jc) {
-        const int64_t o = (int64_t)b * lc + ((lane - Jr) >> 1);
-        q.kind = 2; q.half = (lane - Jr) & 1;
-        q.a = ac[o]; q.b = bc[o]; q.c = cc[o]; q.d = dc[o];
-    }
-    return q;
-}
-
-__device__ __forceinline__ void gen_row(const Col &q, double tn, double &u, double &v) {
-    if (q.kind == 2) {
-        double s, co;
-        sincos(q.d * tn, &s, &co);        // theta = fl(d t), as celerite2
-        if (q.half == 0) { u = fma(q.a, co, q.b * s); v = co; }
-        else             { u = fma(q.a, s, -(q.b * co)); v = s; }
-    } else if (q.kind == 1) {
-        u = q.a; v = 1.0;
-    } else {
-        u = 0.0; v = 0.0;
-    }
-}
-
-// one forward row: (S, G, w, D, z) of row n-1 in, of row n out; u, p of row n out
-template <int WM>
-__device__ __forceinline__ void fwd_row(double (&S)[WM], double &G, double &w, double &D, double &z,
-                                        const Col &q, double tprev, double tn, double An, double yn,
-                                        double *sh, int lane, double &u, double &p) {
-    double v;
-    gen_row(q, tn, u, v);
-    p = exp(q.c * (tprev - tn));
-    const double wi = D * w;
-    sh[lane] = w;
-    sh[SV_LANES + lane] = p;
-    sh[2 * SV_LANES + lane] = u;
-    __syncthreads();
-    double f = 0.0;
-#pragma unroll
-    for (int k = 0; k < WM; ++k) {
-        const double s = (p * sh[SV_LANES + k]) * fma(wi, sh[k], S[k]);
-        S[k] = s;
-        f = fma(s, sh[2 * SV_LANES + k], f);
-        SV_PACE(k);
-    }
-    G = p * fma(w, z, G);
-    const double uf = wsum(u * f), ug = wsum(u * G);
-    D = An - uf;
-    z = yn - ug;
-    w = (v - f) / D;
+    return nseg * solve_ck(WM) + K * solve_rs() + 2 * solve_n64(N) + (int64_t)WM * ROW_LANES + M * ROW_LANES;
 }
 
 // the virtual row at t* >= t_n behind row n, whose (S, w, D) come in and stay: its pivot d* (the filter variance at
@@ -141,27 +62,21 @@ __device__ __forceinline__ void query_row(const double (&S)[WM], double w, doubl
         const double p = exp(q.c * (tn - tq));
         const double wi = D * w;
         sh[lane] = w;
-        sh[SV_LANES + lane] = p;
-        sh[2 * SV_LANES + lane] = u;
+        sh[ROW_LANES + lane] = p;
+        sh[2 * ROW_LANES + lane] = u;
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < WM; ++k) {
-            f = fma((p * sh[SV_LANES + k]) * fma(wi, sh[k], S[k]), sh[2 * SV_LANES + k], f);
-            SV_PACE(k);
+            f = fma((p * sh[ROW_LANES + k]) * fma(wi, sh[k], S[k]), sh[2 * ROW_LANES + k], f);
+            ROW_PACE(k);
         }
     }
     d = k0 - wsum(u * f);
     R = v - f;
 }
 
-__device__ __forceinline__ int64_t clamp_count(const int64_t *cnt, int b, int64_t full) {
-    if (!cnt) return full;
-    const int64_t v = cnt[b];
-    return v < 0 ? 0 : v > full ? full : v;
-}
-
 template <int WM, bool QUERY>
-__global__ __launch_bounds__(SV_LANES) void k_var(
+__global__ __launch_bounds__(ROW_LANES) void k_var(
     int64_t N, int64_t M, int64_t K, int64_t nseg, int Jr, int Jc,
     const double *__restrict__ ar, const double *__restrict__ cr, const double *__restrict__ ac,
     const double *__restrict__ bc, const double *__restrict__ cc, const double *__restrict__ dc,
@@ -172,10 +87,10 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
     double *__restrict__ work, int64_t work_bs,
     double *alpha, double *mu, double *hdiag, double *var, double *var_at,
     double *__restrict__ ll, int32_t *__restrict__ info) {
-    __shared__ double sh[2][3 * SV_LANES];       // fwd_row's and the backward row's broadcasts (W, P, U), by row parity
+    __shared__ double sh[2][3 * ROW_LANES];       // fwd_row's and the backward row's broadcasts (W, P, U), by row parity
     // pass 1: a query's broadcasts (W, p*, U*), by query parity; pass 2: [n & 1][0 .. 64) r of row n and
     // [m & 1][64 .. 128) x of query m
-    __shared__ double sx[2][3 * SV_LANES];
+    __shared__ double sx[2][3 * ROW_LANES];
     const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
     const Col q = load_col(b, lane, Jr, Jc, ar, cr, ac, bc, cc, dc);
     t += (int64_t)b * t_bs;
@@ -190,7 +105,7 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
     double *zw = rows + K * solve_rs();            // z_n, then alpha_n
     double *Dw = zw + solve_n64(N);
     double *Yw = Dw + solve_n64(N);                // Y while a segment is recomputed
-    double *Rw = Yw + (int64_t)WM * SV_LANES;      // R* of every query
+    double *Rw = Yw + (int64_t)WM * ROW_LANES;      // R* of every query
     const double dadd = diag_add[b];
     // (M = 0 without QUERY, a fact the compiler is not told: the backward loop keeps its query loop in both
     // instances, where it runs no iteration.  Without that inner loop the register allocator does not split the live
@@ -213,7 +128,7 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
         while (m < Mq && (No == 0 || ts[m] < t[0])) {          // owned by no row: the prior
             double R, d;
             query_row<WM>(S, w, D, q, false, 0.0, ts[m], dadd, sx[m & 1], lane, R, d);
-            Rw[m * SV_LANES + lane] = R;
+            Rw[m * ROW_LANES + lane] = R;
             if (lane == (int)(m & 63)) var_at[m] = d;
             ++m;
         }
@@ -221,13 +136,7 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
     #pragma unroll 1
     for (int64_t n = 0; n < N; ++n) {
         if (left == 0) {
-            double *c = ck + seg * solve_ck(WM);
-#pragma unroll
-            for (int k = 0; k < WM; ++k) c[lane * WM + k] = S[k];
-            c[(WM + 0) * SV_LANES + lane] = G;
-            c[(WM + 1) * SV_LANES + lane] = w;
-            c[(WM + 2) * SV_LANES + lane] = D;
-            c[(WM + 3) * SV_LANES + lane] = z;
+            ck_store<WM>(ck + seg * solve_ck(WM), lane, S, G, w, D, z);
             left = K;
             ++seg;
         }
@@ -249,7 +158,7 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
             while (m < Mq && n < No && (n + 1 >= No || ts[m] < t[n + 1])) {      // t_n <= t* < t_{n+1}
                 double R, d;
                 query_row<WM>(S, w, D, q, true, tn, ts[m], dadd, sx[m & 1], lane, R, d);
-                Rw[m * SV_LANES + lane] = R;
+                Rw[m * ROW_LANES + lane] = R;
                 if (lane == (int)(m & 63)) var_at[m] = d;
                 ++m;
             }
@@ -258,14 +167,14 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
     if (bad) {
         const double nan = __builtin_nan("");
         if (lane == 0) { ll[b] = -INFINITY; info[b] = (int32_t)bad; }
-        for (int64_t i = lane; i < N; i += SV_LANES) {
+        for (int64_t i = lane; i < N; i += ROW_LANES) {
             if (alpha) alpha[i] = nan;
             if (mu) mu[i] = nan;
             if (hdiag) hdiag[i] = nan;
             if (var) var[i] = nan;
         }
         if (QUERY)
-            for (int64_t i = lane; i < Mq; i += SV_LANES) var_at[i] = nan;
+            for (int64_t i = lane; i < Mq; i += ROW_LANES) var_at[i] = nan;
         return;
     }
     if (lane == 0) {
@@ -294,10 +203,10 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
         __builtin_amdgcn_sched_barrier(0);       // (Y is out before S comes in: the two never share the registers)
 #pragma unroll
         for (int k = 0; k < WM; ++k) S[k] = c[lane * WM + k];
-        G = c[(WM + 0) * SV_LANES + lane];
-        w = c[(WM + 1) * SV_LANES + lane];
-        D = c[(WM + 2) * SV_LANES + lane];
-        z = c[(WM + 3) * SV_LANES + lane];
+        G = c[(WM + 0) * ROW_LANES + lane];
+        w = c[(WM + 1) * ROW_LANES + lane];
+        D = c[(WM + 2) * ROW_LANES + lane];
+        z = c[(WM + 3) * ROW_LANES + lane];
         #pragma unroll 1
         for (int64_t n = n0; n < n1; ++n) {
             const double tn = t[n], tp = n ? t[n - 1] : tn;
@@ -305,8 +214,8 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
             fwd_row<WM>(S, G, w, D, z, q, tp, tn, An, y[n], sh[n & 1], lane, u, p);
             double *r = rows + (n - n0) * solve_rs();
             r[lane] = w;
-            r[SV_LANES + lane] = u;
-            r[2 * SV_LANES + lane] = p;
+            r[ROW_LANES + lane] = u;
+            r[2 * ROW_LANES + lane] = p;
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -315,7 +224,7 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
         #pragma unroll 1
         for (int64_t n = n1 - 1; n >= n0; --n) {
             const double *r = rows + (n - n0) * solve_rs();
-            const double wn = r[lane], un = r[SV_LANES + lane], pn = r[2 * SV_LANES + lane];
+            const double wn = r[lane], un = r[ROW_LANES + lane], pn = r[2 * ROW_LANES + lane];
             const int slot = (int)(n & 63);
             if (slot == 63 || n == N - 1) {
                 const int64_t i = (n - slot) + lane;
@@ -328,16 +237,16 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
             // Z = P_{n+1} Y P_{n+1} in place, q = Z W_n
             double *bw = sh[n & 1], *br = sx[n & 1];
             bw[lane] = wn;
-            bw[SV_LANES + lane] = pnext;
-            bw[2 * SV_LANES + lane] = un;
+            bw[ROW_LANES + lane] = pnext;
+            bw[2 * ROW_LANES + lane] = un;
             __syncthreads();
             double qv = 0.0;
 #pragma unroll
             for (int k = 0; k < WM; ++k) {
-                const double zk = (pnext * bw[SV_LANES + k]) * Y[k];
+                const double zk = (pnext * bw[ROW_LANES + k]) * Y[k];
                 Y[k] = zk;
                 qv = fma(zk, bw[k], qv);
-                SV_PACE(k);
+                ROW_PACE(k);
             }
             const double h = 1.0 / Dn + wsum(wn * qv);
             const double rv = fma(0.5 * h, un, -qv);
@@ -345,8 +254,8 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
             __syncthreads();
 #pragma unroll
             for (int k = 0; k < WM; ++k) {
-                Y[k] = fma(un, br[k], fma(rv, bw[2 * SV_LANES + k], Y[k]));
-                SV_PACE(k);
+                Y[k] = fma(un, br[k], fma(rv, bw[2 * ROW_LANES + k], Y[k]));
+                ROW_PACE(k);
             }
             unext = un; pnext = pn; anext = a;
             if (lane == slot) { abuf = a; hbuf = h; }
@@ -355,15 +264,15 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
                 const double tn = t[n];
                 #pragma unroll 1
                 while (mq >= 0 && (n == 0 || ts[mq] >= t[n - 1])) {
-                    double *bx = sx[mq & 1] + SV_LANES;
-                    const double x = exp(q.c * (ts[mq] - tn)) * Rw[mq * SV_LANES + lane];
+                    double *bx = sx[mq & 1] + ROW_LANES;
+                    const double x = exp(q.c * (ts[mq] - tn)) * Rw[mq * ROW_LANES + lane];
                     bx[lane] = x;
                     __syncthreads();
                     double acc = 0.0;
 #pragma unroll
                     for (int k = 0; k < WM; ++k) {
                         acc = fma(Y[k], bx[k], acc);
-                        SV_PACE(k);
+                        ROW_PACE(k);
                     }
                     const double quadq = wsum(x * acc);
                     if (lane == (int)(mq & 63)) var_at[mq] = var_at[mq] - quadq;     // (d*: this lane's own write)
@@ -373,9 +282,7 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
             if (slot == 0) {
                 const int64_t i = n + lane;
                 if (i < N) {
-                    zw[i] = abuf;
-                    if (alpha) alpha[i] = abuf;
-                    if (mu) mu[i] = dg ? y[i] - dg[i] * abuf : y[i];
+                    stage_alpha(i, abuf, zw, alpha, mu, dg, y);
                     if (hdiag) hdiag[i] = hbuf;
                     if (var) {
                         const double di = dg ? dg[i] : 0.0;
@@ -387,15 +294,13 @@ __global__ __launch_bounds__(SV_LANES) void k_var(
     }
 }
 
-inline bool var_shape_ok(int64_t N, int W) { return N >= 1 && W >= 1 && W <= SV_MAX_W; }
-
 }  // namespace
 
 extern "C" {
 
 int64_t gf_var_batch_work(int64_t N, int W, int64_t M, int64_t seg) {
-    if (!var_shape_ok(N, W) || M < 0 || seg < 0) return 0;
-    const int WM = solve_wm(W);
+    if (!row_shape_ok(N, W) || M < 0 || seg < 0) return 0;
+    const int WM = row_wm(W);
     return var_work(N, WM, solve_pick_seg(N, W, seg), M);
 }
 
@@ -412,13 +317,13 @@ int gf_var_batch(int B, int64_t N, int Jr, int Jc,
     if (B < 1 || N < 1 || M < 0 || Jr < 0 || Jc < 0 || W < 1 || seg < 0)
         return gf_internal_error(-1, "gf_var_batch: bad shape (B=%d, N=%lld, M=%lld, Jr=%d, Jc=%d, seg=%lld)", B,
                                  (long long)N, (long long)M, Jr, Jc, (long long)seg);
-    if (W > SV_MAX_W)
-        return gf_internal_error(-3, "gf_var_batch: width W=%d exceeds the one-wave limit %d", W, SV_MAX_W);
+    if (W > ROW_MAX_W)
+        return gf_internal_error(-3, "gf_var_batch: width W=%d exceeds the one-wave limit %d", W, ROW_MAX_W);
     if ((M > 0) != (var_at != nullptr) || (M > 0 && !ts))
         return gf_internal_error(-1, "gf_var_batch: ts and var_at go with M=%lld > 0 queries", (long long)M);
     if (t_bs < 0 || diag_bs < 0 || y_bs < 0 || ts_bs < 0)
         return gf_internal_error(-1, "gf_var_batch: negative stride");
-    const int WM = solve_wm(W);
+    const int WM = row_wm(W);
     const int64_t K = solve_pick_seg(N, W, seg), nseg = (N + K - 1) / K;
     if (work_bs < var_work(N, WM, K, M))
         return gf_internal_error(-1, "gf_var_batch: work_bs=%lld < gf_var_batch_work(N, W, M, seg)=%lld",
@@ -427,7 +332,7 @@ int gf_var_batch(int B, int64_t N, int Jr, int Jc,
         return gf_internal_error(-1, "gf_var_batch: null pointer");
     hipStream_t st = (hipStream_t)stream;
 #define VR_LAUNCH(WMV, QV)                                                                                         \
-    hipLaunchKernelGGL((k_var<WMV, QV>), dim3((unsigned)B), dim3(SV_LANES), 0, st, N, M, K, nseg, Jr, Jc, ar, cr,  \
+    hipLaunchKernelGGL((k_var<WMV, QV>), dim3((unsigned)B), dim3(ROW_LANES), 0, st, N, M, K, nseg, Jr, Jc, ar, cr,  \
                        ac, bc, cc, dc, diag_add, t, t_bs, diag, diag_bs, y, y_bs, ts, ts_bs, nobs, nq, work,       \
                        work_bs, alpha, mu, hdiag, var, var_at, ll, info)
     if (M > 0) {
