@@ -408,37 +408,62 @@ class BatchedLogLikelihood:
                              "include_mean=False and add the mean at t yourself")
         return m[:, :1]
 
-    def _predict_at(self, pack_or_kernels, kernel, include_mean, return_alpha, t):
-        """:meth:`predict_device` with ``t=``: alpha as without it, then the two sums between the sorted axes."""
-        from .predict import check_width, component_pack, predict_at, solve_batch
-        eng = self.engine
-        torch = eng.torch
-        Jr0, Jc0 = eng._struct0
-        check_width(Jr0 + 2 * Jc0)
-        ts, nq, as_list = self._query_times(t)
-        mean = self._mean_per_problem() if include_mean and np.any(self._mean != 0.0) else None
-        component = None if kernel is None else component_pack(kernel, self.B)
-        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
-        res = solve_batch(eng, Jr, Jc, real, comp, diag_add, None, self.predict_workspace_bytes,
-                          want_alpha=True, want_mu=False)
+    def _record_predict(self, res):
+        """The ``last_predict_*`` attributes from the result of a solve_batch / variance_batch call."""
+        #: (workspace bytes of a group, number of groups, problems per group) and the HIP events of the last call
         self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
         self._predict_events, self._predict_at_events = res["events"], []
         self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
         self.last_predict_info = res["info"]
+
+    def _add_mean(self, x, include_mean):
+        """Add the mean of construction to a (B, N) device tensor at the observed rows, in place."""
+        if include_mean and np.any(self._mean != 0.0):
+            # (whatever y - mean broadcast at construction: a scalar, (N,), (B, 1) or (B, N); ragged: one per problem)
+            eng = self.engine
+            m = self._mean[:, None] if self.rows is not None else self._mean
+            m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
+            x += eng.torch.as_tensor(m, dtype=eng.torch.float64, device=eng.device)
+
+    def _query_mean(self, include_mean):
+        """The mean a call with ``t=`` adds (:meth:`_mean_per_problem`), or None: looked at before anything is
+        enqueued, as it may raise."""
+        return self._mean_per_problem() if include_mean and np.any(self._mean != 0.0) else None
+
+    def _mean_at(self, cf, alpha, ts, nq, mean):
+        """The second launch of a call with ``t=``: K(t*, t) alpha of the coefficients ``cf`` at the query stamps,
+        (B, M) on the device, with the per-problem ``mean`` of :meth:`_query_mean` added."""
+        from .predict import predict_at
+        eng = self.engine
+        at = predict_at(eng, *cf, alpha, ts, nobs=self.rows, nq=nq)
+        self._predict_at_events = at["events"]
+        mu = at["mu"]
+        if mean is not None:
+            mu += eng.torch.as_tensor(np.array(mean), dtype=eng.torch.float64, device=eng.device)
+        return mu
+
+    def _empty_queries(self):
+        eng = self.engine
+        return eng.torch.empty((self.B, 0), dtype=eng.torch.float64, device=eng.device)
+
+    def _predict_at(self, pack_or_kernels, kernel, include_mean, return_alpha, t):
+        """:meth:`predict_device` with ``t=``: alpha as without it, then the two sums between the sorted axes."""
+        from .predict import check_width, component_pack, solve_batch
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        ts, nq, as_list = self._query_times(t)
+        mean = self._query_mean(include_mean)
+        component = None if kernel is None else component_pack(kernel, self.B)
+        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
+        res = solve_batch(eng, Jr, Jc, real, comp, diag_add, None, self.predict_workspace_bytes,
+                          want_alpha=True, want_mu=False)
+        self._record_predict(res)
         if ts.shape[1] == 0:
-            mu = torch.empty((self.B, 0), dtype=torch.float64, device=eng.device)
+            mu = self._empty_queries()
         else:
-            cf = (Jr, Jc, real, comp) if component is None else component
-            at = predict_at(eng, *cf, res["alpha"], ts, nobs=self.rows, nq=nq)
-            self._predict_at_events = at["events"]
-            mu = at["mu"]
-            if mean is not None:
-                mu += torch.as_tensor(np.array(mean), dtype=torch.float64, device=eng.device)
-        if as_list:
-            mu = [mu[b, :int(n)] for b, n in enumerate(nq)]
-        alpha = res["alpha"]
-        if self.rows is not None:
-            alpha = [alpha[b, :int(n)] for b, n in enumerate(self.rows)]
+            mu = self._mean_at((Jr, Jc, real, comp) if component is None else component, res["alpha"], ts, nq, mean)
+        mu, alpha = self._cut_queries(mu, nq, as_list), self._cut_rows(res["alpha"])
         return (mu, alpha) if return_alpha else mu
 
     def _variance_call(self, pack_or_kernels, ts=None, nq=None, **want):
@@ -451,10 +476,7 @@ class BatchedLogLikelihood:
         Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
         res = variance_batch(eng, Jr, Jc, real, comp, diag_add, ts=ts, nobs=self.rows, nq=nq,
                              cap_bytes=self.predict_workspace_bytes, **want)
-        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
-        self._predict_events, self._predict_at_events = res["events"], []
-        self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
-        self.last_predict_info = res["info"]
+        self._record_predict(res)
         return (Jr, Jc, real, comp), res
 
     def _cut_rows(self, x):
@@ -463,42 +485,33 @@ class BatchedLogLikelihood:
             return x
         return [x[b, :int(n)] for b, n in enumerate(self.rows)]
 
+    @staticmethod
+    def _cut_queries(x, nq, as_list):
+        """(B, M) -> the list of each problem's own queries where ``t=`` was a list."""
+        return [x[b, :int(n)] for b, n in enumerate(nq)] if as_list else x
+
     def _predict_var(self, pack_or_kernels, kernel, include_mean, return_alpha, t):
         """:meth:`predict_device` with ``return_var=True``."""
         if kernel is not None:
             raise NotImplementedError(
                 "return_var with kernel=component is not supported: the component's conditional variance "
                 "K'(0) - K' Sigma^-1 K'^T does not reduce to the inverse diagonal of Sigma")
-        eng = self.engine
-        torch = eng.torch
         if t is None:
             _, res = self._variance_call(pack_or_kernels, want_alpha=return_alpha, want_mu=True, want_h=False,
                                          want_var=True)
-            mu = res["mu"]
-            if include_mean and np.any(self._mean != 0.0):
-                m = self._mean[:, None] if self.rows is not None else self._mean
-                m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
-                mu += torch.as_tensor(m, dtype=torch.float64, device=eng.device)
-            mu, var, alpha = self._cut_rows(mu), self._cut_rows(res["var"]), self._cut_rows(res["alpha"])
+            self._add_mean(res["mu"], include_mean)
+            mu, var, alpha = self._cut_rows(res["mu"]), self._cut_rows(res["var"]), self._cut_rows(res["alpha"])
             return (mu, var, alpha) if return_alpha else (mu, var)
-        from .predict import predict_at
         ts, nq, as_list = self._query_times(t)
-        mean = self._mean_per_problem() if include_mean and np.any(self._mean != 0.0) else None
+        mean = self._query_mean(include_mean)
         M = ts.shape[1]
         cf, res = self._variance_call(pack_or_kernels, ts=ts if M else None, nq=nq if M else None, want_alpha=True,
                                       want_mu=False, want_h=False, want_var=False)
         if M == 0:
-            mu = torch.empty((self.B, 0), dtype=torch.float64, device=eng.device)
-            var = torch.empty((self.B, 0), dtype=torch.float64, device=eng.device)
+            mu, var = self._empty_queries(), self._empty_queries()
         else:
-            at = predict_at(eng, *cf, res["alpha"], ts, nobs=self.rows, nq=nq)
-            self._predict_at_events = at["events"]
-            mu, var = at["mu"], res["var_at"]
-            if mean is not None:
-                mu += torch.as_tensor(np.array(mean), dtype=torch.float64, device=eng.device)
-        if as_list:
-            mu = [mu[b, :int(n)] for b, n in enumerate(nq)]
-            var = [var[b, :int(n)] for b, n in enumerate(nq)]
+            mu, var = self._mean_at(cf, res["alpha"], ts, nq, mean), res["var_at"]
+        mu, var = self._cut_queries(mu, nq, as_list), self._cut_queries(var, nq, as_list)
         alpha = self._cut_rows(res["alpha"])
         return (mu, var, alpha) if return_alpha else (mu, var)
 
@@ -516,13 +529,9 @@ class BatchedLogLikelihood:
         tensors (B, N), lists for a ragged batch.  (y_n - mean_n)^2 / var_n flags outliers.  No host synchronisation."""
         _, res = self._variance_call(pack_or_kernels, want_alpha=True, want_mu=False, want_h=True, want_var=False)
         eng = self.engine
-        torch = eng.torch
         var = 1.0 / res["hdiag"]
         mean = eng.y.reshape(-1, eng.N) - res["alpha"] * var
-        if include_mean and np.any(self._mean != 0.0):
-            m = self._mean[:, None] if self.rows is not None else self._mean
-            m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
-            mean += torch.as_tensor(m, dtype=torch.float64, device=eng.device)
+        self._add_mean(mean, include_mean)
         return self._cut_rows(mean), self._cut_rows(var)
 
     @staticmethod
@@ -581,23 +590,10 @@ class BatchedLogLikelihood:
         Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
         res = solve_batch(eng, Jr, Jc, real, comp, diag_add, component, self.predict_workspace_bytes,
                           want_alpha=return_alpha, want_mu=component is None)
-        #: (workspace bytes of a group, number of groups, problems per group) and the HIP events of the last call
-        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
-        self._predict_events, self._predict_at_events = res["events"], []
-        self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr
-        self.last_predict_info = res["info"]
+        self._record_predict(res)
         mu = res["mu"] if component is None else res["mu_comp"]
-        torch = eng.torch
-        if include_mean and np.any(self._mean != 0.0):
-            # (whatever y - mean broadcast at construction: a scalar, (N,), (B, 1) or (B, N); ragged: one per problem)
-            m = self._mean[:, None] if self.rows is not None else self._mean
-            m = np.array(np.broadcast_to(m, np.broadcast_shapes(np.shape(m), (1, 1))))
-            mu += torch.as_tensor(m, dtype=torch.float64, device=eng.device)
-        if self.rows is not None:
-            mu = [mu[b, :int(n)] for b, n in enumerate(self.rows)]
-            alpha = None if res["alpha"] is None else [res["alpha"][b, :int(n)] for b, n in enumerate(self.rows)]
-        else:
-            alpha = res["alpha"]
+        self._add_mean(mu, include_mean)
+        mu, alpha = self._cut_rows(mu), self._cut_rows(res["alpha"])
         return (mu, alpha) if return_alpha else mu
 
     @property
@@ -622,11 +618,7 @@ class BatchedLogLikelihood:
         """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch or a list of query times)."""
         out = self.predict_device(pack_or_kernels, kernel=kernel, include_mean=include_mean,
                                   return_alpha=return_alpha, t=t, return_var=return_var)
-
-        def host(x):
-            return [v.cpu().numpy() for v in x] if isinstance(x, list) else x.cpu().numpy()
-
-        return tuple(host(x) for x in out) if (return_alpha or return_var) else host(out)
+        return tuple(self._to_host(x) for x in out) if (return_alpha or return_var) else self._to_host(out)
 
     def evaluate_device(self, pack=None):
         """Enqueue one evaluation per problem; returns the (B,) device tensor (no host sync).

@@ -2,9 +2,8 @@
 Gradients of batched log-likelihoods.
 
 The device computes d log L / d (celerite coefficients) for B problems at once (``gf_loglike_grad``, the
-reverse-mode counterpart of celerite2's ``driver.factor_rev`` / ``solve_lower_rev``); this module
-  * sizes its workspace and splits a batch into groups under a byte cap (a problem's result does not depend on
-    the group it lands in);
+reverse-mode counterpart of celerite2's ``driver.factor_rev`` / ``solve_lower_rev``), in groups under a byte cap
+(:mod:`gadfly_amd.rowcall`); this module
   * restates :func:`gadfly_amd.batch.sho_coefficient_pack` in torch (float64 / complex128), so that the chain
     rule from the coefficient adjoints to (S0, w0, Q) -- exposure integration, the diagonal shift and
     ``diag_add``'s dependence on the amplitudes included -- is ONE autograd vector-Jacobian product, with no
@@ -15,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rowcall import GroupedCall, check_pack_batch, group_plan
 
 __all__ = ["sho_coefficient_pack_torch", "check_width", "check_pack_batch", "workspace_plan",
            "coefficient_gradients", "parameter_vjp", "LogLikelihood", "DEFAULT_WORKSPACE_BYTES"]
@@ -69,25 +69,11 @@ def check_width(W):
             f"has W = {W}")
 
 
-def check_pack_batch(B, Jr, Jc, real, comp, diag_add):
-    """ValueError unless a stacked coefficient pack holds exactly B problems of the structure (Jr, Jc) in the
-    layout the device reads (real (2, B, max(Jr, 1)), comp (4, B, max(Jc, 1)), diag_add (B,)): gf_loglike_grad
-    indexes every array by the problem, so a shorter pack must never reach it."""
-    want = ((2, B, max(Jr, 1)), (4, B, max(Jc, 1)), (B,))
-    got = tuple(tuple(np.shape(x)) for x in (real, comp, diag_add))
-    if got != want:
-        raise ValueError(f"coefficient pack of shapes {got} does not match the batch of {B} problems "
-                         f"(expected {want})")
-
-
 def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES):
     """(doubles per problem, problems per group, number of groups) of a gradient call."""
     check_width(W)
-    per = int(_lib.load().gf_grad_work(int(N), int(W)))
-    if per <= 0:
-        raise ValueError(f"no gradient workspace for N = {N}, W = {W}")
-    group = int(max(1, min(B, int(cap_bytes) // (8 * per))))
-    return per, group, (B + group - 1) // group
+    return group_plan(_lib.load().gf_grad_work(int(N), int(W)), B, cap_bytes,
+                      f"no gradient workspace for N = {N}, W = {W}")
 
 
 def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES):
@@ -101,52 +87,30 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
         raise ValueError("coefficient pack does not match the batch structure")
     B, N = engine.B, engine.N
     check_pack_batch(B, Jr, Jc, real, comp, diag_add)
-    per, group, ngroups = workspace_plan(N, W, B, cap_bytes)
-    lib, p = engine.lib, _lib.ptr
-    dev = engine.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        work = torch.empty((group * per,), **f64)
+    plan = workspace_plan(N, W, B, cap_bytes)
+    f64 = dict(dtype=torch.float64, device=engine.device)
+    with torch.cuda.device(engine.device):
+        rc = GroupedCall(engine, "gf_loglike_grad", plan, (real, comp, diag_add))
         ll = torch.empty((B,), **f64)
-        info = torch.zeros((B,), dtype=torch.int32, device=dev)
+        info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
         g_diag = torch.empty((B,), **f64)
         g_mean = torch.empty((B,), **f64)
         lr, lc = max(Jr, 1), max(Jc, 1)
         g_real = np.zeros((2, B, lr))
         g_comp = np.zeros((4, B, lc))
-        real = np.ascontiguousarray(real, dtype=np.float64)
-        comp = np.ascontiguousarray(comp, dtype=np.float64)
-        diag_add = np.ascontiguousarray(diag_add, dtype=np.float64)
-        t, y, dg = engine.t, engine.y, engine.diag
-        tbs, ybs = engine._bs(t), engine._bs(y)
-        dbs = 0 if dg is None else engine._bs(dg)
-        events = []
-        for b0 in range(0, B, group):
-            nb = min(group, B - b0)
-            cr_ = torch.as_tensor(np.ascontiguousarray(real[:, b0:b0 + nb]), **f64)
-            cc_ = torch.as_tensor(np.ascontiguousarray(comp[:, b0:b0 + nb]), **f64)
-            da = torch.as_tensor(diag_add[b0:b0 + nb], **f64)
-            gr = torch.zeros((2, nb, lr), **f64)
-            gc = torch.zeros((4, nb, lc), **f64)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            st = lib.gf_loglike_grad(
-                nb, N, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]), p(da),
-                t.data_ptr() + 8 * b0 * tbs, tbs,
-                None if dg is None else dg.data_ptr() + 8 * b0 * dbs, dbs,
-                y.data_ptr() + 8 * b0 * ybs, ybs, p(work), per,
-                ll.data_ptr() + 8 * b0, p(gr), p(gc), g_diag.data_ptr() + 8 * b0, g_mean.data_ptr() + 8 * b0,
-                info.data_ptr() + 4 * b0, stream)
-            _lib.check(st, "gf_loglike_grad")
-            e1.record()
-            events.append((e0, e1))
-            g_real[:, b0:b0 + nb] = gr.cpu().numpy()
-            g_comp[:, b0:b0 + nb] = gc.cpu().numpy()
+
+        def group(g):
+            gr = torch.zeros((2, g.nb, lr), **f64)
+            gc = torch.zeros((4, g.nb, lc), **f64)
+            g.launch(g.nb, N, Jr, Jc, *g.coef[0], *g.data, *g.work, g.at(ll), gr.data_ptr(), gc.data_ptr(),
+                     g.at(g_diag), g.at(g_mean), g.at(info), g.stream)
+            g_real[:, g.b0:g.b0 + g.nb] = gr.cpu().numpy()
+            g_comp[:, g.b0:g.b0 + g.nb] = gc.cpu().numpy()
+
+        events = rc.run(group)
         return dict(ll=ll.cpu().numpy(), real=g_real[:, :, :Jr], comp=g_comp[:, :, :Jc],
                     diag_add=g_diag.cpu().numpy(), mean=g_mean.cpu().numpy(), info=info.cpu().numpy(),
-                    workspace_bytes=8 * per * group, groups=ngroups, group_size=group,
-                    device_ms=sum(a.elapsed_time(b) for a, b in events))
+                    device_ms=sum(a.elapsed_time(b) for a, b in events), **rc.plan)
 
 
 #: terms of each kind (overdamped, underdamped) padded to a multiple of this in the chain rule's layout

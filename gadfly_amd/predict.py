@@ -3,18 +3,17 @@ Conditional means of batched problems.
 
 The device computes alpha = K^-1 (y - mean), mu = y - diag alpha and, optionally, the share of the data one part of
 the kernel explains for B problems at once (``gf_solve_batch``: a checkpointed forward sweep and the upper solve
-backwards, no stored factor); this module sizes its workspace, splits a batch into groups under a byte cap (a
-problem's result does not depend on the group it lands in) and stacks the component's coefficients.
-``gf_predict_batch_at`` then carries alpha to new times t* (DESIGN.md 3.11): the two sorted-axis sums of the full
-kernel or of a component, no workspace.  ``gf_var_batch`` is ``gf_solve_batch`` with one more backward
-recurrence: the inverse diagonal h, the conditional variances at the observed times and at new ones, grouped the same
-way under the same cap with the staged queries counted.
+backwards, no stored factor); this module stacks the component's coefficients.  ``gf_predict_batch_at`` then carries
+alpha to new times t* (DESIGN.md 3.11): the two sorted-axis sums of the full kernel or of a component, no workspace.
+``gf_var_batch`` is ``gf_solve_batch`` with one more backward recurrence: the inverse diagonal h, the
+conditional variances at the observed times and at new ones, the staged queries counted in its workspace.  The groups
+under the byte cap, the query axes and the launches are :mod:`gadfly_amd.rowcall`'s.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .grad import check_pack_batch
+from .rowcall import GroupedCall, check_pack_batch, group_plan, query_axes
 
 __all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "predict_at", "variance_plan",
            "variance_batch", "DEFAULT_WORKSPACE_BYTES"]
@@ -34,11 +33,8 @@ def check_width(W, what="this kernel"):
 def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0):
     """(doubles per problem, problems per group, number of groups) of a gf_solve_batch call."""
     check_width(W)
-    per = int(_lib.load().gf_solve_batch_work(int(N), int(W), int(seg)))
-    if per <= 0:
-        raise ValueError(f"no solve workspace for N = {N}, W = {W}, seg = {seg}")
-    group = int(max(1, min(B, int(cap_bytes) // (8 * per))))
-    return per, group, (B + group - 1) // group
+    return group_plan(_lib.load().gf_solve_batch_work(int(N), int(W), int(seg)), B, cap_bytes,
+                      f"no solve workspace for N = {N}, W = {W}, seg = {seg}")
 
 
 def component_pack(kernel, B):
@@ -80,54 +76,21 @@ def solve_batch(engine, Jr, Jc, real, comp, diag_add, component=None, cap_bytes=
         raise ValueError("coefficient pack does not match the batch structure")
     B, N = engine.B, engine.N
     check_pack_batch(B, Jr, Jc, real, comp, diag_add)
-    per, group, ngroups = workspace_plan(N, W, B, cap_bytes, seg)
-    lib, p = engine.lib, _lib.ptr
-    dev = engine.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    jr2 = jc2 = 0
-    if component is not None:
-        jr2, jc2, real2, comp2 = component
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        work = torch.empty((group * per,), **f64)
+    plan = workspace_plan(N, W, B, cap_bytes, seg)
+    jr2, jc2, real2, comp2 = (0, 0, None, None) if component is None else component
+    f64 = dict(dtype=torch.float64, device=engine.device)
+    with torch.cuda.device(engine.device):
+        rc = GroupedCall(engine, "gf_solve_batch", plan, (real, comp, diag_add),
+                         None if component is None else (real2, comp2))
         ll = torch.empty((B,), **f64)
-        info = torch.zeros((B,), dtype=torch.int32, device=dev)
+        info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
         alpha = torch.empty((B, N), **f64) if want_alpha else None
         mu = torch.empty((B, N), **f64) if want_mu else None
         mu_comp = torch.empty((B, N), **f64) if component is not None else None
-        real = np.ascontiguousarray(real, dtype=np.float64)
-        comp = np.ascontiguousarray(comp, dtype=np.float64)
-        diag_add = np.ascontiguousarray(diag_add, dtype=np.float64)
-        t, y, dg = engine.t, engine.y, engine.diag
-        tbs, ybs = engine._bs(t), engine._bs(y)
-        dbs = 0 if dg is None else engine._bs(dg)
-        at = lambda x, off: None if x is None else x.data_ptr() + off      # noqa: E731
-        events = []
-        for b0 in range(0, B, group):
-            nb = min(group, B - b0)
-            cr_ = torch.as_tensor(np.ascontiguousarray(real[:, b0:b0 + nb]), **f64)
-            cc_ = torch.as_tensor(np.ascontiguousarray(comp[:, b0:b0 + nb]), **f64)
-            da = torch.as_tensor(diag_add[b0:b0 + nb], **f64)
-            c2 = [None] * 6
-            if component is not None:
-                r2_ = torch.as_tensor(np.ascontiguousarray(real2[:, b0:b0 + nb]), **f64)
-                c2_ = torch.as_tensor(np.ascontiguousarray(comp2[:, b0:b0 + nb]), **f64)
-                c2 = [p(r2_[0]), p(r2_[1]), p(c2_[0]), p(c2_[1]), p(c2_[2]), p(c2_[3])]
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            st = lib.gf_solve_batch(
-                nb, N, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]), p(da),
-                jr2, jc2, *c2,
-                t.data_ptr() + 8 * b0 * tbs, tbs,
-                None if dg is None else dg.data_ptr() + 8 * b0 * dbs, dbs,
-                y.data_ptr() + 8 * b0 * ybs, ybs, int(seg), p(work), per,
-                at(alpha, 8 * b0 * N), at(mu, 8 * b0 * N), at(mu_comp, 8 * b0 * N),
-                ll.data_ptr() + 8 * b0, info.data_ptr() + 4 * b0, stream)
-            _lib.check(st, "gf_solve_batch")
-            e1.record()
-            events.append((e0, e1))
-        return dict(alpha=alpha, mu=mu, mu_comp=mu_comp, ll=ll, info=info, workspace_bytes=8 * per * group,
-                    groups=ngroups, group_size=group, events=events)
+        events = rc.run(lambda g: g.launch(
+            g.nb, N, Jr, Jc, *g.coef[0], jr2, jc2, *g.coef[1], *g.data, int(seg), *g.work,
+            g.at(alpha, N), g.at(mu, N), g.at(mu_comp, N), g.at(ll), g.at(info), g.stream))
+        return dict(alpha=alpha, mu=mu, mu_comp=mu_comp, ll=ll, info=info, events=events, **rc.plan)
 
 
 def predict_at(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):
@@ -148,26 +111,11 @@ def predict_at(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):
         raise ValueError(f"alpha of shape {tuple(alpha.shape)} does not hold the batch's ({B}, {N}) rows")
     dev = engine.device
     f64 = dict(dtype=torch.float64, device=dev)
-    i64 = dict(dtype=torch.int64, device=dev)
     lib, p = engine.lib, _lib.ptr
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ts = torch.as_tensor(ts, dtype=torch.float64).to(dev)
-        if ts.ndim == 1:
-            ts = ts[None, :]
-        if ts.ndim != 2 or ts.shape[0] not in (1, B) or ts.shape[1] < 1:
-            raise ValueError(f"query times of shape {tuple(ts.shape)} for a batch of {B} problems")
-        ts = ts.contiguous()
+        ts, M, nobs, nq = query_axes(engine, ts, nobs, nq)
         alpha = alpha.contiguous()
-        M = int(ts.shape[1])
-        counts = []
-        for cnt, full in ((nobs, N), (nq, M)):
-            if cnt is not None:
-                cnt = np.ascontiguousarray(cnt, dtype=np.int64)
-                if cnt.shape != (B,) or np.any(cnt < 0) or np.any(cnt > full):
-                    raise ValueError("dimension mismatch")
-                cnt = torch.as_tensor(cnt, **i64)
-            counts.append(cnt)
         mu = torch.empty((B, M), **f64)
         cr_ = torch.as_tensor(np.ascontiguousarray(real, dtype=np.float64), **f64)
         cc_ = torch.as_tensor(np.ascontiguousarray(comp, dtype=np.float64), **f64)
@@ -176,7 +124,7 @@ def predict_at(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):
         e0.record()
         st = lib.gf_predict_batch_at(
             B, N, M, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]),
-            p(t), engine._bs(t), p(counts[0]), p(ts), engine._bs(ts), p(counts[1]),
+            p(t), engine._bs(t), p(nobs), p(ts), engine._bs(ts), p(nq),
             p(alpha), N, p(mu), M, stream)
         _lib.check(st, "gf_predict_batch_at")
         e1.record()
@@ -188,11 +136,8 @@ def variance_plan(N, W, B, M=0, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0):
     the solve's workspace, one slot for Y and 64 doubles per staged query (at M = N the queries dominate and the groups
     shrink)."""
     check_width(W)
-    per = int(_lib.load().gf_var_batch_work(int(N), int(W), int(M), int(seg)))
-    if per <= 0:
-        raise ValueError(f"no variance workspace for N = {N}, W = {W}, M = {M}, seg = {seg}")
-    group = int(max(1, min(B, int(cap_bytes) // (8 * per))))
-    return per, group, (B + group - 1) // group
+    return group_plan(_lib.load().gf_var_batch_work(int(N), int(W), int(M), int(seg)), B, cap_bytes,
+                      f"no variance workspace for N = {N}, W = {W}, M = {M}, seg = {seg}")
 
 
 def variance_batch(engine, Jr, Jc, real, comp, diag_add, ts=None, nobs=None, nq=None,
@@ -209,66 +154,17 @@ def variance_batch(engine, Jr, Jc, real, comp, diag_add, ts=None, nobs=None, nq=
         raise ValueError("coefficient pack does not match the batch structure")
     B, N = engine.B, engine.N
     check_pack_batch(B, Jr, Jc, real, comp, diag_add)
-    lib, p = engine.lib, _lib.ptr
-    dev = engine.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    i64 = dict(dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        M = 0
-        if ts is not None:
-            ts = torch.as_tensor(ts, dtype=torch.float64).to(dev)
-            if ts.ndim == 1:
-                ts = ts[None, :]
-            if ts.ndim != 2 or ts.shape[0] not in (1, B):
-                raise ValueError(f"query times of shape {tuple(ts.shape)} for a batch of {B} problems")
-            ts = ts.contiguous()
-            M = int(ts.shape[1])
-            if M == 0:
-                ts = None
-        counts = []
-        for cnt, full in ((nobs, N), (nq, M)):
-            if cnt is not None:
-                cnt = np.ascontiguousarray(cnt, dtype=np.int64)
-                if cnt.shape != (B,) or np.any(cnt < 0) or np.any(cnt > full):
-                    raise ValueError("dimension mismatch")
-                cnt = torch.as_tensor(cnt, **i64)
-            counts.append(cnt)
-        per, group, ngroups = variance_plan(N, W, B, M, cap_bytes, seg)
-        work = torch.empty((group * per,), **f64)
+    f64 = dict(dtype=torch.float64, device=engine.device)
+    with torch.cuda.device(engine.device):
+        ts, M, nobs, nq = query_axes(engine, ts, nobs, nq, empty_ok=True)
+        rc = GroupedCall(engine, "gf_var_batch", variance_plan(N, W, B, M, cap_bytes, seg), (real, comp, diag_add))
         ll = torch.empty((B,), **f64)
-        info = torch.zeros((B,), dtype=torch.int32, device=dev)
+        info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
         outs = {k: (torch.empty((B, N), **f64) if want else None) for k, want in
                 (("alpha", want_alpha), ("mu", want_mu), ("hdiag", want_h), ("var", want_var))}
         var_at = torch.empty((B, M), **f64) if M else None
-        real = np.ascontiguousarray(real, dtype=np.float64)
-        comp = np.ascontiguousarray(comp, dtype=np.float64)
-        diag_add = np.ascontiguousarray(diag_add, dtype=np.float64)
-        t, y, dg = engine.t, engine.y, engine.diag
-        tbs, ybs = engine._bs(t), engine._bs(y)
-        dbs = 0 if dg is None else engine._bs(dg)
         qbs = 0 if ts is None else engine._bs(ts)
-        at = lambda x, off: None if x is None else x.data_ptr() + off      # noqa: E731
-        events = []
-        for b0 in range(0, B, group):
-            nb = min(group, B - b0)
-            cr_ = torch.as_tensor(np.ascontiguousarray(real[:, b0:b0 + nb]), **f64)
-            cc_ = torch.as_tensor(np.ascontiguousarray(comp[:, b0:b0 + nb]), **f64)
-            da = torch.as_tensor(diag_add[b0:b0 + nb], **f64)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            st = lib.gf_var_batch(
-                nb, N, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]), p(da),
-                t.data_ptr() + 8 * b0 * tbs, tbs,
-                None if dg is None else dg.data_ptr() + 8 * b0 * dbs, dbs,
-                y.data_ptr() + 8 * b0 * ybs, ybs,
-                at(ts, 8 * b0 * qbs), qbs, M, at(counts[0], 8 * b0), at(counts[1], 8 * b0),
-                int(seg), p(work), per,
-                at(outs["alpha"], 8 * b0 * N), at(outs["mu"], 8 * b0 * N), at(outs["hdiag"], 8 * b0 * N),
-                at(outs["var"], 8 * b0 * N), at(var_at, 8 * b0 * M),
-                ll.data_ptr() + 8 * b0, info.data_ptr() + 4 * b0, stream)
-            _lib.check(st, "gf_var_batch")
-            e1.record()
-            events.append((e0, e1))
-        return dict(ll=ll, info=info, var_at=var_at, workspace_bytes=8 * per * group, groups=ngroups,
-                    group_size=group, events=events, **outs)
+        events = rc.run(lambda g: g.launch(
+            g.nb, N, Jr, Jc, *g.coef[0], *g.data, g.at(ts, qbs), qbs, M, g.at(nobs), g.at(nq), int(seg), *g.work,
+            *(g.at(x, N) for x in outs.values()), g.at(var_at, M), g.at(ll), g.at(info), g.stream))
+        return dict(ll=ll, info=info, var_at=var_at, events=events, **rc.plan, **outs)
