@@ -1518,19 +1518,20 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
 //   s   <- lambda^2 s + lambda G z_j + G z_j+1              lane = term, two rows per step, z by LDS broadcast
 //          (k_steady_finish: on both half-waves, rows 32 .. 63 from a zero state, joined by lambda^32 -- FOLD below)
 // k_steady_finish folds the first two lines (FOLD below): with p = y + C s,  z = H y + Q s,  Q = H C.  Q takes C's
-// registers (one row per lane; the set-up applies H to each of C's columns), u = H y depends on the data alone and is
-// formed one block ahead, and the chain from a block's state to the next is  s -> LDS -> z = u + Q s -> LDS -> state
-// update -> join: H's 64 reads and its 32-deep FMA chains are off it.  H y needs no LDS image: y lies one row per lane
-// and moves up one lane per tap (DPP wave_shr:1), h by broadcast.
+// registers (one row per lane; the set-up applies H to each of C's columns: a column lies one row per lane and moves
+// up one lane per tap, DPP wave_shr:1, h by broadcast), u = H y depends on the data alone and is formed for 16 blocks
+// at once on the matrix pipe in front of them (the group phase, below), and the chain from a block's state to the
+// next is  s -> LDS -> z = u + Q s -> LDS -> state update -> join: H's 64 reads and its 32-deep FMA chains are off it.
 // h is the row form's answer to a unit impulse, computed at the problem's first tail entry of an evaluation and kept
 // in the steady buffer; the p coefficients are recomputed at every launch (per lane one fm_sincos + fm_exp per term,
 // through an LDS staging area of 8 terms so that the loop over the terms is not unrolled around them).
 // One wave per problem, grid B; rows [max(switch row + 1, tile start), tile end) of a problem that has switched.
-// t and y arrive by one coalesced load per block, issued a block ahead; d (= d_inf) and z leave by one coalesced
+// t and y arrive by one coalesced load per block, issued a block ahead (k_steady_finish: t so, y in the group phase's
+// operand layout for 16 blocks at once); d (= d_inf) and z leave by one coalesced
 // store per block (k_steady_tail; k_steady_finish, the streamed log-likelihood's instance, stores no row: below).
 // A partial last block runs the same code: H is lower triangular, so the rows beyond the tile (y clamped to the
 // last row) touch no row before them; the s loop is bounded and the stores are masked.  (k_steady_finish: behind its
-// loop of full blocks, with the u the block before it formed.)
+// group's full blocks, with its own column of the group's U.)
 // Every spacing t_r - t_{r-1} of a tail row r is tested as RowGen tests it (a gap: > gthr; off the frozen cadence:
 // >= jthr): a hit raises ST_VIOL and the rows of that evaluation mean nothing (finite).
 // ------------------------------------------------------------------------------------
@@ -1545,6 +1546,9 @@ __device__ __forceinline__ void stage_end() {
     __builtin_amdgcn_sched_barrier(0);
 }
 constexpr int RED_NACC = 3;         // the reductions' accumulators per problem: sum log d, sum z^2/d, min d
+
+#define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+typedef double d4 __attribute__((ext_vector_type(4)));
 
 // STORE = true: the rows leave as d and z (k_steady_tail, tile by tile); STORE = false: no row is stored, every lane
 // keeps the running sum of z^2 of its row slot over all blocks, and the wave adds the problem's tail to acc
@@ -1582,14 +1586,16 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
 
     __shared__ __attribute__((aligned(16))) double s_s[64];         // (s_r, s_i) of term k at [2k], [2k + 1]
     __shared__ __attribute__((aligned(16))) double s_p[128];        // 64 zeros, then p of the block
-    __shared__ __attribute__((aligned(16))) double s_h[64];         // impulse response
+    // impulse response; FOLD: behind 16 zeros, h at a negative index for the group phase's tiles on H's diagonal
+    __shared__ __attribute__((aligned(16))) double s_h[FOLD ? 16 + 64 : 64];
+    double *const hh = s_h + (FOLD ? 16 : 0);       // h(0)
     __shared__ __attribute__((aligned(16))) double s_z[64];         // z of the block
     __shared__ double s_c[STT_STAGE][2][64];                        // staging of the p coefficients
     // 64 rows of H against an image: lane i adds h(m) v[i - m], m in [0, 64), even m to a0 and odd m to a1
     auto taps = [&](const double *pp, double &a0, double &a1) {
 #pragma unroll
         for (int m = 0; m < 64; m += 2) {
-            const double2 hv = ((const double2 *)s_h)[m >> 1];
+            const double2 hv = ((const double2 *)hh)[m >> 1];
             a0 = fma(hv.x, pp[-m], a0);
             a1 = fma(hv.y, pp[-m - 1], a1);
         }
@@ -1601,7 +1607,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
 #pragma unroll 1
         for (int m = 0; m < 64; m += 2) {
-            const double2 hv = ((const double2 *)s_h)[m >> 1];
+            const double2 hv = ((const double2 *)hh)[m >> 1];
             a0 = fma(hv.x, va, a0);
             b0 = fma(hv.x, vb, b0);
             va = wave_shr1(va);
@@ -1647,7 +1653,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
 
     // impulse response: the row form on y = (1, 0, 0, ...) from s = 0, once per evaluation
     if (hdr[ST_HOK] != 0.0) {
-        s_h[lane] = hdr[ST_H + lane];
+        hh[lane] = hdr[ST_H + lane];
     } else {
         double hr = Gr, hi = Gi, hv = (lane == 0) ? 1.0 : 0.0;      // h(0) = 1, s = G
         const double ha = (lane < 32) ? ck_a : 0.0, hb = (lane < 32) ? ck_b : 0.0;  // (each term once in the sum)
@@ -1658,11 +1664,12 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             hi = fma(Gi, hm, xi);
             hv = (lane == m) ? hm : hv;
         }
-        s_h[lane] = hv;
+        hh[lane] = hv;
         hdr[ST_H + lane] = hv;
         if (lane == 0) hdr[ST_HOK] = 1.0;
     }
     if constexpr (!FOLD) s_p[lane] = 0.0;
+    else if (lane < 16) s_h[lane] = 0.0;
 
     // lane = row of a block: -alpha_k lambda_k^(i+1) = (pr_k, pi_k) with Re(.) taken against (s_r, s_i):
     // p = y + sum_k pr_k s_r,k + pi_k s_i,k.  FOLD: H applied to each of these 2 JT columns where they are
@@ -1749,15 +1756,54 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         if (j < lim) one_row(s_z[j]);
     }
     } else {
-    // The folded block.  u = H y of a block depends on the data alone: it is formed a block ahead, in pieces between
-    // the phases of the chain  s -> LDS -> z = u + Q s -> LDS -> state update -> join,  whose waits it fills.  y is
-    // loaded a block ahead, one row per lane, and moves up a lane per tap.  The series' last block has no successor:
-    // its u comes from rows clamped as row_of clamps them, and nothing reads it.
-    double u, y_nx = yg[row_of(nb + 64)];
-    {
-        double unused;
-        shifted_taps(yg[row_of(nb)], 0.0, u, unused);
-    }
+    // The folded block.  u = H y of a block depends on the data alone, and on its own block's alone (H is the Toeplitz
+    // triangle inside a block): the group phase forms it for 16 consecutive blocks at once, on the matrix pipe, as
+    // U = H [y_k .. y_k+15], a (64 x 64) (64 x 16) product in 16 x 16 tiles of H against 4-row slices of Y
+    // (v_mfma_f64_16x16x4_f64).  H is lower block-triangular: 10 tiles x 4 slices = 40 MFMAs into one accumulator per
+    // 16 rows of U.  No lane shifts and no broadcasts of h:
+    //   B (4 x 16, slice q of Y's tile Jt): lane l holds y[g0 + 64 (l & 15) + 16 Jt + 4 q + (l >> 4)] straight from
+    //     memory, its index clamped to the series' last row as row_of clamps (rows < N only); 16 loads per group;
+    //   A (16 x 4, slice q of H's tile type d = I - Jt): lane l holds h(16 d + (l & 15) - 4 q - (l >> 4)), zero at a
+    //     negative index: one read of s_h with its 16 zeros in front, 19 consecutive doubles per read;
+    //   D: lane l holds U[16 I + (l >> 4) + 4 r][block l & 15] in element r; it goes to s_u[block][row] with a row
+    //     stride of 64 + 1 doubles: a 64-bit LDS store is served in groups of 16 consecutive lanes over 32 banks, and
+    //     the 16 blocks of a group then fall on its 16 double-wide banks (no conflict; a pad of 2 measured 2-way).
+    // A block then takes its u, lane = row, by one read.  A partial group runs the same phase: its surplus columns hold
+    // clamped rows, columns do not mix, and nothing reads them.  The chain of a block stays
+    // s -> LDS -> z = u + Q s -> LDS -> state update -> join.
+    constexpr int SU = 64 + 1;
+    __shared__ __attribute__((aligned(16))) double s_u[16 * SU];
+    const int mc = lane & 15, mk = lane >> 4;
+    auto group_phase = [&](const int64_t g0) {
+        double ha[4][4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) ha[d][q] = hh[16 * d + mc - 4 * q - mk];
+        d4 U[4];
+#pragma unroll
+        for (int I = 0; I < 4; ++I) U[I] = d4{0.0, 0.0, 0.0, 0.0};
+        const int64_t r0 = g0 + 64 * mc + mk;
+#pragma unroll
+        for (int Jt = 0; Jt < 4; ++Jt) {
+            double yb[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t i = r0 + 16 * Jt + 4 * q;
+                yb[q] = yg[i < last ? i : last];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int I = Jt; I < 4; ++I) U[I] = GF_MFMA64(ha[I - Jt][q], yb[q], U[I]);
+        }
+        wave_lds_fence();                           // behind the last block's read of its u
+#pragma unroll
+        for (int I = 0; I < 4; ++I)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s_u[mc * SU + 16 * I + mk + 4 * r] = U[I][r];
+        wave_lds_fence();
+    };
     // the state update: the lower half-wave takes the block's rows 0 .. 31 from the incoming state, the upper one the
     // rows 32 .. 63 from a zero state -- half the chain --, and s <- lambda^(rows of the upper half) s_low + s_high
     // joins them (the update is linear in the state); the upper half starts the next block from zero again.  A
@@ -1771,17 +1817,18 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         si = half ? 0.0 : fma(jr, sli, fma(ji, slr, sui));
     };
     int64_t cb = nb;
-    // The full blocks: one basic block each, in stages.  A stage ends in a scheduling barrier, so that its LDS reads
-    // are issued a stage before the FMAs that take them and no further ahead (the registers hold Q): the s broadcasts
-    // in groups of FG terms, z of the state update eight rows ahead, and in every stage four taps of the next
-    // block's u -- their reads in one stage, their FMAs in the next.
-    for (; cb + 64 <= N; cb += 64) {
-        double ys = y_nx;                           // y of the rows cb + 64 + lane: moves up a lane per tap of u
+    // A group: its phase, then its blocks.  The full blocks: one basic block each, in stages.  A stage ends in a
+    // scheduling barrier, so that its LDS reads are issued a stage before the FMAs that take them and no further ahead
+    // (the registers hold Q): the s broadcasts in groups of FG terms, z of the state update eight rows ahead.
+    while (cb < N) {
+    group_phase(cb);
+    const double *ub = s_u + lane;                  // this lane's row of the block's u
+    const int64_t ge = (N - cb > 16 * 64) ? cb + 16 * 64 : N;
+    for (; cb + 64 <= ge; cb += 64, ub += SU) {
         const double tv = t_nx, tp = tp_nx;         // t of the rows cb + lane
         {
             const int64_t i = row_of(cb + 64);
             t_nx = tg[i]; tp_nx = tg[i - 1];
-            y_nx = yg[row_of(cb + 128)];
         }
         const double dt = tv - tp;
         viol |= (dt > gthr) || !(fabs(dt - delta) < jthr);
@@ -1789,28 +1836,8 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
         wave_lds_fence();
         constexpr int NG = (JT + FG - 1) / FG;
-        // u_stage reads four taps' h in one call and takes them in the next: 16 reading calls and one more
-        static_assert(NG + 16 >= 17, "the stages of a full block must call u_stage at least 17 times");
-        double a0 = 0.0, a1 = 0.0, z0 = u, z1 = 0.0;
-        double2 sv[2][FG], uh[2], zz[16];
-        int uq = 0;                                 // (a constant in every stage once the stages are unrolled)
-        auto u_stage = [&]() {
-            if (uq > 0 && uq <= 16) {
-                a0 = fma(uh[0].x, ys, a0);
-                ys = wave_shr1(ys);
-                a1 = fma(uh[0].y, ys, a1);
-                ys = wave_shr1(ys);
-                a0 = fma(uh[1].x, ys, a0);
-                ys = wave_shr1(ys);
-                a1 = fma(uh[1].y, ys, a1);
-                ys = wave_shr1(ys);
-            }
-            if (uq < 16) {
-                uh[0] = ((const double2 *)s_h)[2 * uq];
-                uh[1] = ((const double2 *)s_h)[2 * uq + 1];
-            }
-            ++uq;
-        };
+        double z0 = *ub, z1 = 0.0;
+        double2 sv[2][FG], zz[16];
         auto s_ld = [&](const int g) {
 #pragma unroll
             for (int i = 0; i < FG; ++i)
@@ -1820,7 +1847,6 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             if (g + 1 < NG) s_ld(g + 1);
-            u_stage();
             stage_end();
 #pragma unroll
             for (int i = 0; i < FG; ++i) {
@@ -1840,21 +1866,19 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
 #pragma unroll
                 for (int i = j2 + 4; i < j2 + 8; ++i) zz[i] = ((const double2 *)zb)[i];
             }
-            u_stage();
             stage_end();
             two_rows(zz[j2]);
         }
         join(l32r, l32i);
-        u = a0 + a1;
     }
-    if (cb < N) {                                   // a partial last block: lim rows, u from the block before
+    if (cb < ge) {                                  // a partial last block (ge = N): lim rows
         const int lim = (int)(N - cb);
         const double dt = t_nx - tp_nx;
         viol |= (lane < lim) && ((dt > gthr) || !(fabs(dt - delta) < jthr));
         wave_lds_fence();
         if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
         wave_lds_fence();
-        double z0 = u, z1 = 0.0;
+        double z0 = *ub, z1 = 0.0;
 #pragma unroll
         for (int k = 0; k < JT; ++k) {
             add_term(k, ((const double2 *)s_s)[k], z0, z1);
@@ -1876,6 +1900,8 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             jr = xr;
         }
         join(jr, ji);
+        cb = N;
+    }
     }
     }
     if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
@@ -1929,9 +1955,6 @@ k_steady_finish(const int64_t N, const int Jc, const double gap,
     steady_tail_rows<ROWS, false>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr, info,
                                   steady_, acc_, sw_lo, sw_hi);
 }
-
-#define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------
 // Closed-loop transition sweeps of the time-parallel evaluation, W <= 63 (k_phi7: k_factor7's lane tiling,

@@ -13,7 +13,10 @@ most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, sca
 Blocks that hold an exponential or a sincos (fm_exp / fm_sincos end in v_ldexp_f64) are marked `exp`: the reset
 row's decay and the generator's anchors.  VALU counts every v_* opcode
 (v_readlane / v_readfirstlane / v_permlane* included, as SQ_INSTS_VALU counts them); LDS counts ds_*, `spill`
-scratch_* (register spills), `mov64` 64-bit register copies, `movb32` 32-bit moves.
+scratch_* (register spills), `mov64` 64-bit register copies, `movb32` 32-bit moves.  Matrix instructions (v_mfma_*) are
+a class of their own, `MFMA`, and not in VALU: they issue to the matrix pipe.  k_steady_finish forms u = H y in a group
+phase in front of every 16 blocks (the blocks that hold its MFMAs, outside the block loop): reported per group and as
+its share per block.
 """
 import argparse
 import os
@@ -85,9 +88,14 @@ def row_loop(bl, reg):
 
 
 def counts(ins):
-    c = {"valu": 0, "fma": 0, "lds": 0, "salu": 0, "mov64": 0, "movb32": 0, "ldexp": 0, "branch": 0, "scratch": 0}
+    c = {"valu": 0, "fma": 0, "lds": 0, "salu": 0, "mov64": 0, "movb32": 0, "ldexp": 0, "branch": 0, "scratch": 0,
+         "mfma": 0, "gload": 0}
     for op in ins:
-        if op.startswith("v_"):
+        if op.startswith("v_mfma"):
+            c["mfma"] += 1
+        elif op.startswith("global_load"):
+            c["gload"] += 1
+        elif op.startswith("v_"):
             c["valu"] += 1
             c["fma"] += op.startswith(("v_fma_f64", "v_fmac_f64"))
             c["mov64"] += op in ("v_mov_b64", "v_mov_b64_e32", "v_pk_mov_b32", "v_lshl_add_u64")
@@ -142,6 +150,17 @@ def steady_tail(lines, rows, kernel="k_steady_tail"):
         dyn[k] += c[k]
     print(f"  per full 64-row block: {dyn['valu']:.0f} VALU, {dyn['lds']:.0f} LDS, {dyn['salu']:.0f} SALU, "
           f"{dyn['branch']:.0f} branches;  per row: {dyn['valu'] / 64:.2f} VALU, {dyn['lds'] / 64:.2f} LDS")
+    in_loop = counts([op for k in range(i0, i1 + 1) for op in bl[k]["ins"]])["mfma"]
+    group = [k for k, b in enumerate(bl) if counts(b["ins"])["mfma"] and not i0 <= k <= i1]
+    if in_loop:
+        print(f"  {in_loop} MFMA inside the block loop")
+    if group:
+        g = counts([op for k in group for op in bl[k]["ins"]])
+        print(f"  group phase (blocks {', '.join(bl[k]['name'] for k in group)}, once per 16 blocks): {g['mfma']} MFMA, "
+              f"{g['valu']} VALU, {g['lds']} LDS, {g['gload']} global loads, {g['salu']} SALU;  per block: "
+              f"{g['mfma'] / 16:.2f} MFMA, {g['valu'] / 16:.1f} VALU, {g['lds'] / 16:.1f} LDS")
+        print(f"  per full 64-row block with its share of the group phase: {dyn['valu'] + g['valu'] / 16:.0f} VALU, "
+              f"{g['mfma'] / 16:.2f} MFMA, {dyn['lds'] + g['lds'] / 16:.0f} LDS")
 
 
 def main():
