@@ -16,6 +16,8 @@ from .batch import (BatchedLogLikelihood, log_likelihood_batch, BatchedSampler, 
 from . import terms  # noqa: F401
 from .psd import PowerSpectrum, bin_power_spectrum  # noqa: F401
 from .interp import interpolate_missing_data, stitch_quarters  # noqa: F401
+from . import spectral  # noqa: F401
+from .spectral import SpectralLikelihood  # noqa: F401
 
 __version__ = "0.1.0"
 
@@ -25,4 +27,7 @@ def __getattr__(name):
     if name == "LogLikelihood":
         from .grad import LogLikelihood
         return LogLikelihood
+    # torch.autograd.Function over SpectralLikelihood.value_and_grad (gadfly_amd.spectral); imported on first use
+    if name == "SpectralLogLikelihood":
+        return spectral.SpectralLogLikelihood
     raise AttributeError(f"module 'gadfly_amd' has no attribute {name!r}")

@@ -159,7 +159,8 @@ class PowerSpectrum:
     """
     An observed power spectrum (reference psd.py:364-396): ``frequency`` [uHz], ``power``
     [ppm^2/uHz] (shape (M,), or (R, M) for a batch of R series sharing the frequency axis),
-    optional ``error``, ``name``, ``norm`` and ``detrended_lc``.
+    optional ``error``, ``name``, ``norm`` and ``detrended_lc``.  ``counts``: the number of ordinates averaged into
+    each point of a binned spectrum (set by :func:`bin_power_spectrum`), None on an unbinned one.
     """
 
     def __init__(self, frequency, power, error=None, name=None, norm=None, detrended_lc=None):
@@ -169,6 +170,7 @@ class PowerSpectrum:
         self.name = name
         self.norm = norm
         self.detrended_lc = detrended_lc
+        self.counts = None
         self._power_dev = None              # device copy of `power` when it was made there
 
     @property
@@ -394,5 +396,7 @@ def bin_power_spectrum(power_spectrum, bins=None, log=True, constant=1, device=N
     centers = 10 ** mid if log else mid
     single = np.ndim(power_spectrum.power) == 1
     name = (power_spectrum.name if power_spectrum.name is not None else "Power spectrum") + " (binned)"
-    return PowerSpectrum(centers, stat_h[0] if single else stat_h,
-                         err_h[0] if single else err_h, name=name)
+    binned = PowerSpectrum(centers, stat_h[0] if single else stat_h,
+                           err_h[0] if single else err_h, name=name)
+    binned.counts = np.diff(start)          # ordinates per bin (the Whittle weights of a binned spectrum)
+    return binned

@@ -773,6 +773,37 @@ int gf_var_batch(int B, int64_t N, int Jr, int Jc,
                  double *alpha, double *mu, double *hdiag, double *var, double *var_at,
                  double *ll, int32_t *info, void *stream);
 
+/*
+ * Spectral log-likelihoods of B sums of J SHO terms against observed power spectra, their gradients and the model
+ * spectra: the objective behind gadfly's hyperparameters.json (notebooks/virgo_lc.ipynb: chi-square
+ * of TermConvolution.get_psd against the binned spectrum) and the Whittle likelihood of a periodogram.  With
+ * omega = 2 pi f (f in uHz), exposure delta[b] >= 0 and white floor floor[b] >= 0 (NULL = 0):
+ *     S_b(w) = sinc^2(delta_b w / 2) sum_j sqrt(2/pi) S0_j w0_j^4 / (((w - w0_j)(w + w0_j))^2 + w^2 w0_j^2 / Q_j^2) + c_b
+ *     objective 0 (whittle):  ll_b = - sum_k n_k (ln S_b(w_k) + P_k / S_b(w_k))     weight = n_k, NULL = 1
+ *     objective 1 (chi2):     ll_b = - 1/2 sum_k ((P_k - S_b(w_k)) / e_k)^2          weight = e_k, required
+ * over the USED frequencies: P_k and its weight finite, the weight positive; used[b] counts them.
+ *   S0, w0, Q [B][J]; delta [B]; omega [M] shared; power / weight with batch strides in elements (0 = one spectrum
+ *     for every problem); J <= 256 (-3 beyond), M >= 1, B <= 65535 per call
+ *   work: gf_spectral_work(B, M, J) doubles (0 for a shape outside the limits); a problem's share, and so its result,
+ *     depends on M and J alone
+ *   ll [B], used [B], info [B]: where S_b(w_k) is not > 0 at a used frequency, ll = -inf, every gradient of the
+ *     problem is NaN and info = k + 1 for the first such k (0 otherwise)
+ *   gS0, gw0, gQ [B][J], gfloor [B]: d ll_b / d (S0, w0, Q, c); each may be NULL, all NULL = value only (the value
+ *     has the same bits either way)
+ *   model [B][M] (or NULL): S_b(w_k) at every frequency, used or not
+ * gf_spectral_tile(): the frequencies one workgroup takes.  No atomics: results are bit-identical from run to run and
+ * do not depend on the other problems of the call.
+ */
+int gf_spectral_tile(void);
+int64_t gf_spectral_work(int B, int64_t M, int J);
+int gf_spectral_like(int B, int64_t M, int J, int objective,
+                     const double *S0, const double *w0, const double *Q,
+                     const double *delta, const double *floor, const double *omega,
+                     const double *power, int64_t power_bs, const double *weight, int64_t weight_bs,
+                     double *work, double *ll, int64_t *used, int32_t *info,
+                     double *gS0, double *gw0, double *gQ, double *gfloor,
+                     double *model, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
