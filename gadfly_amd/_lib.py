@@ -20,7 +20,8 @@ if os.environ.get("GADFLY_SO"):                 # another build of the same libr
 SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dense.hip"),
            os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip"),
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),
-           os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip")]
+           os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
+           os.path.join(CSRC, "gadfly_fisher.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -137,6 +138,9 @@ SIGNATURES = {
     "gf_spectral_tile": (_int, []),
     "gf_spectral_work": (_i64, [_int, _i64, _int]),
     "gf_spectral_like": (_int, [_int, _i64, _int, _int] + [_vp] * 6 + [_vp, _i64, _vp, _i64] + [_vp] * 9 + [_vp]),
+    "gf_spectral_fisher_slab": (_int, []),
+    "gf_spectral_fisher_work": (_i64, [_int, _i64, _int]),
+    "gf_spectral_fisher": (_int, [_int, _i64, _int, _int] + [_vp] * 6 + [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_vp]),
 }
 
 

@@ -15,21 +15,92 @@ plus a white floor, for B parameter sets at once and any number of terms up to 2
 
 Both are log-likelihoods (to be maximised), summed over the used frequencies: those whose power and weight / error are
 finite and whose weight / error is positive (the empty bins of ``.bin()`` are NaN and drop out, as with the notebook's
-``nansum``).  There is no optimiser here: :class:`SpectralLogLikelihood` is a ``torch.autograd.Function`` for
-``torch.optim`` or a sampler.  Frequencies in uHz, power in ppm^2/uHz, delta in 1/uHz.
+``nansum``).  :class:`SpectralLogLikelihood` is a ``torch.autograd.Function`` for ``torch.optim`` or a sampler.
+Frequencies in uHz, power in ppm^2/uHz, delta in 1/uHz.
+
+The curvature of both objectives is the Fisher information (``gf_spectral_fisher``)
+
+    F_b = sum_k v_k grad S_b(w_k) grad S_b(w_k)^T,    v_k = n_k / S_k^2 (whittle),  v_k = 1 / e_k^2 (chi2)
+
+in the parameter order S0_0 .. S0_{J-1}, w0_0 .., Q_0 .., floor: :meth:`SpectralLikelihood.fisher_device`.  From it
+come the covariances and standard errors of a fit (:meth:`SpectralLikelihood.covariance`,
+:meth:`SpectralLikelihood.standard_errors`) and the fit itself, a damped Fisher scoring of B problems in lockstep
+(:meth:`SpectralLikelihood.fit`).
 """
 import numpy as np
 
 from . import _lib
 
-__all__ = ["SpectralLikelihood", "SpectralLogLikelihood", "white_floor", "check_parameters", "OBJECTIVES",
-           "MAX_TERMS", "DEFAULT_WORKSPACE_BYTES"]
+__all__ = ["SpectralLikelihood", "SpectralLogLikelihood", "SpectralFit", "white_floor", "check_parameters",
+           "parameter_index", "OBJECTIVES", "PARAMETERS", "MAX_TERMS", "DEFAULT_WORKSPACE_BYTES"]
 
 OBJECTIVES = {"whittle": 0, "chi2": 1}
 MAX_TERMS = 256                         # gf_spectral_like's limit on J
 MAX_GROUP = 65535                       # problems per launch (the grid's second axis)
 #: default cap on the workspace of one launch (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = 2 << 30
+
+
+PARAMETERS = ("S0", "w0", "Q", "floor")     # the canonical order of the Fisher matrix's blocks
+
+
+def parameter_index(names, J, what="wrt"):
+    """Rows of the (3 J + 1)-parameter Fisher matrix the blocks ``names`` select, in the canonical order (S0, w0, Q,
+    floor) whatever the order of ``names``; ValueError for an unknown name or an empty selection."""
+    names = (names,) if isinstance(names, str) else tuple(names)
+    bad = [k for k in names if k not in PARAMETERS]
+    if bad or not names:
+        raise ValueError(f"{what} holds unknown names {bad} (S0, w0, Q, floor)" if bad else f"{what} is empty")
+    idx = [np.arange(i * J, (i + 1) * J if i < 3 else 3 * J + 1) for i, k in enumerate(PARAMETERS) if k in names]
+    return np.concatenate(idx)
+
+
+class SpectralFit:
+    """What :meth:`SpectralLikelihood.fit` returns: ``S0, w0, Q`` (B, J), ``floor`` (B,) and ``ll`` (B,) at the last
+    accepted point, ``iterations`` (B,), ``converged`` (B,) bool, and the covariance ``cov`` (B, P', P') of the free
+    parameters there with ``cov_ok`` (B,) (see :meth:`SpectralLikelihood.covariance`); ``free`` names the blocks."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return (f"SpectralFit({int(np.sum(self.converged))} of {len(self.converged)} converged, "
+                f"at most {int(np.max(self.iterations))} iterations, free={self.free})")
+
+
+def _scaled_inverse(F):
+    """(cov, ok) of a (B, P, P) stack: the inverse of each matrix through the Cholesky factor of its Marquardt-scaled
+    form D^-1/2 F D^-1/2, D = diag F; NaN and ok = False where that is not positive definite or not finite."""
+    F = np.asarray(F, dtype=np.float64)
+    B, P, _ = F.shape
+    cov = np.full((B, P, P), np.nan)
+    d = np.diagonal(F, axis1=1, axis2=2)
+    ok = np.all(np.isfinite(F.reshape(B, -1)), axis=1) & np.all(d > 0.0, axis=1)
+    if not ok.any():
+        return cov, ok
+    rows = np.flatnonzero(ok)
+    s = 1.0 / np.sqrt(d[rows])
+    ss = s[:, :, None] * s[:, None, :]          # (exactly symmetric, and so is everything scaled by it)
+    C = F[rows] * ss
+    try:
+        L = np.linalg.cholesky(C)
+        good = np.ones(len(rows), dtype=bool)
+    except np.linalg.LinAlgError:               # one of them is not positive definite: find out which
+        L = np.zeros_like(C)
+        good = np.zeros(len(rows), dtype=bool)
+        for i in range(len(rows)):
+            try:
+                L[i] = np.linalg.cholesky(C[i])
+                good[i] = True
+            except np.linalg.LinAlgError:
+                L[i] = np.eye(P)
+    Li = np.linalg.inv(L)
+    inv = np.matmul(np.transpose(Li, (0, 2, 1)), Li)
+    inv = (0.5 * (inv + np.transpose(inv, (0, 2, 1)))) * ss
+    good &= np.all(np.isfinite(inv.reshape(len(rows), -1)), axis=1)
+    cov[rows[good]] = inv[good]
+    ok[rows[~good]] = False
+    return cov, ok
 
 
 def white_floor(yerr, d):
@@ -279,6 +350,185 @@ class SpectralLikelihood:
         """(B,) numpy log-likelihoods of a list of SHO-sum kernels (as ``BatchedLogLikelihood`` takes them)."""
         S0, w0, Q, delta = kernel_parameters(kernels)
         return self.evaluate_device(S0, w0, Q, delta, floor).cpu().numpy()
+
+    # ------------------------------------------------------------------------------------
+    def fisher_plan(self, B, J):
+        """(doubles per problem, problems per group, number of groups) of the Fisher call under
+        ``self.workspace_bytes``."""
+        from .rowcall import group_plan
+        per = _lib.load().gf_spectral_fisher_work(1, int(self.M), int(J))
+        per, group, _ = group_plan(per, B, self.workspace_bytes, f"no Fisher workspace for M = {self.M}, J = {J}")
+        group = min(group, MAX_GROUP)
+        return per, group, (B + group - 1) // group
+
+    def _fisher_arguments(self, S0, w0, Q, delta, floor, wrt, log, what="wrt"):
+        """The host side of a Fisher call: checked parameters, the selected rows and (B, P') parameter values."""
+        S0, w0, Q, delta, floor = check_parameters(S0, w0, Q, delta, floor, self.rows)
+        B, J = S0.shape
+        idx = parameter_index(wrt, J, what)
+        theta = np.concatenate([S0, w0, Q, (np.zeros(B) if floor is None else floor)[:, None]], axis=1)[:, idx]
+        if log and np.any(theta == 0.0):
+            raise ValueError("log=True needs every selected parameter to be non-zero (an S0 = 0, or floor None or 0)")
+        return (S0, w0, Q, delta, floor), idx, theta
+
+    def fisher_device(self, S0, w0, Q, delta, floor=None, wrt=PARAMETERS, log=False):
+        """(B, P', P') device tensor: the Fisher information of the objective (see the module docstring) with respect
+        to the blocks ``wrt`` in the canonical order S0, w0, Q, floor (P' = 3 J + 1 for all four).  ``log=True``: with
+        respect to ln theta, ``F_ij theta_i theta_j``.  A problem whose model is not positive at a used frequency
+        gets NaN (``last_info``); one without used frequencies a matrix of zeros.  The same host checks, uploads and
+        group plan as :meth:`run_device`."""
+        (S0, w0, Q, delta, floor), idx, theta = self._fisher_arguments(S0, w0, Q, delta, floor, wrt, log)
+        B, J = S0.shape
+        P = 3 * J + 1
+        torch = _lib.require_device()
+        lib = _lib.load()
+        per, group, ngroups = self.fisher_plan(B, J)
+        d = self._buffers()
+        dev = d["device"]
+        f64 = dict(dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            pars = torch.as_tensor(np.stack([S0, w0, Q]), **f64)                        # (3, B, J)
+            dl = torch.as_tensor(delta, **f64)
+            fl = None if floor is None else torch.as_tensor(floor, **f64)
+            work = torch.empty((group * per,), **f64)
+            F = torch.empty((B, P, P), **f64)
+            used = torch.empty((B,), dtype=torch.int64, device=dev)
+            info = torch.empty((B,), dtype=torch.int32, device=dev)
+
+            def at(x, b0, per_problem=1):
+                return None if x is None else x.data_ptr() + x.element_size() * b0 * per_problem
+
+            self._events = []
+            self.last_power_ptr = d["power"].data_ptr()
+            for b0 in range(0, B, group):
+                nb = min(group, B - b0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _lib.check(lib.gf_spectral_fisher(
+                    nb, self.M, J, OBJECTIVES[self.objective], at(pars[0], b0, J), at(pars[1], b0, J),
+                    at(pars[2], b0, J), at(dl, b0), at(fl, b0), d["omega"].data_ptr(),
+                    at(d["power"], b0, d["power_bs"]), d["power_bs"], at(d["weight"], b0, d["weight_bs"]),
+                    d["weight_bs"], work.data_ptr(), at(F, b0, P * P), at(used, b0), at(info, b0), st),
+                    "gf_spectral_fisher")
+                e1.record()
+                self._events.append((e0, e1))
+            if len(idx) != P:
+                sel = torch.as_tensor(idx, dtype=torch.int64, device=dev)
+                F = F.index_select(1, sel).index_select(2, sel)
+            if log:
+                th = torch.as_tensor(theta, **f64)
+                F = F * th[:, :, None] * th[:, None, :]
+        self.last_plan = (8 * per * group, ngroups, group)
+        self._used, self._info = used, info
+        return F
+
+    def fisher(self, S0, w0, Q, delta, floor=None, wrt=PARAMETERS, log=False):
+        """:meth:`fisher_device` as a (B, P', P') numpy array."""
+        return self.fisher_device(S0, w0, Q, delta, floor, wrt, log).cpu().numpy()
+
+    def covariance(self, S0, w0, Q, delta, floor=None, wrt=PARAMETERS, log=False):
+        """``(cov, ok)``: the inverse Fisher matrices (B, P', P') and a (B,) bool.  Each matrix is inverted through
+        the Cholesky factor of its Marquardt-scaled form D^-1/2 F D^-1/2, D = diag F (on the host, in LAPACK: DESIGN.md
+        3.14); a problem whose matrix is not positive definite or holds NaN -- a zero diagonal entry, a term with
+        S0 = 0, a model that is not positive -- gets NaN and ``ok = False``."""
+        return _scaled_inverse(self.fisher(S0, w0, Q, delta, floor, wrt, log))
+
+    def standard_errors(self, S0, w0, Q, delta, floor=None, wrt=PARAMETERS, log=False):
+        """The square roots of the covariance's diagonal as a dict over ``wrt``: ``S0, w0, Q`` (B, J), ``floor``
+        (B,); NaN for a problem :meth:`covariance` could not invert."""
+        cov, _ = self.covariance(S0, w0, Q, delta, floor, wrt, log)
+        se = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+        J = np.atleast_2d(_host(S0)).shape[-1]
+        out, at = {}, 0
+        for k in PARAMETERS:
+            if k in wrt:
+                n = J if k != "floor" else 1
+                out[k] = se[:, at:at + n] if k != "floor" else se[:, at]
+                at += n
+        return out
+
+    def fit(self, S0, w0, Q, delta, floor=None, free=PARAMETERS, max_iter=100, xtol=1e-10, damping=1e-3,
+            max_step=1.0):
+        """Maximise the objective of all B problems at once over the blocks ``free``, from the given start: a damped
+        Fisher scoring (Levenberg-Marquardt) in u = ln theta, the problems in lockstep -- one gradient call and at
+        most one Fisher call per iteration for the whole batch.  Per problem, with lambda starting at ``damping``:
+
+            F_u = F o theta theta^T,  g_u = g o theta        at the accepted point
+            d = solve(F_u + lambda diag(F_u), g_u);   d *= min(1, max_step / max|d|)
+            ll' = ll(exp(u + d))
+            if ll' finite and ll' >= ll:  accept; lambda = max(lambda / 10, 1e-9); converged if max|d| < xtol
+            else:                         reject; lambda = min(10 lambda, 1e9)
+
+        Converged and failed problems are frozen; parameters outside ``free`` keep their bits.  Free parameters must
+        be > 0 (ValueError).  A problem whose start is -inf or that has no used frequency ends with
+        ``converged = False`` and leaves the others alone.  Returns a :class:`SpectralFit`."""
+        (S0, w0, Q, delta, floor), idx, theta = self._fisher_arguments(S0, w0, Q, delta, floor, free, False, "free")
+        if np.any(theta <= 0.0):
+            raise ValueError("free parameters must be > 0 (the fit works in their logarithms)")
+        free = tuple(k for k in PARAMETERS if k in free)
+        B, J = S0.shape
+        full = np.concatenate([S0, w0, Q, (np.zeros(B) if floor is None else floor)[:, None]], axis=1)
+
+        def split(th):
+            """The call arguments at the free parameters ``th`` (the others as given)."""
+            p = full.copy()
+            p[:, idx] = th
+            return p[:, :J], p[:, J:2 * J], p[:, 2 * J:3 * J], delta, (None if floor is None else p[:, 3 * J])
+
+        def value_and_gradient(th):
+            ll, g = self.value_and_grad(*split(th))
+            return ll, np.concatenate([g[k] if k != "floor" else g[k][:, None] for k in PARAMETERS], axis=1)[:, idx]
+
+        u = np.log(theta)
+        ll, g = value_and_gradient(np.exp(u))
+        active = np.isfinite(ll) & (self.last_used > 0) & np.all(np.isfinite(g), axis=1)
+        lam = np.full(B, float(damping))
+        iterations = np.zeros(B, dtype=np.int64)
+        converged = np.zeros(B, dtype=bool)
+        Fu, stale = None, True
+        for _ in range(int(max_iter)):
+            if not active.any():
+                break
+            th = np.exp(u)
+            if stale:
+                Fu = self.fisher(*split(th), wrt=free, log=True)
+                stale = False
+            gu = g * th
+            d = np.zeros_like(u)
+            rows = np.flatnonzero(active)
+            diag = np.eye(len(idx)) * np.diagonal(Fu[rows], axis1=1, axis2=2)[:, None, :]
+            A = Fu[rows] + lam[rows, None, None] * diag
+            try:
+                d[rows] = np.linalg.solve(A, gu[rows][:, :, None])[:, :, 0]
+            except np.linalg.LinAlgError:       # a singular system among them: one by one
+                for i, b in enumerate(rows):
+                    try:
+                        d[b] = np.linalg.solve(A[i], gu[b])
+                    except np.linalg.LinAlgError:
+                        d[b] = np.nan
+            solved = active & np.all(np.isfinite(d), axis=1)
+            d[~solved] = 0.0
+            big = np.max(np.abs(d), axis=1)
+            d *= np.minimum(1.0, float(max_step) / np.where(big > 0.0, big, 1.0))[:, None]
+            step = np.max(np.abs(d), axis=1)
+            ll2, g2 = value_and_gradient(np.exp(u + d))
+            accept = solved & np.isfinite(ll2) & (ll2 >= ll)
+            reject = active & ~accept
+            iterations[active] += 1
+            u[accept] += d[accept]
+            ll[accept], g[accept] = ll2[accept], g2[accept]
+            lam[accept] = np.maximum(lam[accept] / 10.0, 1e-9)
+            lam[reject] = np.minimum(lam[reject] * 10.0, 1e9)
+            done = accept & (step < float(xtol))
+            converged |= done
+            active &= ~done
+            stale = bool(accept.any())
+        a0, aw, aq, _, fl = split(np.exp(u))
+        cov, cov_ok = self.covariance(a0, aw, aq, delta, fl, wrt=free)
+        return SpectralFit(S0=np.array(a0), w0=np.array(aw), Q=np.array(aq),
+                           floor=np.zeros(B) if fl is None else np.array(fl), ll=ll, iterations=iterations,
+                           converged=converged, cov=cov, cov_ok=cov_ok, free=free)
 
 
 def _function():

@@ -804,6 +804,30 @@ int gf_spectral_like(int B, int64_t M, int J, int objective,
                      double *gS0, double *gw0, double *gQ, double *gfloor,
                      double *model, void *stream);
 
+/*
+ * Fisher information of the spectral objectives: per problem the weighted Gram matrix of the model
+ * spectrum's Jacobian over the used frequencies,
+ *     F_b = sum_k v_k grad S_b(w_k) grad S_b(w_k)^T,    v_k = n_k / S_b(w_k)^2 (whittle),  v_k = 1 / e_k^2 (chi2)
+ * the Gauss-Newton matrix of chi2 and the expected information of Whittle (minus the Hessian where P = S).  The
+ * arguments, limits, status codes and the rule for USED frequencies are gf_spectral_like's; P_k enters through that
+ * rule alone.
+ *   fisher [B][P][P], P = 3 J + 1, in the parameter order S0_0 .. S0_{J-1}, w0_0 .., Q_0 .., floor: exactly symmetric,
+ *     diagonal >= 0; unused frequencies add exact zeros (no used frequency: a matrix of zeros)
+ *   used [B], info [B]: what gf_spectral_like returns for the same inputs; where S_b(w_k) is not > 0 at a used
+ *     frequency the problem's whole matrix is NaN (info = k + 1), the other problems are not touched
+ *   work: gf_spectral_fisher_work(B, M, J) doubles (0 for a shape outside the limits); a problem's share, and so its
+ *     result, depends on M and J alone
+ * gf_spectral_fisher_slab(): the frequencies summed into one partial; the partials are added in slab order.  No
+ * atomics: a problem's matrix is bit-identical from run to run and does not depend on the other problems of the call.
+ */
+int gf_spectral_fisher_slab(void);
+int64_t gf_spectral_fisher_work(int B, int64_t M, int J);
+int gf_spectral_fisher(int B, int64_t M, int J, int objective,
+                       const double *S0, const double *w0, const double *Q,
+                       const double *delta, const double *floor, const double *omega,
+                       const double *power, int64_t power_bs, const double *weight, int64_t weight_bs,
+                       double *work, double *fisher, int64_t *used, int32_t *info, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
