@@ -12,11 +12,12 @@ from .core import (  # noqa: F401
 from . import scale  # noqa: F401
 from .gp import GaussianProcess, ConditionalDistribution, LinAlgError  # noqa: F401
 from .batch import (BatchedLogLikelihood, log_likelihood_batch, BatchedSampler, sample_batch,  # noqa: F401
-                    predict_batch)
+                    predict_batch, sample_conditional_batch)
 from . import terms  # noqa: F401
 from .psd import PowerSpectrum, bin_power_spectrum  # noqa: F401
 from .interp import interpolate_missing_data, stitch_quarters  # noqa: F401
 from . import spectral  # noqa: F401
+from . import conddraw  # noqa: F401
 from .spectral import SpectralLikelihood  # noqa: F401
 
 __version__ = "0.1.0"

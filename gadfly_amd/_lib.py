@@ -21,7 +21,7 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dens
            os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip"),
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
-           os.path.join(CSRC, "gadfly_fisher.hip")]
+           os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -132,6 +132,14 @@ SIGNATURES = {
                                  _vp, _vp, _vp]),
     "gf_predict_batch_at": (_int, [_int, _i64, _i64, _int, _int] + [_vp] * 6
                             + [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp]),
+    "gf_solve_batch_rhs_block": (_int, [_int]),
+    "gf_solve_batch_rhs_work": (_i64, [_i64, _int, _int, _i64]),
+    "gf_solve_batch_rhs": (_int, [_int, _i64, _int, _int, _int] + [_vp] * 7
+                           + [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64]
+                           + [_vp, _vp, _i64, _i64, _vp, _vp] + [_vp]),
+    "gf_predict_batch_at_rhs_block": (_int, []),
+    "gf_predict_batch_at_rhs": (_int, [_int, _i64, _i64, _int, _int, _int] + [_vp] * 6
+                                + [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64] + [_vp]),
     "gf_var_batch_work": (_i64, [_i64, _int, _i64, _i64]),
     "gf_var_batch": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_vp, _i64, _vp, _i64, _vp, _i64]
                      + [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7 + [_vp]),

@@ -277,6 +277,8 @@ class BatchedLogLikelihood:
         self.steady_reruns = 0
         self._viol_flags = {}               # id(out) -> violation flags of the evaluations not yet resolved
         self._last_cond = None
+        #: exposure times of the kernels of construction (0: not exposure-integrated), for :meth:`sample_conditional`
+        self._delta0 = self._deltas_of(kernels)
 
     @property
     def B(self):
@@ -285,6 +287,7 @@ class BatchedLogLikelihood:
     def pack(self, kernels):
         pk = _Pack(self.engine.pack_coefficients([k.get_device_coefficients() for k in kernels]))
         pk.psd_safe = all(_sho_only(k, self._dt_min, self._t_abs_max) for k in kernels)
+        pk.delta = self._deltas_of(kernels)
         return pk
 
     def pack_parameters(self, S0, w0, Q, delta):
@@ -295,6 +298,7 @@ class BatchedLogLikelihood:
                            and np.all(np.asarray(Q) > 0.0)
                            and all(_exposure_resolved(float(dl), self._dt_min, self._t_abs_max)
                                    for dl in np.atleast_1d(np.asarray(delta, dtype=np.float64))))
+        pk.delta = np.broadcast_to(np.asarray(delta, dtype=np.float64).reshape(-1), (self.B,)).copy()
         return pk
 
     #: cap on the gradient workspace of one call in bytes (:meth:`value_and_grad`): larger batches run in groups
@@ -613,6 +617,147 @@ class BatchedLogLikelihood:
             e1.synchronize()
         return sum(a.elapsed_time(b) for a, b in events)
 
+    # -- R right-hand sides per factorisation, posterior draws ----------------------------------
+
+    @staticmethod
+    def _deltas_of(kernels):
+        """Exposure time per kernel (0 for one that is not exposure-integrated)."""
+        return np.array([float(getattr(k, "delta", 0.0) or 0.0) for k in kernels], dtype=np.float64)
+
+    def _host_axes(self):
+        """The observed stamps on the host, a list of B series cut to their real rows (copied back once)."""
+        if getattr(self, "_t_host", None) is None:
+            t = self.engine.t.cpu().numpy()
+            rows = [t.shape[1]] * self.B if self.rows is None else [int(n) for n in self.rows]
+            self._t_host = [t[b if t.shape[0] > 1 else 0, :n].copy() for b, n in enumerate(rows)]
+        return self._t_host
+
+    def _rhs_tensor(self, y):
+        """y of shape (B, N), (B, R, N), (N,) or (R, N) shared -> ((1 or B, R, N) device tensor, restore(x) that gives
+        a (B, R, N) result the layout of y: a shared y gives (B, N) / (B, R, N))."""
+        eng = self.engine
+        torch = eng.torch
+        B, N = self.B, eng.N
+        y = torch.as_tensor(y).to(dtype=torch.float64, device=eng.device)
+        if y.ndim == 0 or y.shape[-1] != N or y.ndim > 3:
+            raise ValueError(f"right-hand sides of shape {tuple(y.shape)} for {B} problems of {N} rows")
+        if y.ndim == 1:
+            return y[None, None, :], lambda x: x[:, 0]
+        if y.ndim == 3:
+            if y.shape[0] != B:
+                raise ValueError(f"right-hand sides of shape {tuple(y.shape)} for {B} problems of {N} rows")
+            return y, lambda x: x
+        if y.shape[0] == B:                 # (B, N): one right-hand side per problem ((R, N) with R = B reads so too)
+            return y[:, None, :], lambda x: x[:, 0]
+        return y[None], lambda x: x
+
+    def _solve_rhs(self, y, pack_or_kernels, **want):
+        from .predict import check_width, solve_batch_rhs
+        if self.rows is not None:
+            raise NotImplementedError("right-hand sides for a ragged batch are not supported: pass per-series data "
+                                      "to a batch of its own")
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        y3, restore = self._rhs_tensor(y)
+        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
+        res = solve_batch_rhs(eng, Jr, Jc, real, comp, diag_add, y3, self.predict_workspace_bytes, **want)
+        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self._predict_events, self._predict_at_events = res["events"], []
+        self.last_predict_ll, self.last_predict_info = res["ll"], res["info"]
+        return res, restore
+
+    def apply_inverse_device(self, y, pack_or_kernels=None):
+        """alpha = (K_b + diag)^-1 y for B kernels at once, celerite2's ``apply_inverse``: ``y`` of shape (B, N),
+        (B, R, N), or (N,) / (R, N) shared by all problems (host array or device tensor; the mean is NOT subtracted);
+        returns a float64 device tensor of the same layout ((B, N) / (B, R, N) for a shared y).  The R right-hand sides
+        of a problem go through ONE pass over its rows (``gf_solve_batch_rhs``).  NaN rows where the matrix is not
+        positive definite; W > 63 raises ``NotImplementedError``.  No host synchronisation."""
+        res, restore = self._solve_rhs(y, pack_or_kernels, want_alpha=True, want_mu=False)
+        return restore(res["alpha"])
+
+    def log_likelihood_device(self, y, pack_or_kernels=None):
+        """The log-likelihoods of R data vectors per kernel (zero mean: pass y - mean), (B, R) on the device, from one
+        factorisation per block of right-hand sides; ``y`` as :meth:`apply_inverse_device`.  -inf where the matrix is
+        not positive definite."""
+        res, _ = self._solve_rhs(y, pack_or_kernels, want_alpha=False, want_mu=False)
+        return res["ll"]
+
+    def sample_conditional_device(self, pack_or_kernels=None, t=None, size=None, normals=None, seed=None,
+                                  include_mean=True):
+        """Draws from the conditional distribution of the B processes given their data, exact and with
+        every cross-covariance between the queries, in O((N + M) W^2) per draw: no M x M matrix is formed.
+
+        Returns a float64 device tensor (B, M), or (B, size, M) with ``size``, at the new times ``t`` -- every form
+        :meth:`predict_device` takes as ``t=`` -- or (B, N) / (B, size, N) at the observed stamps without ``t``; a
+        list of B tensors where ``t`` was a list or the batch is ragged.  The draws are of the noise-free process
+        (what ``predict`` gives the mean and variance of) and are NOT centred: they are draws around the data.
+
+        ``normals=(eps, eta)`` fixes the draw: standard normals of shapes (B, size, Nu) and (B, size, N) (no ``size``
+        axis without ``size``), Nu the length of the union of observed and query stamps; lists of per-problem arrays
+        for ragged layouts, shapes as :func:`gadfly_amd.conddraw.union_axes` reports them.  Otherwise they come from a
+        device generator seeded with ``seed`` as :class:`BatchedSampler` seeds its own: the same seed gives the same
+        bits.  ``size`` draws are ``size`` right-hand sides of one solve, ``gf_solve_batch_rhs``'s block of them per
+        factorisation; the union-axis prior draws cost one fused sweep each.
+
+        :attr:`last_predict_ll` ((B, size): the residuals' log-likelihoods), :attr:`last_predict_info`,
+        :attr:`last_predict_plan` and :attr:`last_predict_device_ms` are filled from the solve as :meth:`predict_device`
+        fills them; :attr:`last_conditional_info` holds the failing row of the UNION-axis factor per problem (0: none;
+        such a problem's draws are NaN, the others are unaffected) and :attr:`last_conditional_ms` the device time
+        split into sweeps, assembly, solve and the new-times launch.
+
+        Raises before anything is enqueued: ``NotImplementedError`` for W > 63; ``ValueError`` for unsorted queries,
+        ``normals`` of the wrong shape, a mean that varies along the rows together with ``t``, and -- for an
+        exposure-integrated kernel -- a query closer than the exposure time to a different observed stamp or to
+        another query (coincident stamps are merged and fine).  Packs made from raw coefficient arrays carry no
+        exposure time and are not checked.  ``kernel=component`` draws are not offered."""
+        from . import conddraw
+        from .predict import check_width
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        if size is not None:
+            size = int(size)
+            if size < 1:
+                raise ValueError("size must be a positive number of draws")
+        ts = nq = mean = None
+        as_list = self.rows is not None
+        if t is not None:
+            ts, nq, as_list = self._query_times(t)
+            mean = self._query_mean(include_mean)
+        if pack_or_kernels is None:
+            pack, deltas = self._pack0, self._delta0
+        else:
+            pack = self._host_pack(pack_or_kernels)
+            deltas = getattr(pack_or_kernels, "delta", None)
+            if deltas is None and not isinstance(pack_or_kernels, tuple):
+                deltas = self._deltas_of(pack_or_kernels)
+        z, info, res, events = conddraw.conditional_draws(self, pack, self._host_axes(), ts, nq, deltas, size, normals,
+                                                          seed, mean, include_mean)
+        self.last_predict_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self._predict_events, self._predict_at_events = res["events"], events["at"]
+        self.last_predict_ll = res["ll"] if self._pad_corr is None else res["ll"] + self._pad_corr[:, None]
+        self.last_predict_info = res["info"]
+        self.last_conditional_info = info
+        self._cond_events = events
+        if size is None:
+            z = z[:, 0]
+        if as_list:
+            lens = self.rows if t is None else (nq if nq is not None else [ts.shape[1]] * self.B)
+            return [z[b, ..., :int(n)] for b, n in enumerate(lens)]
+        return z
+
+    @property
+    def last_conditional_ms(self):
+        """Device time of the last :meth:`sample_conditional_device` call by part (synchronises): ``sweeps`` (the
+        union-axis prior draws), ``assembly``, ``solve``, ``at`` (the new-times launch)."""
+        return {k: self._events_ms(v) for k, v in self._cond_events.items()}
+
+    def sample_conditional(self, pack_or_kernels=None, t=None, size=None, normals=None, seed=None, include_mean=True):
+        """:meth:`sample_conditional_device`, returned as numpy (a list of arrays where that returns a list)."""
+        return self._to_host(self.sample_conditional_device(pack_or_kernels, t=t, size=size, normals=normals,
+                                                            seed=seed, include_mean=include_mean))
+
     def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None,
                 return_var=False):
         """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch or a list of query times)."""
@@ -771,6 +916,15 @@ def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, de
     the conditional variances, ``(mu, var)``."""
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
                                 device=device).predict(kernel=kernel, t=t_pred, return_var=return_var)
+
+
+def sample_conditional_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, t_pred=None, size=None, normals=None,
+                             seed=None, device=None):
+    """One-shot form of :meth:`BatchedLogLikelihood.sample_conditional_device`: posterior draws of B kernels given
+    their data, at ``t_pred`` (what that method takes as ``t=``) or at the observed stamps, as a float64 device tensor
+    (a list for ragged layouts)."""
+    return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean, device=device
+                                ).sample_conditional_device(t=t_pred, size=size, normals=normals, seed=seed)
 
 
 def _is_series_list(x):

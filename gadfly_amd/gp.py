@@ -654,6 +654,42 @@ class GaussianProcess:
             result = result + self._to_device(np.broadcast_to(self._mean_value, (self._size,)).copy())
         return result - (result.mean(dim=0) if result.ndim == 2 else result.mean())
 
+    def sample_conditional(self, y, t=None, size=None, normals=None, seed=None, include_mean=True,
+                           return_quantity=False):
+        """Draws from the conditional distribution given ``y`` -- at the new times ``t`` or at the observed ones --
+        WITHOUT the M x M covariance: Matheron's rule on the union of observed and query stamps,
+        O((N + M) W^2) per draw, through :meth:`gadfly_amd.BatchedLogLikelihood.sample_conditional_device` with a
+        batch of one.  Returns numpy (M,) or (size, M) [ppm]; the draws are of the noise-free process and are not
+        centred.  ``normals=(eps, eta)`` of shapes (Nu,), (N,) -- (size, Nu), (size, N) with ``size`` -- fix the draw,
+        ``seed`` seeds the device generator otherwise.  Extension; not in the reference.
+
+        The batch-of-one route runs one wave for the whole problem and is slow per row (DESIGN.md 3.9 leg (c)): the
+        one-wave kernels are built for many problems side by side.  It is still the only route that does not need the
+        M x M matrix -- :meth:`ConditionalDistribution.sample` (``condition(y, t).sample()``), the celerite2-compatible
+        dense route, forms it and costs O(M^3).  Kernels wider than W = 63 raise ``NotImplementedError``."""
+        from .batch import BatchedLogLikelihood
+        if _units.has_unit(y):
+            y = self._flux_to_ppm(y)
+        if t is not None and (_units.is_time(t) or _units.has_unit(t)):
+            t = self._time_to_freq(t)
+        y = self._process_input(y, require_vector=True)
+        if t is not None:
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            if t.ndim != 1:
+                raise ValueError("dimension mismatch")
+        resid = y - self._mean(self._t)
+        bll = BatchedLogLikelihood([self.kernel], self._t, resid[None, :], diag=self._diag, device=self._device)
+        if normals is not None:
+            if not isinstance(normals, (tuple, list)) or len(normals) != 2:
+                raise ValueError("normals must be the pair (eps, eta)")
+            normals = tuple(np.asarray(x, dtype=np.float64)[None] for x in normals)
+        out = bll.sample_conditional(t=t, size=size, normals=normals, seed=seed, include_mean=False)[0]
+        if include_mean:
+            out = out + self._mean(self._t if t is None else t)
+        if return_quantity:
+            return self._ppm_to_flux(out)
+        return out
+
     def condition(self, y, t=None, include_mean=True, kernel=None,
                   return_quantity=False):
         """Condition the GP on observations ``y`` (reference gp.py:206-239)."""

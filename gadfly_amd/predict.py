@@ -6,7 +6,9 @@ the kernel explains for B problems at once (``gf_solve_batch``: a checkpointed f
 backwards, no stored factor); this module stacks the component's coefficients.  ``gf_predict_batch_at`` then carries
 alpha to new times t* (DESIGN.md 3.11): the two sorted-axis sums of the full kernel or of a component, no workspace.
 ``gf_var_batch`` is ``gf_solve_batch`` with one more backward recurrence: the inverse diagonal h, the
-conditional variances at the observed times and at new ones, the staged queries counted in its workspace.  The groups
+conditional variances at the observed times and at new ones, the staged queries counted in its workspace.
+``gf_solve_batch_rhs`` and ``gf_predict_batch_at_rhs`` are the first two for R right-hand sides per
+problem through one pass over the rows, column by column the same bits.  The groups
 under the byte cap, the query axes and the launches are :mod:`gadfly_amd.rowcall`'s.
 """
 import numpy as np
@@ -16,7 +18,7 @@ from . import _lib
 from .rowcall import GroupedCall, check_pack_batch, group_plan, query_axes
 
 __all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "predict_at", "variance_plan",
-           "variance_batch", "DEFAULT_WORKSPACE_BYTES"]
+           "variance_batch", "rhs_workspace_plan", "solve_batch_rhs", "predict_at_rhs", "DEFAULT_WORKSPACE_BYTES"]
 
 #: default cap on the workspace of one call (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = _lib.GF_SOLVE_WORKSPACE_BYTES
@@ -168,3 +170,83 @@ def variance_batch(engine, Jr, Jc, real, comp, diag_add, ts=None, nobs=None, nq=
             g.nb, N, Jr, Jc, *g.coef[0], *g.data, g.at(ts, qbs), qbs, M, g.at(nobs), g.at(nq), int(seg), *g.work,
             *(g.at(x, N) for x in outs.values()), g.at(var_at, M), g.at(ll), g.at(info), g.stream))
         return dict(ll=ll, info=info, var_at=var_at, events=events, **rc.plan, **outs)
+
+
+def rhs_workspace_plan(N, W, B, R, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0):
+    """(doubles per problem, problems per group, number of groups) of a gf_solve_batch_rhs call with R right-hand
+    sides per problem: every block of right-hand sides has its own checkpoints and staged rows, so R counts."""
+    check_width(W)
+    if int(R) < 1:
+        raise ValueError("at least one right-hand side is needed")
+    return group_plan(_lib.load().gf_solve_batch_rhs_work(int(N), int(W), int(R), int(seg)), B, cap_bytes,
+                      f"no solve workspace for N = {N}, W = {W}, R = {R}, seg = {seg}")
+
+
+def solve_batch_rhs(engine, Jr, Jc, real, comp, diag_add, y, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0,
+                    want_alpha=True, want_mu=True):
+    """Enqueue ``gf_solve_batch_rhs`` over an engine's time axes and diagonal for R right-hand sides per problem:
+    ``y`` a float64 device tensor (B, R, N), or (1, R, N) / (R, N) shared by all problems (the engine's own data are
+    not looked at).  Coefficients as :func:`solve_batch`, no component.  Returns a dict of device tensors -- ``alpha``,
+    ``mu`` ((B, R, N) each, None where not asked for), ``ll`` (B, R), ``info`` (B,) -- with the plan and ``events`` as
+    :func:`solve_batch`.  Column r has the bits :func:`solve_batch` gives for ``y[:, r]`` as data.  No host
+    synchronisation."""
+    W = Jr + 2 * Jc
+    if (Jr, Jc) != engine._struct0:
+        raise ValueError("coefficient pack does not match the batch structure")
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, diag_add)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3 or y.shape[0] not in (1, B) or y.shape[1] < 1 or y.shape[2] != N or y.dtype != torch.float64:
+        raise ValueError(f"right-hand sides of shape {tuple(y.shape)} for a batch of {B} problems of {N} rows")
+    R = int(y.shape[1])
+    plan = rhs_workspace_plan(N, W, B, R, cap_bytes, seg)
+    f64 = dict(dtype=torch.float64, device=engine.device)
+    with torch.cuda.device(engine.device):
+        y = y.to(engine.device).contiguous()
+        ybs = 0 if y.shape[0] == 1 else R * N
+        rc = GroupedCall(engine, "gf_solve_batch_rhs", plan, (real, comp, diag_add))
+        ll = torch.empty((B, R), **f64)
+        info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
+        alpha = torch.empty((B, R, N), **f64) if want_alpha else None
+        mu = torch.empty((B, R, N), **f64) if want_mu else None
+        events = rc.run(lambda g: g.launch(
+            g.nb, N, R, Jr, Jc, *g.coef[0], *g.data[:4], g.at(y, ybs), ybs, N, int(seg), *g.work,
+            g.at(alpha, R * N), g.at(mu, R * N), R * N, N, g.at(ll, R), g.at(info), g.stream))
+        return dict(alpha=alpha, mu=mu, ll=ll, info=info, events=events, **rc.plan)
+
+
+def predict_at_rhs(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):
+    """Enqueue ``gf_predict_batch_at_rhs``: :func:`predict_at` for ``alpha`` (B, R, N) on the device
+    (:func:`solve_batch_rhs`).  Returns dict(``mu`` (B, R, M) device tensor, ``events``); rows from ``nq[b]`` on are
+    never written.  Column r has the bits :func:`predict_at` gives for ``alpha[:, r]``.  No host synchronisation."""
+    W = Jr + 2 * Jc
+    if W < 1:
+        raise ValueError("the kernel has no terms")
+    check_width(W)
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, np.zeros(B))
+    if alpha.ndim != 3 or alpha.shape[0] != B or alpha.shape[1] < 1 or alpha.shape[2] != N \
+            or alpha.dtype != torch.float64:
+        raise ValueError(f"alpha of shape {tuple(alpha.shape)} does not hold the batch's ({B}, R, {N}) rows")
+    R = int(alpha.shape[1])
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    lib, p = engine.lib, _lib.ptr
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ts, M, nobs, nq = query_axes(engine, ts, nobs, nq)
+        alpha = alpha.contiguous()
+        mu = torch.empty((B, R, M), **f64)
+        cr_ = torch.as_tensor(np.ascontiguousarray(real, dtype=np.float64), **f64)
+        cc_ = torch.as_tensor(np.ascontiguousarray(comp, dtype=np.float64), **f64)
+        t = engine.t
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        st = lib.gf_predict_batch_at_rhs(
+            B, N, M, R, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]),
+            p(t), engine._bs(t), p(nobs), p(ts), engine._bs(ts), p(nq),
+            p(alpha), R * N, N, p(mu), R * M, M, stream)
+        _lib.check(st, "gf_predict_batch_at_rhs")
+        e1.record()
+    return dict(mu=mu, events=[(e0, e1)])

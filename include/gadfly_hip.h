@@ -22,6 +22,11 @@
  *   gf_var_batch        the same plus the diagonal of K* - K*^T (K + diag)^-1 K* (celerite2's
  *                       ConditionalDistribution.variance)   <- gp.py:241-306 (predict(..., return_var=True)) for B
  *                                                      kernels at once
+ *   gf_solve_batch_rhs / gf_predict_batch_at_rhs
+ *                       gf_solve_batch / gf_predict_batch_at for R right-hand sides per problem through one pass over
+ *                       the rows: celerite2's apply_inverse of a matrix, the log-likelihoods of R data vectors and the
+ *                       operator of exact conditional draws (no celerite2 counterpart beyond the dense
+ *                       ConditionalDistribution.sample) for B kernels at once
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HIP) unless marked "host"; float64 throughout;
@@ -736,6 +741,47 @@ int gf_predict_batch_at(int B, int64_t N, int64_t M, int Jr, int Jc,
                         const double *ts, int64_t ts_bs, const int64_t *nq,
                         const double *alpha, int64_t alpha_bs,
                         double *mu, int64_t mu_bs, void *stream);
+
+/*
+ * gf_solve_batch for R right-hand sides per problem: alpha_r = K^-1 y_r, mu_r = y_r - diag alpha_r and
+ * the log-likelihood of every y_r, the factor rows, decays, state update and pivot of each row made ONCE for the RB =
+ * gf_solve_batch_rhs_block(W) right-hand sides a wave carries.  The ceil(R / RB) blocks of a problem are the grid's
+ * second dimension (they run side by side, each on its own slice of the workspace).  No component.
+ *   coefficients, t, diag, seg as gf_solve_batch
+ *   y [B][R][N]: batch stride y_bs (0 = shared by all problems), right-hand-side stride y_rs >= N
+ *   work: work_bs >= gf_solve_batch_rhs_work(N, W, R, seg) doubles per problem
+ *   alpha, mu [B][R][N] (either may be NULL): batch stride out_bs >= R N, right-hand-side stride out_rs >= N
+ *   ll [B][R] (contiguous), info [B]
+ * Column r of alpha, mu and ll has the bits gf_solve_batch gives for y_r alone, for every R, seg and batch; info is
+ * gf_solve_batch's.  A problem whose pivot fails gets NaN in every row of every right-hand side, -inf in its row of ll
+ * and the 1-based failing row in info; the other problems are unaffected.  No atomics.
+ * Returns -1 for bad shapes (R < 1 among them), strides or null pointers, -3 for W > 63.
+ */
+int gf_solve_batch_rhs_block(int W);
+int64_t gf_solve_batch_rhs_work(int64_t N, int W, int R, int64_t seg);
+int gf_solve_batch_rhs(int B, int64_t N, int R, int Jr, int Jc,
+                       const double *ar, const double *cr, const double *ac, const double *bc,
+                       const double *cc, const double *dc, const double *diag_add,
+                       const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                       const double *y, int64_t y_bs, int64_t y_rs, int64_t seg, double *work, int64_t work_bs,
+                       double *alpha, double *mu, int64_t out_bs, int64_t out_rs, double *ll, int32_t *info,
+                       void *stream);
+
+/*
+ * gf_predict_batch_at for R columns of alpha per problem: generator rows, sincos and exp made once per
+ * observed row and per query, the two sums carried for gf_predict_batch_at_rhs_block() columns at a time (the blocks
+ * are the grid's second dimension).  Same tie rule, nobs / nq semantics and NaN propagation.
+ *   alpha [B][R][N]: strides alpha_bs >= R N, alpha_rs >= N;  mu [B][R][M]: strides mu_bs >= R M, mu_rs >= M
+ * Column r of mu has the bits gf_predict_batch_at gives for alpha_r alone.  No workspace, no LDS, no atomics.
+ */
+int gf_predict_batch_at_rhs_block(void);
+int gf_predict_batch_at_rhs(int B, int64_t N, int64_t M, int R, int Jr, int Jc,
+                            const double *ar, const double *cr, const double *ac,
+                            const double *bc, const double *cc, const double *dc,
+                            const double *t, int64_t t_bs, const int64_t *nobs,
+                            const double *ts, int64_t ts_bs, const int64_t *nq,
+                            const double *alpha, int64_t alpha_bs, int64_t alpha_rs,
+                            double *mu, int64_t mu_bs, int64_t mu_rs, void *stream);
 
 /*
  * Conditional variances of B problems: the second half of celerite2's
