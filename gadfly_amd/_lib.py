@@ -73,6 +73,9 @@ SIGNATURES = {
                          + [_vp] * 3 + [_vp]),
     "gf_steady_finish_window": (_int, [_int, _i64, _int, _int, _int, _int] + [_vp] * 5 + [_vp, _i64, _vp, _i64]
                                 + [_vp] * 3 + [_i64, _i64] + [_vp]),
+    "gf_steady_chunk_size": (_i64, [_i64, _int]),
+    "gf_steady_finish_chunked": (_int, [_int, _i64, _int, _int, _int, _int] + [_vp] * 5 + [_vp, _i64, _vp, _i64]
+                                 + [_vp] * 3 + [_i64, _i64, _int, _vp] + [_vp]),
     "gf_sample_fused": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int] + [_vp] * 8
                         + [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_vp]),
     "gf_chunk_sweep": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int] + [_vp] * 8

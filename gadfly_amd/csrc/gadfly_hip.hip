@@ -1553,7 +1553,26 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // STORE = true: the rows leave as d and z (k_steady_tail, tile by tile); STORE = false: no row is stored, every lane
 // keeps the running sum of z^2 of its row slot over all blocks, and the wave adds the problem's tail to acc
 // (k_steady_finish: rows [switch row, N) of the whole series in one launch).
-template <int ROWS, bool STORE>
+//
+// CHUNK != 0 (STORE = false only): one wave of the chunked finishing launch (k_steady_chunk, below).  Behind the
+// switch a block is linear and time-invariant in the state -- z = u + Q s, s' = M s + K u --, so a chunk of n blocks
+// from s_in ends in M^n s_in + (its end state from zero), and the chunks of one tail run side by side:
+//   CHUNK = 1 (pass A): wave (problem, c) runs the rows [sw + c chunk_rows, sw + (c + 1) chunk_rows) -- chunk 0 from the
+//     header's state, keeping its sum of z^2; the others from zero, for their end state alone; the last one (c > 0)
+//     not at all -- and writes the end state to its workspace slot;
+//   CHUNK = 3 (one wave per problem of three chunks or more, no spacing test): M, the full block's own code on the
+//     2 Jc unit states with u = 0, column by column into the workspace's P;
+//   CHUNK = 2 (pass B, behind k_steady_chunk_power, which leaves P = M^n there): wave c >= 1 forms its true s_in,
+//     s_in[1] = s_out[0], s_in[c + 1] = s_out0[c] + P s_in[c], runs its rows from it and writes its sum of z^2 to its
+//     slot; the last chunk writes the header's state.
+// No two waves write different values to one word: acc is k_steady_chunk_sum's, the header's state the last chunk's,
+// ST_VIOL takes the same value from any wave, and h is computed by every wave for itself (ST_H, ST_HOK read only).
+// chunk_rows is a multiple of 16 blocks, so every chunk starts on the problem's own grid of groups: u keeps the bits
+// of the one-wave launch.
+constexpr int CH_P = 64 * 64;       // workspace of a problem: P[64][64] over (s_r[0..31], s_i[0..31]), then the slots
+constexpr int CH_SLOT = 72;         // a chunk's slot: [0, 64) its end state, [64] its sum of z^2
+
+template <int ROWS, bool STORE, int CHUNK = 0>
 __device__ __forceinline__ void
 steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const double gap,
                  const double *__restrict__ ac_, const double *__restrict__ bc_,
@@ -1561,7 +1580,9 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
                  const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
                  double *__restrict__ d_, double *__restrict__ z_, const int32_t *__restrict__ info,
                  double *__restrict__ steady_, double *__restrict__ acc_,
-                 const int64_t sw_lo, const int64_t sw_hi) {
+                 const int64_t sw_lo, const int64_t sw_hi,
+                 const int64_t chunk_rows = 0, double *__restrict__ ws_ = nullptr, const int64_t ws_ld = 0) {
+    static_assert(CHUNK == 0 || !STORE, "the chunked launch stores no row");
     constexpr int JT = ROWS / 2;                    // term slots (Jc <= JT <= 32; slots from Jc on are zero)
     // the finishing instance's form of a block: the state update on both half-waves (lane 32 h + k: term k, rows 32 h ..
     // 32 h + 31 of a block), and H off the chain from one block's state to the next, z = H (y + C s) = H y + Q s with
@@ -1577,6 +1598,26 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     if constexpr (!STORE) { if (sw < sw_lo || sw >= sw_hi) return; }    // another launch's problem: nothing touched
     const int64_t nb = sw > n_first ? sw - n_first : 0;     // first tail row of this tile (local)
     if (nb >= N) return;
+    // the rows [r_lo, r_hi) of this wave: the whole tail, or one chunk of it
+    int64_t r_lo_ = nb, r_hi_ = N;
+    int ch = 0, nch = 1;
+    double *__restrict__ wsp = nullptr;
+    if constexpr (CHUNK != 0) {
+        ch = blockIdx.y;
+        nch = (int)((N - nb + chunk_rows - 1) / chunk_rows);
+        wsp = ws_ + (size_t)pr * ws_ld;
+        if constexpr (CHUNK == 3) {
+            if (nch < 3) return;                    // no chunk takes a correction by P
+            r_hi_ = nb + 128 * (int64_t)Jc;         // 2 Jc blocks; no row of the series is read for them
+        } else {
+            if (ch >= nch) return;
+            if (CHUNK == 1 && ch > 0 && ch == nch - 1) return;
+            if (CHUNK == 2 && ch == 0) return;
+            r_lo_ = nb + ch * chunk_rows;
+            r_hi_ = (N - r_lo_ > chunk_rows) ? r_lo_ + chunk_rows : N;
+        }
+    }
+    const int64_t r_lo = r_lo_, r_hi = r_hi_;
     const double *__restrict__ tg = t_ + (size_t)pr * t_bs + n_first;
     const double *__restrict__ yg = y_ + (size_t)pr * y_bs + n_first;
     double *__restrict__ dg = STORE ? d_ + (size_t)pr * N : nullptr;
@@ -1639,6 +1680,35 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     const bool gain = FOLD || lane < 32;
     const double Gr = gain ? hdr[ST_GR + (lane & 31)] : 0.0, Gi = gain ? hdr[ST_GI + (lane & 31)] : 0.0;
     double sr = (lane < 32) ? hdr[ST_SR + (lane & 31)] : 0.0, si = (lane < 32) ? hdr[ST_SI + (lane & 31)] : 0.0;
+    if constexpr (CHUNK == 1) {
+        if (ch > 0) { sr = 0.0; si = 0.0; }
+    }
+    if constexpr (CHUNK == 2) {
+        // this chunk's true incoming state from the end states of pass A, lane = element of (s_r[0..31], s_i[0..31]):
+        // v = s_out[0];  v <- s_out0[c'] + P v  for c' = 1 .. ch - 1, v by LDS broadcast, P's row from memory
+        const double *__restrict__ slot = wsp + CH_P;
+        const double *__restrict__ prow = wsp + 64 * lane;
+        double v = slot[lane];
+        for (int cp = 1; cp < ch; ++cp) {
+            wave_lds_fence();
+            s_z[lane] = v;
+            wave_lds_fence();
+            double a0 = slot[cp * CH_SLOT + lane], a1 = 0.0;
+#pragma unroll 4
+            for (int k = 0; k < 64; k += 2) {
+                const double2 vv = ((const double2 *)s_z)[k >> 1];
+                a0 = fma(prow[k], vv.x, a0);
+                a1 = fma(prow[k + 1], vv.y, a1);
+            }
+            v = a0 + a1;
+        }
+        wave_lds_fence();
+        s_z[lane] = v;
+        wave_lds_fence();
+        sr = (lane < 32) ? s_z[lane] : 0.0;
+        si = (lane < 32) ? s_z[lane + 32] : 0.0;
+        wave_lds_fence();
+    }
     const double l2r = fma(lr, lr, -li * li), l2i = 2.0 * lr * li;  // lambda^2
     const double lgr = fma(lr, Gr, -li * Gi), lgi = fma(lr, Gi, li * Gr);   // lambda G
     double l32r = l2r, l32i = l2i;                                  // FOLD: lambda^32 joins the two half-blocks
@@ -1665,8 +1735,10 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             hv = (lane == m) ? hm : hv;
         }
         hh[lane] = hv;
-        hdr[ST_H + lane] = hv;
-        if (lane == 0) hdr[ST_HOK] = 1.0;
+        if constexpr (CHUNK == 0) {                 // (a chunk's wave keeps h to itself: its neighbours may be reading)
+            hdr[ST_H + lane] = hv;
+            if (lane == 0) hdr[ST_HOK] = 1.0;
+        }
     }
     if constexpr (!FOLD) s_p[lane] = 0.0;
     else if (lane < 16) s_h[lane] = 0.0;
@@ -1706,7 +1778,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     const int64_t last = N - 1;
     auto row_of = [&](const int64_t cb) { const int64_t i = cb + lane; return i < last ? i : last; };
     bool viol = false;
-    double t_nx = tg[row_of(nb)], tp_nx = tg[row_of(nb) - 1];
+    double t_nx = tg[row_of(r_lo)], tp_nx = tg[row_of(r_lo) - 1];
     // the pieces every form of a block shares: term k of p (or of Q s) against the broadcast (s_r, s_i), even terms to
     // x0 and odd ones to x1; the state over two rows z_j, z_j+1, and over one
     auto add_term = [&](const int k, const double2 sv, double &x0, double &x1) {
@@ -1816,15 +1888,29 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         sr = half ? 0.0 : fma(jr, slr, fma(-ji, sli, sur));
         si = half ? 0.0 : fma(jr, sli, fma(ji, slr, sui));
     };
-    int64_t cb = nb;
+    int64_t cb = r_lo;
     // A group: its phase, then its blocks.  The full blocks: one basic block each, in stages.  A stage ends in a
     // scheduling barrier, so that its LDS reads are issued a stage before the FMAs that take them and no further ahead
     // (the registers hold Q): the s broadcasts in groups of FG terms, z of the state update eight rows ahead.
-    while (cb < N) {
-    group_phase(cb);
+    if constexpr (CHUNK == 3) {                     // M is the block's map at u = 0; the unused columns of P are zero
+        for (int i = lane; i < 16 * SU; i += 64) s_u[i] = 0.0;
+        for (int i = lane; i < 64 * (32 - Jc); i += 64) {
+            const int r = i / (32 - Jc), k = Jc + i % (32 - Jc);
+            wsp[64 * r + k] = 0.0;
+            wsp[64 * r + 32 + k] = 0.0;
+        }
+        wave_lds_fence();
+    }
+    while (cb < r_hi) {
+    if constexpr (CHUNK != 3) group_phase(cb);
     const double *ub = s_u + lane;                  // this lane's row of the block's u
-    const int64_t ge = (N - cb > 16 * 64) ? cb + 16 * 64 : N;
+    const int64_t ge = (r_hi - cb > 16 * 64) ? cb + 16 * 64 : r_hi;
     for (; cb + 64 <= ge; cb += 64, ub += SU) {
+        if constexpr (CHUNK == 3) {                 // block j of this wave: unit state j (s_r of term j, then s_i)
+            const int j = (int)((cb - r_lo) >> 6);
+            sr = (j < Jc && lane == j) ? 1.0 : 0.0;
+            si = (j >= Jc && lane == j - Jc) ? 1.0 : 0.0;
+        } else {
         const double tv = t_nx, tp = tp_nx;         // t of the rows cb + lane
         {
             const int64_t i = row_of(cb + 64);
@@ -1832,6 +1918,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         }
         const double dt = tv - tp;
         viol |= (dt > gthr) || !(fabs(dt - delta) < jthr);
+        }
         wave_lds_fence();
         if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
         wave_lds_fence();
@@ -1870,9 +1957,16 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             two_rows(zz[j2]);
         }
         join(l32r, l32i);
+        if constexpr (CHUNK == 3) {
+            if (lane < 32) {                        // column j of M
+                const int j = (int)((cb - r_lo) >> 6), col = j < Jc ? j : 32 + j - Jc;
+                wsp[64 * lane + col] = sr;
+                wsp[64 * (32 + lane) + col] = si;
+            }
+        }
     }
     if (cb < ge) {                                  // a partial last block (ge = N): lim rows
-        const int lim = (int)(N - cb);
+        const int lim = (int)(r_hi - cb);
         const double dt = t_nx - tp_nx;
         viol |= (lane < lim) && ((dt > gthr) || !(fabs(dt - delta) < jthr));
         wave_lds_fence();
@@ -1900,9 +1994,25 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             jr = xr;
         }
         join(jr, ji);
-        cb = N;
+        cb = r_hi;
     }
     }
+    }
+    if constexpr (CHUNK != 0) {
+        if constexpr (CHUNK == 3) return;           // (its rows were no rows of the series)
+        if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
+        double *__restrict__ slot = wsp + CH_P + ch * CH_SLOT;
+        if (ch == nch - 1) {
+            if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
+        } else if (CHUNK == 1 && lane < 32) {
+            slot[lane] = sr;
+            slot[32 + lane] = si;
+        }
+        if (CHUNK == 2 || ch == 0) {
+            const double q = wave_sum(zsq);         // fixed order; k_steady_chunk_sum adds the chunks' in chunk order
+            if (lane == 0) slot[64] = q;
+        }
+        return;
     }
     if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
     if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
@@ -1954,6 +2064,86 @@ k_steady_finish(const int64_t N, const int Jc, const double gap,
                 const int64_t sw_lo, const int64_t sw_hi) {
     steady_tail_rows<ROWS, false>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr, info,
                                   steady_, acc_, sw_lo, sw_hi);
+}
+
+// The chunked finishing launch: the tail of a problem of the window in chunks of chunk_rows rows, one wave per chunk,
+// grid B x (the largest chunk count of a series of N rows; B x 1 for PASS = 3, the waves of M).  PASS = 3 and 1, then
+// k_steady_chunk_power, then PASS = 2, then k_steady_chunk_sum, on one stream (steady_tail_rows has the scheme).
+template <int ROWS, int PASS>
+__global__ void __launch_bounds__(64, 2)
+k_steady_chunk(const int64_t N, const int Jc, const double gap,
+               const double *__restrict__ ac_, const double *__restrict__ bc_,
+               const double *__restrict__ cc_, const double *__restrict__ dc_, const double *__restrict__ cmax_,
+               const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
+               const int32_t *__restrict__ info, double *__restrict__ steady_,
+               const int64_t sw_lo, const int64_t sw_hi, const int64_t chunk_rows, double *__restrict__ ws_,
+               const int64_t ws_ld) {
+    steady_tail_rows<ROWS, false, PASS>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr,
+                                        info, steady_, nullptr, sw_lo, sw_hi, chunk_rows, ws_, ws_ld);
+}
+
+// the window's problems with at least `least` chunks: first tail row, 0 for every other problem
+__device__ __forceinline__ int64_t steady_chunk_problem(const int pr, const int64_t N, const int32_t *__restrict__ info,
+                                                        const double *__restrict__ steady_, const int64_t sw_lo,
+                                                        const int64_t sw_hi, const int64_t chunk_rows, const int least) {
+    if (info[pr] != 0) return 0;
+    const double swd = steady_[(size_t)pr * ST_SIZE + ST_SW];
+    if (!(swd > 0.0)) return 0;
+    const int64_t sw = (int64_t)swd;
+    if (sw < sw_lo || sw >= sw_hi || sw >= N) return 0;
+    return (N - sw + chunk_rows - 1) / chunk_rows >= least ? sw : 0;
+}
+
+// P = M^(2^squarings) in place, one workgroup of 256 per problem: thread (i, q) holds P[i][16 q .. 16 q + 15], the
+// matrix lies in LDS between two squarings.  About 11 squarings of 64 x 64 per problem: the rate does not matter.
+__global__ void __launch_bounds__(256)
+k_steady_chunk_power(const int64_t N, const int32_t *__restrict__ info, const double *__restrict__ steady_,
+                     const int64_t sw_lo, const int64_t sw_hi, const int64_t chunk_rows, const int squarings,
+                     double *__restrict__ ws_, const int64_t ws_ld) {
+    const int pr = blockIdx.x;
+    if (steady_chunk_problem(pr, N, info, steady_, sw_lo, sw_hi, chunk_rows, 3) == 0) return;   // (block-uniform)
+    __shared__ double s_m[64][64 + 1];
+    double *__restrict__ P = ws_ + (size_t)pr * ws_ld;
+    const int i = threadIdx.x >> 2, c0 = 16 * (threadIdx.x & 3);
+    double a[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) a[j] = P[64 * i + c0 + j];
+    for (int q = 0; q < squarings; ++q) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 16; ++j) s_m[i][c0 + j] = a[j];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 16; ++j) a[j] = 0.0;
+#pragma unroll 4
+        for (int k = 0; k < 64; ++k) {
+            const double m = s_m[i][k];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) a[j] = fma(m, s_m[k][c0 + j], a[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) P[64 * i + c0 + j] = a[j];
+}
+
+// the chunks' sums into acc, one thread per problem, in chunk order: the additions of the one-wave launch
+__global__ void __launch_bounds__(64)
+k_steady_chunk_sum(const int B, const int64_t N, const int32_t *__restrict__ info, const double *__restrict__ steady_,
+                   const int64_t sw_lo, const int64_t sw_hi, const int64_t chunk_rows,
+                   const double *__restrict__ ws_, const int64_t ws_ld, double *__restrict__ acc_) {
+    const int pr = blockIdx.x * 64 + threadIdx.x;
+    if (pr >= B) return;
+    const int64_t sw = steady_chunk_problem(pr, N, info, steady_, sw_lo, sw_hi, chunk_rows, 1);
+    if (sw == 0) return;
+    const int nch = (int)((N - sw + chunk_rows - 1) / chunk_rows);
+    const double *__restrict__ slot = ws_ + (size_t)pr * ws_ld + CH_P;
+    double q = 0.0;
+    for (int c = 0; c < nch; ++c) q += slot[c * CH_SLOT + 64];
+    const double dinf = steady_[(size_t)pr * ST_SIZE + ST_D];
+    double *__restrict__ a = acc_ + (size_t)pr * RED_NACC;
+    a[0] += (double)(N - sw) * log(dinf);
+    a[1] += q / dinf;
+    a[2] = fmin(a[2], dinf);
 }
 
 // ------------------------------------------------------------------------------------
@@ -6155,6 +6345,57 @@ int gf_steady_finish_window(int B, int64_t N, int Jr, int Jc, int block, int var
                             int64_t sw_lo, int64_t sw_hi, void *stream) {
     return steady_finish_launch("gf_steady_finish_window", B, N, Jr, Jc, block, variant, ac, bc, cc, dc, cmax, t, t_bs,
                                 y, y_bs, info, steady, acc, sw_lo, sw_hi, stream);
+}
+
+int64_t gf_steady_chunk_size(int64_t N, int chunk_blocks) {
+    if (N < 1 || chunk_blocks < 1) return 0;
+    const int64_t chunk_rows = 64 * (int64_t)chunk_blocks;
+    return CH_P + (N + chunk_rows - 1) / chunk_rows * CH_SLOT;
+}
+
+#define GF_SC_CASE(R) case R: \
+    hipLaunchKernelGGL((k_steady_chunk<R, 3>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld); \
+    hipLaunchKernelGGL((k_steady_chunk<R, 1>), dim3(B, nmax), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld); \
+    hipLaunchKernelGGL(k_steady_chunk_power, dim3(B), dim3(256), 0, st, N, info, steady, sw_lo, sw_hi, chunk_rows, squarings, chunk_ws, ws_ld); \
+    hipLaunchKernelGGL((k_steady_chunk<R, 2>), dim3(B, nmax), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld); \
+    break;
+
+int gf_steady_finish_chunked(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                             const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                             const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                             const int32_t *info, double *steady, double *acc,
+                             int64_t sw_lo, int64_t sw_hi, int chunk_blocks, double *chunk_ws, void *stream) {
+    const char *who = "gf_steady_finish_chunked";
+    if (B < 1 || N < 1) return set_err("%s: empty problem (B=%lld, N=%lld)", who, B, N);
+    if (Jr != 0 || Jc < 1 || Jc > 31)
+        return set_err("%s: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%lld, Jc=%lld)", who, Jr, Jc);
+    if (block < 1 || block > 64 || (block & (block - 1)))
+        return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
+    if (!ac || !bc || !cc || !dc || !cmax || !t || !y || !info || !steady || !acc || !chunk_ws)
+        return set_err("%s: null pointer", who);
+    if (sw_lo < 0 || sw_hi < sw_lo)
+        return set_err("%s: the window of switch rows needs 0 <= sw_lo <= sw_hi (sw_lo=%lld, sw_hi=%lld)", who, sw_lo, sw_hi);
+    if (chunk_blocks < 16 || (chunk_blocks & (chunk_blocks - 1)))
+        return set_err("%s: chunk_blocks=%lld must be a power of two >= 16 (chunks start on the groups' grid)", who, chunk_blocks);
+    if (sw_lo == sw_hi) return 0;       // an empty window: no launch
+    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
+    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
+    const int64_t chunk_rows = 64 * (int64_t)chunk_blocks, ws_ld = gf_steady_chunk_size(N, chunk_blocks);
+    const int64_t nmax64 = (N + chunk_rows - 1) / chunk_rows;
+    if (nmax64 > 65535) return set_err("%s: %lld chunks per problem are more than a launch takes", who, nmax64);
+    const int nmax = (int)nmax64;
+    int squarings = 0;
+    while ((1 << squarings) < chunk_blocks) ++squarings;
+    hipStream_t st = (hipStream_t)stream;
+    switch ((2 * Jc + 3) / 4 * 4) {
+        GF_SC_CASE(4) GF_SC_CASE(8) GF_SC_CASE(12) GF_SC_CASE(16) GF_SC_CASE(20) GF_SC_CASE(24)
+        GF_SC_CASE(28) GF_SC_CASE(32) GF_SC_CASE(36) GF_SC_CASE(40) GF_SC_CASE(44) GF_SC_CASE(48)
+        GF_SC_CASE(52) GF_SC_CASE(56) GF_SC_CASE(60) GF_SC_CASE(64)
+        default: return set_err("%s: internal dispatch error", who);
+    }
+    hipLaunchKernelGGL(k_steady_chunk_sum, dim3((B + 63) / 64), dim3(64), 0, st, B, N, info, steady, sw_lo, sw_hi,
+                       chunk_rows, chunk_ws, ws_ld, acc);
+    return check_launch(who);
 }
 
 int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,

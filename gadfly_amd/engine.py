@@ -878,8 +878,17 @@ class StreamingBatch:
         # before any problem can switch run the plain one): learnt from the switch rows of earlier evaluations
         self._steady_from = 0               # first row whose tile runs the steady instance
         self._steady_skip = 0               # evaluations left on the plain sweep after one in which nothing armed
-        self._steady_feedback = None        # (pinned host scalar, event): earliest switch row of the last steady one
-        self.finish_events = []             # time_factor: (start, end) of each gf_steady_finish launch (not in factor_events)
+        # (pinned host scalars, event) of the last steady one: earliest switch row, 7/8 quantile, latest switch row
+        self._steady_feedback = None
+        self.finish_events = []             # time_factor: (start, end) of each finishing launch (not in factor_events)
+        # the overlapped finishing schedule: the early switchers' tails on a side stream beside the
+        # stragglers' tiles (gf_steady_finish_window), the stragglers' own in chunks behind the last tile
+        # (gf_steady_finish_chunked).  False: one gf_steady_finish behind the last tile, for comparisons
+        self.steady_overlap = True
+        self._steady_split = 0              # rows in front of the split (a multiple of the tile; 0: one launch)
+        self._steady_chunk_blocks = None    # None: the smallest power of two >= ceil(N / 64 / 8) (tests force 16)
+        self._steady_chunk_ws = None        # [B][gf_steady_chunk_size()] workspace of the chunked launch
+        self._finish_side = None            # the early launch's stream
         T = int(min(max(int(tile_rows), 1), self.N))
         if T < self.N:
             T = max(64, T // 64 * 64)         # tiles start on a reset row (any block <= 64)
@@ -1195,7 +1204,30 @@ class StreamingBatch:
             if self._steady is None:
                 self._steady = torch.empty((B, int(lib.gf_steady_size())), dtype=torch.float64, device=self.device)
             self._steady.zero_()
-        for k in range((N + T - 1) // T):
+        ntiles = (N + T - 1) // T
+        # the overlapped finishing schedule: the problems that switch up to the end of tile k_e on a side stream behind
+        # that tile's reduction, the others in chunks behind the last tile; k_e from the last evaluation's switch rows
+        overlap = self.steady_used and self.steady_overlap and B >= self.STEADY_OVERLAP_MIN_B
+        split = self._steady_split if overlap else 0
+        k_e = split // T - 1 if 0 < split < N else -1
+        if not 0 <= k_e < ntiles - 1:
+            split, k_e = 0, -1
+
+        def finish(name, stream, *tail):
+            """One finishing launch on `stream`, with an event pair of its own."""
+            if self.time_factor:
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+            st = getattr(lib, name)(B, N, self.Jr, self.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]),
+                                    p(comp[3]), p(cmax), p(self.t), self._bs(self.t), p(self.y), self._bs(self.y),
+                                    p(self.info), p(self._steady), p(self.acc), *tail, stream.cuda_stream)
+            _lib.check(st, name)
+            if self.time_factor:
+                e1.record(stream)
+                self.finish_events.append((e0, e1))
+
+        for k in range(ntiles):
             n0 = k * T
             rows = min(T, N - n0)
             if self.time_factor:
@@ -1226,25 +1258,36 @@ class StreamingBatch:
                 st = lib.gf_reduce_tile(B, rows, p(self.d), p(self.z), p(self.work), p(self.acc),
                                         1 if k == 0 else 0, main.cuda_stream)
                 _lib.check(st, "gf_reduce_tile")
+            if k == k_e:
+                # every problem that has switched by now: its last write of acc on this stream is behind us, and the
+                # later tiles touch neither its header nor its acc
+                if self._finish_side is None:
+                    self._finish_side = torch.cuda.Stream(device=self.device)
+                self._finish_side.wait_event(main.record_event())
+                finish("gf_steady_finish_window", self._finish_side, 1, split + 1)
         if self.steady_used:
-            # every switched problem's rows from its switch row to the end of the series, in one launch: no row is
-            # stored, acc takes their sums (its own event pair: factor_events stays one entry per tile)
-            if self.time_factor:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(main)
-            st = lib.gf_steady_finish(B, N, self.Jr, self.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]),
-                                      p(comp[3]), p(cmax), p(self.t), self._bs(self.t), p(self.y), self._bs(self.y),
-                                      p(self.info), p(self._steady), p(self.acc), main.cuda_stream)
-            _lib.check(st, "gf_steady_finish")
-            if self.time_factor:
-                e1.record(main)
-                self.finish_events.append((e0, e1))
-            # earliest switch row (0: nothing armed) for the next plan: no sync here
+            # every switched problem's rows from its switch row to the end of the series: no row is stored, acc takes
+            # their sums (event pairs of their own: factor_events stays one entry per tile)
+            if split:
+                cb = self._steady_chunk_blocks
+                if cb is None:
+                    cb = 16
+                    while cb * 8 * 64 < N:
+                        cb *= 2
+                if self._steady_chunk_ws is None or self._steady_chunk_ws[1] != cb:
+                    ws = torch.empty((B, int(lib.gf_steady_chunk_size(N, cb))), dtype=torch.float64, device=self.device)
+                    self._steady_chunk_ws = (ws, cb)
+                finish("gf_steady_finish_chunked", main, split + 1, (1 << 63) - 1, cb, p(self._steady_chunk_ws[0]))
+                main.wait_stream(self._finish_side)
+            else:
+                finish("gf_steady_finish", main)
+            # for the next plan, without a sync here: the earliest switch row (0: nothing armed), the row in front of
+            # which all but B/8 problems had switched (0: fewer than that switched at all), and the latest switch row
             sw = self._steady[:, 0]
-            first = torch.where(sw > 0.0, sw, torch.full_like(sw, float("inf"))).min()
-            host = torch.zeros((1,), dtype=torch.float64, pin_memory=True)
-            host.copy_(torch.where(torch.isfinite(first), first, torch.zeros_like(first)).reshape(1), non_blocking=True)
+            swi = torch.where(sw > 0.0, sw, torch.full_like(sw, float("inf")))
+            fb = torch.stack([swi.min(), torch.kthvalue(swi, B - B // 8).values, sw.max()])
+            host = torch.zeros((3,), dtype=torch.float64, pin_memory=True)
+            host.copy_(torch.where(torch.isfinite(fb), fb, torch.zeros_like(fb)), non_blocking=True)
             done = torch.cuda.Event()
             done.record(main)
             self._steady_feedback = (host, done)
@@ -1256,6 +1299,8 @@ class StreamingBatch:
 
     #: evaluations between two tries of the steady instance while nothing arms (a series too short, a kernel too slow)
     STEADY_PROBE = 16
+    #: smallest batch that takes the overlapped finishing schedule: below it the device is not full to begin with
+    STEADY_OVERLAP_MIN_B = 64
 
     def _steady_plan(self, arm_from):
         """Row from whose tile on this evaluation runs the steady instance, None for the plain sweep throughout.
@@ -1263,15 +1308,23 @@ class StreamingBatch:
         register budget), so it is started only where a switch can be near: one tile and the rule's look-back before
         the earliest switch row of the last steady evaluation whose result has arrived (read without waiting; a
         sampler's proposals move slowly).  A problem that would have switched earlier switches a little later: speed,
-        never values.  After an evaluation in which nothing armed, the next STEADY_PROBE - 1 run the plain sweep."""
+        never values.  After an evaluation in which nothing armed, the next STEADY_PROBE - 1 run the plain sweep.
+        The same feedback sets the split of the overlapped finishing schedule (_steady_split)."""
         fb = self._steady_feedback
         if fb is not None and fb[1].query():
-            first, self._steady_feedback = int(fb[0][0]), None
+            (first, most, latest), self._steady_feedback = (int(v) for v in fb[0]), None
             if first > 0:
                 self._steady_from = max(0, first - self.STEADY_MIN_ROWS - self.tile_rows)
                 self._steady_skip = 0
             else:
                 self._steady_from, self._steady_skip = 0, self.STEADY_PROBE - 1
+            # the finishing schedule's split: the end of the tile in which all but B/8 problems had switched (a problem
+            # whose first tail row is sw leaves the sweep in the tile of row sw - 1); 0 where no problem is expected
+            # behind it
+            T = self.tile_rows
+            self._steady_split = ((most - 1) // T + 1) * T if most > 0 else 0
+            if latest <= self._steady_split:
+                self._steady_split = 0
         if self._steady_skip > 0:
             self._steady_skip -= 1
             return None

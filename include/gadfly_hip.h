@@ -274,6 +274,25 @@ int gf_steady_finish_window(int B, int64_t N, int Jr, int Jc, int block, int var
                             const double *t, int64_t t_bs, const double *y, int64_t y_bs,
                             const int32_t *info, double *steady, double *acc,
                             int64_t sw_lo, int64_t sw_hi, void *stream);
+/*
+ * gf_steady_finish_chunked : gf_steady_finish_window with more than one wave per problem -- for a window that holds
+ *     few problems with long tails.  Behind the switch a 64-row block is linear and time-invariant in the state
+ *     (z = u + Q s, s' = M s + K u), so the tail runs in chunks of chunk_blocks blocks side by side: pass A (chunk 0
+ *     from the true state, the others from zero, and M from the block's own code on unit states), P = M^chunk_blocks
+ *     by squarings, pass B (every later chunk again from its true state s_in[c + 1] = s_out0[c] + P s_in[c], summing
+ *     z^2), and the chunks' sums added in chunk order: five launches on `stream`, about two chunk lengths instead of
+ *     the whole tail.  The window, the problems left alone, what acc and steady take and the spacing tests are
+ *     gf_steady_finish_window's; acc[b][0] and acc[b][2] take its bits, acc[b][1] and the state agree with it to
+ *     rounding (the same bits for the same N, switch row and chunk_blocks, in whatever order the waves run).
+ *     chunk_blocks: a power of two >= 16 (every chunk starts on the problem's grid of 16-block groups).
+ *     chunk_ws: B x gf_steady_chunk_size(N, chunk_blocks) doubles, the launch's alone until it has ended.
+ */
+int64_t gf_steady_chunk_size(int64_t N, int chunk_blocks);
+int gf_steady_finish_chunked(int B, int64_t N, int Jr, int Jc, int block, int variant,
+                             const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
+                             const double *t, int64_t t_bs, const double *y, int64_t y_bs,
+                             const int32_t *info, double *steady, double *acc,
+                             int64_t sw_lo, int64_t sw_hi, int chunk_blocks, double *chunk_ws, void *stream);
 
 /*
  * Fused sampling sweep: B draws y = L D^1/2 eps of B different kernels, K = L D L^T, in the sweep that factors
