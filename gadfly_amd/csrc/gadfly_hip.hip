@@ -1275,6 +1275,80 @@ constexpr int ST_LAG = 16, ST_COUNT = 4;
 constexpr double ST_THR = 1e-10;
 constexpr int ST_SIZE = ST_RING + ST_LAG * 64;
 
+// The log-likelihood reductions' shape (k_reduce1 / k_reduce2, below): G groups of RED_BLOCK rows per problem.
+constexpr int RED_NACC = 3;         // the reductions' accumulators per problem: sum log d, sum z^2/d, min d
+constexpr int RED_BLOCK = 256;
+constexpr int RED_MAXG = 512;
+
+__host__ __device__ inline int red_groups(int64_t N) {
+    int64_t g = (N + 4095) / 4096;
+    if (g < 1) g = 1;
+    if (g > RED_MAXG) g = RED_MAXG;
+    return (int)g;
+}
+
+// Rows of a tile (first global row n_first) that the steady mode's sweep instance stored for problem b: those in
+// front of the problem's switch row, all N of a problem that has not switched (the bounded reductions).
+__device__ inline int64_t steady_rows_stored(const double *steady, int b, int64_t N, int64_t n_first) {
+    const double swd = steady[(size_t)b * ST_SIZE + ST_SW];
+    if (!(swd > 0.0)) return N;
+    const int64_t r = (int64_t)swd - n_first;
+    return r < 0 ? 0 : (r < N ? r : N);
+}
+
+// One row's terms of the sums: the same expressions wherever a tile is summed (k_reduce1 and steady_tile_sums must
+// give the same bits, so neither may be contracted differently from the other).
+__device__ __forceinline__ void red_row(const double dn, double &s1, double &mn) {
+    s1 += log(dn);
+    mn = fmin(mn, dn);
+}
+__device__ __forceinline__ void red_row_z(const double dn, const double zn, double &s2) { s2 += zn * zn / dn; }
+
+// gf_reduce_tile_steady's additions for ONE problem by ONE wave (the steady sweep's own wave behind its rows:
+// gf_steady_sweep_reduced): rows [0, lim) of the tile's d and z.  The same operations in the same order as
+// k_reduce1<true> + k_reduce2<true>, so the same bits: per group g of RED_BLOCK rows the block's four waves one after
+// the other (lane l of wave w takes rows g RED_BLOCK + 64 w + l + k G RED_BLOCK), thread 0's sum over the four from
+// 0.0 / inf, then k_reduce2's lane g & 63 over its groups in order, the tree over the lanes and lane 0's addition to
+// acc.  (Exact zeros from the lanes and waves without a row change no bit, there as here.)
+__device__ __forceinline__ void steady_tile_sums(const double *dp, const double *zp, const int64_t N, const int64_t lim,
+                                                 double *acc, const int init, const int lane) {
+    if (lim == 0 && !init) return;
+    const int G = red_groups(N);
+    const int64_t gl = (lim + RED_BLOCK - 1) / RED_BLOCK;
+    const int Gn = gl < G ? (int)gl : G;
+    double a1 = 0.0, a2 = 0.0, am = INFINITY;
+#pragma unroll 1
+    for (int g = 0; g < Gn; ++g) {
+        double t1 = 0.0, t2 = 0.0, t3 = INFINITY;
+#pragma unroll 1
+        for (int w = 0; w < RED_BLOCK / 64; ++w) {
+            double s1 = 0.0, s2 = 0.0, mn = INFINITY;
+#pragma unroll 1
+            for (int64_t n = (int64_t)g * RED_BLOCK + 64 * w + lane; n < lim; n += (int64_t)G * RED_BLOCK) {
+                const double dn = dp[n];
+                red_row(dn, s1, mn);
+                red_row_z(dn, zp[n], s2);
+            }
+            wave_sum2(s1, s2);
+            mn = -wave_max(-mn);
+            t1 += s1;
+            t2 += s2;
+            t3 = fmin(t3, mn);
+        }
+        if (lane == (g & 63)) {
+            a1 += t1;
+            a2 += t2;
+            am = fmin(am, t3);
+        }
+    }
+    wave_sum2(a1, a2);
+    am = -wave_max(-am);
+    if (lane == 0) {
+        if (!init) { a1 += acc[0]; a2 += acc[1]; am = fmin(am, acc[2]); }
+        acc[0] = a1; acc[1] = a2; acc[2] = am;
+    }
+}
+
 template <int ROWS, bool ROWSTORE, bool SAMPLE = false, bool STEADY = false>
 __global__ void __launch_bounds__(64, 2)
 k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const int nch,
@@ -1289,17 +1363,25 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
           double *__restrict__ d_, double *__restrict__ z_, double *__restrict__ r_out,
           double *__restrict__ Ut_out, double *__restrict__ Wt_out, double *__restrict__ de_out,
           double *__restrict__ S_state, double *__restrict__ F_state,
-          int32_t *__restrict__ info, double *__restrict__ steady_, const int64_t arm_from) {
+          int32_t *__restrict__ info, double *__restrict__ steady_, const int64_t arm_from,
+          double *acc_, const int acc_init) {
     static_assert(!STEADY || (!ROWSTORE && !SAMPLE), "steady mode: the streamed log-likelihood only");
     const int lane = threadIdx.x;
     const int g = lane >> 5, c = lane & 31;         // row group, column block (columns 2c, 2c + 1)
     const int sel = blockIdx.x;                     // chunks ch0 .. ch0 + nsel - 1 of every problem
     const int pr = sel / nsel, ch = ch0 + (sel - pr * nsel);
     const int b = pr * nch + ch;                    // state slot = problem * nch + chunk
-    if (info[b] != 0) return;
+    // steady mode with acc_ (gf_steady_sweep_reduced; wave-uniform): the wave adds this tile's stored rows to acc[pr]
+    // itself, at whichever exit it leaves by, as gf_reduce_tile_steady would behind it -- tile_lim rows, what
+    // steady_rows_stored gives once the kernel has ended (label tile_sums, at the kernel's end; acc_ null: every
+    // exit is the plain return it was, and the other instances hold nothing of this)
+    int64_t tile_lim = 0;
+#define STEADY_EXIT(lim) do { if constexpr (STEADY) { if (acc_) { tile_lim = (lim); goto tile_sums; } } return; } while (0)
+  {
+    if (info[b] != 0) STEADY_EXIT(steady_rows_stored(steady_, pr, N, n_first));    // (stale rows, as the reduction takes them)
     // steady mode: this problem's buffer; a problem that has switched is k_steady_tail's from its switch row on
     double *__restrict__ hdr = STEADY ? steady_ + (size_t)pr * ST_SIZE : nullptr;
-    if constexpr (STEADY) { if (hdr[ST_SW] > 0.0) return; }
+    if constexpr (STEADY) { if (hdr[ST_SW] > 0.0) STEADY_EXIT(steady_rows_stored(steady_, pr, N, n_first)); }
     const int64_t c0 = (int64_t)ch * chunk_len;
     const int64_t rows = (N - c0 < chunk_len) ? (N - c0) : chunk_len;
     const int64_t g0 = n_first + c0;
@@ -1471,7 +1553,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
                         hdr[ST_D] = dn;
                         hdr[ST_DT] = (tg[n] - tg[n - ST_DLAG]) * (1.0 / ST_DLAG);
                     }
-                    return;                         // (row n + 1 is the tail's first)
+                    STEADY_EXIT(n + 1);             // (row n + 1 is the tail's first; rows 0 .. n were stored)
                 }
             }
         }
@@ -1486,7 +1568,7 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
             if (f31)
                 for (int m = 0; m < 32; ++m) Sg[63 * 64 + 2 * g + 4 * (m >> 1) + (m & 1)] = 0.0;
         }
-        return;
+        STEADY_EXIT(N);                             // (not switched: the reduction takes the tile's N rows, stale ones too)
     }
     wave_lds_fence();
 #pragma unroll
@@ -1502,6 +1584,18 @@ k_factor7(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
         }
         if (f31)                                    // S's own column 63 (these lanes' second column is F~)
             for (int m = 0; m < 32; ++m) Sg[63 * 64 + 2 * g + 4 * (m >> 1) + (m & 1)] = 0.0;
+    }
+    STEADY_EXIT(N);                                 // the end of the tile, not switched: all its rows
+  }
+#undef STEADY_EXIT
+tile_sums:
+    if constexpr (STEADY) {
+        // lane 0 stored this tile's d and z (and the other lanes read them back now): its stores are ordered before
+        // the loads at workgroup scope -- the block is this one wave -- and the sums run at the tail waves' priority
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        steady_tile_sums(d_ + (size_t)pr * N, z_ + (size_t)pr * N, N, tile_lim, acc_ + (size_t)pr * RED_NACC, acc_init, lane);
     }
 }
 
@@ -1545,7 +1639,6 @@ __device__ __forceinline__ void stage_end() {
     wave_lds_fence();
     __builtin_amdgcn_sched_barrier(0);
 }
-constexpr int RED_NACC = 3;         // the reductions' accumulators per problem: sum log d, sum z^2/d, min d
 
 #define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -2053,6 +2146,9 @@ k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double
 //   - k_reduce1<true> / k_reduce2<true> of a later tile find steady_rows_stored == 0 for such a problem and return
 //     without touching `work` or acc[b] (init is set on the series' first tile only, which cannot lie behind a
 //     switch): the last write of acc[b] on the sweep's stream is the reduction of the tile that holds the switch;
+//   - where the sweep adds its own tile (gf_steady_sweep_reduced: no reduction behind it) that last write is the sweep
+//     of the tile that holds the switch, and the event stands behind that sweep: on a later tile the wave of a switched
+//     problem finds steady_rows_stored == 0 at its exit and leaves acc[b] alone, as k_reduce2<true> does;
 //   - the problems that have not switched are not this launch's: it leaves at the window test above.
 template <int ROWS>
 __global__ void __launch_bounds__(64, 2)
@@ -4635,26 +4731,9 @@ k_chunk_decay(const int64_t N, const int64_t chunk_len, const int nch, const int
 // ------------------------------------------------------------------------------------
 // log-likelihood reductions: fixed-shape two-stage tree (deterministic)
 //   stage 1: G blocks per problem -> partial (sum log d, sum z^2/d);  stage 2: one wave
+// (RED_BLOCK, red_groups, steady_rows_stored and the rows' terms stand in front of k_factor7, whose steady instance
+// can add its own tile: steady_tile_sums)
 // ------------------------------------------------------------------------------------
-constexpr int RED_BLOCK = 256;
-constexpr int RED_MAXG = 512;
-
-__host__ __device__ inline int red_groups(int64_t N) {
-    int64_t g = (N + 4095) / 4096;
-    if (g < 1) g = 1;
-    if (g > RED_MAXG) g = RED_MAXG;
-    return (int)g;
-}
-
-// Rows of a tile (first global row n_first) that the steady mode's sweep instance stored for problem b: those in
-// front of the problem's switch row, all N of a problem that has not switched (the bounded reductions).
-__device__ inline int64_t steady_rows_stored(const double *steady, int b, int64_t N, int64_t n_first) {
-    const double swd = steady[(size_t)b * ST_SIZE + ST_SW];
-    if (!(swd > 0.0)) return N;
-    const int64_t r = (int64_t)swd - n_first;
-    return r < 0 ? 0 : (r < N ? r : N);
-}
-
 // BOUNDED: the rows [0, steady_rows_stored) only, in the order the plain instance takes them; a group with no such row
 // ends at once and leaves its slot of `work` alone (k_reduce2<true> does not read it)
 template <bool BOUNDED>
@@ -4668,9 +4747,8 @@ __global__ void __launch_bounds__(RED_BLOCK) k_reduce1(int64_t N, const double *
     double s1 = 0.0, s2 = 0.0, mn = INFINITY;
     for (int64_t n = (int64_t)g * RED_BLOCK + threadIdx.x; n < lim; n += (int64_t)G * RED_BLOCK) {
         const double dn = dp[n];
-        s1 += log(dn);
-        mn = fmin(mn, dn);
-        if (zp) { const double zn = zp[n]; s2 += zn * zn / dn; }
+        red_row(dn, s1, mn);
+        if (zp) red_row_z(dn, zp[n], s2);
     }
     wave_sum2(s1, s2);
     mn = -wave_max(-mn);
@@ -6155,9 +6233,9 @@ static bool sweep_tiled(int variant, int Jr, int Jc) {
 }
 
 #define GF_F3_ARGS dim3(B * chunk_count), dim3(64), 0, st, N, n_first, chunk_len, nch, chunk_first, chunk_count, Jr, Jc, (block | (gen_period << 8) | zero_start), gap, ar, cr, ac, bc, cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, r_out, Ut_out, Wt_out, de_out, S_state, F_state, info
-#define GF_F7_NOSTEADY (double *)nullptr, (int64_t)0
+#define GF_F7_NOSTEADY (double *)nullptr, (int64_t)0, (double *)nullptr, 0
 #define GF_S3_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_factor7<R, false, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R, true>), GF_F3_ARGS); break;
-#define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else if (steady) hipLaunchKernelGGL((k_factor7<R, false, false, true>), GF_F3_ARGS, steady, arm_from); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
+#define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else if (steady) hipLaunchKernelGGL((k_factor7<R, false, false, true>), GF_F3_ARGS, steady, arm_from, acc, acc_init); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
 #define GF_ST_CASE(R) case R: hipLaunchKernelGGL((k_steady_tail<R>), dim3(B), dim3(64), 0, st, N, n_first, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, d, z, info, steady); break;
 
 static int check_sweep_options(const char *who, int gen_period, int variant, int Jr, int Jc) {
@@ -6181,7 +6259,8 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
                         double *d, double *z, double *r_out, double *Ut_out, double *Wt_out,
                         double *de_out, double *S_state, double *F_state,
                         int32_t *info, void *stream, bool sample = false,
-                        double *steady = nullptr, int64_t arm_from = 0, bool tail = true) {
+                        double *steady = nullptr, int64_t arm_from = 0, bool tail = true,
+                        double *acc = nullptr, int acc_init = 0) {
     const int W = Jr + 2 * Jc;
     if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
     // the sampling sweeps (y = eps, z = the draw by global row with y's batch stride): streamed tiles only
@@ -6213,6 +6292,8 @@ static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int6
     hipStream_t st = (hipStream_t)stream;
     if (steady && (W > 63 || !tiled || r_out || Ut_out || Wt_out || de_out || sample || zero_start || nch > 1 || arm_from < 0))
         return set_err("%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%lld)", who, Jc);
+    if (acc && (!steady || tail))       // the sweep's own sums: the steady instance without its tail kernel only
+        return set_err("%s: acc goes with the steady sweep alone", who);
     if (W > 63) {                       // wide kernels: one workgroup per (problem, chunk), k_factorw
         FactorWArgs A;
         A.N = N; A.n_first = n_first; A.chunk_len = chunk_len; A.nch = nch; A.ch0 = chunk_first; A.nsel = chunk_count; A.Jc = Jc;
@@ -6299,6 +6380,22 @@ int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block
     return fused_launch("gf_steady_sweep", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
                         diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
                         nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false);
+}
+
+int gf_steady_sweep_reduced(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                            int gen_period, int variant,
+                            const double *ar, const double *cr, const double *ac,
+                            const double *bc, const double *cc, const double *dc,
+                            const double *diag_add, const double *cmax,
+                            const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                            const double *y, int64_t y_bs,
+                            double *d, double *z, double *S_state, double *F_state,
+                            int32_t *info, double *steady, int64_t arm_from, double *acc, int init, void *stream) {
+    if (!steady || !acc) return set_err("gf_steady_sweep_reduced: null pointer%s", "");
+    return fused_launch("gf_steady_sweep_reduced", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
+                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false,
+                        acc, init ? 1 : 0);
 }
 
 #define GF_SF_CASE(R) case R: hipLaunchKernelGGL((k_steady_finish<R>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc, sw_lo, sw_hi); break;

@@ -764,6 +764,58 @@ class WideFactor:
         return self._unscaled().predict_at(alpha, ts, Us, Vs, other=other)
 
 
+#: the largest switch row a finishing window can name (its open upper end)
+STEADY_SW_MAX = (1 << 63) - 1
+
+
+def steady_boundaries(N, T, most, mid, latest):
+    """(split, mid_end) of the overlapped finishing schedule from the last evaluation's switch rows:
+    `most` is the row in front of which all but B/8 problems had switched, `mid` the one for all but B/64, `latest`
+    the latest switch row (0: unknown).  Both boundaries are rows in front of them, multiples of the tile T: a
+    problem whose first tail row is sw leaves the sweep in the tile of row sw - 1, so the boundary behind `most` is
+    the end of that tile.  split = 0: nobody is expected behind it, one launch.  mid_end = 0: no middle window --
+    without a split, where it falls on the split's own tile, or where nobody is expected behind it."""
+    N, T, most, mid, latest = (int(v) for v in (N, T, most, mid, latest))
+    ntiles = (N + T - 1) // T
+
+    def end_of_tile(row):
+        return ((row - 1) // T + 1) * T if row > 0 else 0
+
+    split = end_of_tile(most)
+    if latest <= split or not 0 <= split // T - 1 < ntiles - 1:
+        return 0, 0
+    mid_end = end_of_tile(mid)
+    if mid_end <= split or latest <= mid_end or not mid_end // T - 1 < ntiles - 1:
+        mid_end = 0
+    return split, mid_end
+
+
+def steady_windows(split, mid_end):
+    """The finishing launches' windows [sw_lo, sw_hi) of switch rows for these boundaries: disjoint, and together
+    [1, STEADY_SW_MAX), so that every switched problem is finished exactly once wherever its switch row falls."""
+    if not split:
+        return [(1, STEADY_SW_MAX)]
+    if not mid_end:
+        return [(1, split + 1), (split + 1, STEADY_SW_MAX)]
+    return [(1, split + 1), (split + 1, mid_end + 1), (mid_end + 1, STEADY_SW_MAX)]
+
+
+def steady_chunk_blocks(N, chunks):
+    """Blocks of 64 rows per chunk of a chunked finishing launch: the smallest power of two >= 16 that cuts a tail of
+    N rows into at most `chunks` chunks."""
+    cb = 16
+    while cb * max(int(chunks), 1) * 64 < N:
+        cb *= 2
+    return cb
+
+
+def steady_final_chunk_blocks(N, B, simds):
+    """The same for the launch behind the last tile where a middle window runs in front of it: it holds the last
+    B/64 problems of the feedback and nothing runs beside it, so one wave per SIMD: as many chunks per problem as
+    keep (B/64 problems) x (chunks) at or below the device's SIMD count."""
+    return steady_chunk_blocks(N, max(1, int(simds) // max(1, int(B) // 64)))
+
+
 class StreamingBatch:
     """
     B independent log-likelihood evaluations streamed through fixed-size tile buffers.
@@ -878,7 +930,7 @@ class StreamingBatch:
         # before any problem can switch run the plain one): learnt from the switch rows of earlier evaluations
         self._steady_from = 0               # first row whose tile runs the steady instance
         self._steady_skip = 0               # evaluations left on the plain sweep after one in which nothing armed
-        # (pinned host scalars, event) of the last steady one: earliest switch row, 7/8 quantile, latest switch row
+        # (pinned host scalars, event) of the last steady one: earliest switch row, 7/8 quantile, 63/64 quantile, latest
         self._steady_feedback = None
         self.finish_events = []             # time_factor: (start, end) of each finishing launch (not in factor_events)
         # the overlapped finishing schedule: the early switchers' tails on a side stream beside the
@@ -886,9 +938,17 @@ class StreamingBatch:
         # (gf_steady_finish_chunked).  False: one gf_steady_finish behind the last tile, for comparisons
         self.steady_overlap = True
         self._steady_split = 0              # rows in front of the split (a multiple of the tile; 0: one launch)
-        self._steady_chunk_blocks = None    # None: the smallest power of two >= ceil(N / 64 / 8) (tests force 16)
+        # rows in front of the middle window's end (a multiple of the tile; 0: no middle window): the stragglers that
+        # switch up to there are finished in chunks on the side stream beside the last ones' tiles
+        self._steady_mid = 0
+        self._steady_chunk_blocks = None    # None: steady_chunk_blocks / steady_final_chunk_blocks (tests force 16)
         self._steady_chunk_ws = None        # [B][gf_steady_chunk_size()] workspace of the chunked launch
-        self._finish_side = None            # the early launch's stream
+        self._steady_mid_ws = None          # the same of the middle window's launch (the two can overlap)
+        self._finish_side = None            # the early launches' stream
+        self._simds = None                  # SIMDs of the device (4 per compute unit), read once
+        # behind the split the sweep's own wave adds its tile to acc (gf_steady_sweep_reduced); False: the separate
+        # reduction on every tile, for comparisons (the same bits)
+        self.steady_sweep_reduces = True
         T = int(min(max(int(tile_rows), 1), self.N))
         if T < self.N:
             T = max(64, T // 64 * 64)         # tiles start on a reset row (any block <= 64)
@@ -1206,12 +1266,27 @@ class StreamingBatch:
             self._steady.zero_()
         ntiles = (N + T - 1) // T
         # the overlapped finishing schedule: the problems that switch up to the end of tile k_e on a side stream behind
-        # that tile's reduction, the others in chunks behind the last tile; k_e from the last evaluation's switch rows
+        # that tile's reduction, those that switch up to the end of tile k_m in chunks on the same stream behind that
+        # tile's sweep, the others in chunks behind the last tile; k_e and k_m from the last evaluation's switch rows
         overlap = self.steady_used and self.steady_overlap and B >= self.STEADY_OVERLAP_MIN_B
         split = self._steady_split if overlap else 0
         k_e = split // T - 1 if 0 < split < N else -1
         if not 0 <= k_e < ntiles - 1:
             split, k_e = 0, -1
+        mid_end = self._steady_mid if split and B >= self.STEADY_MIDDLE_MIN_B else 0
+        k_m = mid_end // T - 1 if mid_end % T == 0 else -1
+        if not k_e < k_m < ntiles - 1:
+            mid_end, k_m = 0, -1
+        windows = steady_windows(split, mid_end)
+
+        def chunked(stream, window, cb, which):
+            """One chunked finishing launch with the workspace of its own."""
+            cb = self._steady_chunk_blocks or cb
+            ws = getattr(self, which)
+            if ws is None or ws[1] != cb:
+                ws = (torch.empty((B, int(lib.gf_steady_chunk_size(N, cb))), dtype=torch.float64, device=self.device), cb)
+                setattr(self, which, ws)
+            finish("gf_steady_finish_chunked", stream, window[0], window[1], cb, p(ws[0]))
 
         def finish(name, stream, *tail):
             """One finishing launch on `stream`, with an event pair of its own."""
@@ -1241,7 +1316,14 @@ class StreamingBatch:
                     p(self.y), self._bs(self.y), p(self.d), p(self.z),
                     p(self.S_state), p(self.F_state), p(self.info))
             steady_tile = self.steady_used and n0 + rows > start    # (both instances hand over the same state)
-            if steady_tile:
+            # behind the split ~90 % of the problems have no rows left: the sweep's own wave adds its tile to acc there
+            # (gf_steady_sweep_reduced: the additions of gf_reduce_tile_steady, without its 3 B workgroups)
+            reduced = steady_tile and split and k > k_e and self.steady_sweep_reduces
+            if reduced:
+                st = lib.gf_steady_sweep_reduced(*args, p(self._steady), arm_from, p(self.acc), 1 if k == 0 else 0,
+                                                 main.cuda_stream)
+                _lib.check(st, "gf_steady_sweep_reduced")
+            elif steady_tile:
                 st = lib.gf_steady_sweep(*args, p(self._steady), arm_from, main.cuda_stream)
                 _lib.check(st, "gf_steady_sweep")
             else:
@@ -1250,7 +1332,9 @@ class StreamingBatch:
             if self.time_factor:
                 e1.record(main)
                 self.factor_events.append((e0, e1, rows))
-            if steady_tile:                 # the rows in front of each problem's switch row: the others were not stored
+            if reduced:                     # (the sweep has added its rows)
+                pass
+            elif steady_tile:               # the rows in front of each problem's switch row: the others were not stored
                 st = lib.gf_reduce_tile_steady(B, rows, n0, p(self.d), p(self.z), p(self._steady), p(self.work),
                                                p(self.acc), 1 if k == 0 else 0, main.cuda_stream)
                 _lib.check(st, "gf_reduce_tile_steady")
@@ -1258,35 +1342,40 @@ class StreamingBatch:
                 st = lib.gf_reduce_tile(B, rows, p(self.d), p(self.z), p(self.work), p(self.acc),
                                         1 if k == 0 else 0, main.cuda_stream)
                 _lib.check(st, "gf_reduce_tile")
-            if k == k_e:
-                # every problem that has switched by now: its last write of acc on this stream is behind us, and the
-                # later tiles touch neither its header nor its acc
+            if k == k_e or k == k_m:
+                # every problem that has switched by now: its last write of acc on this stream -- tile k's reduction,
+                # or tile k's sweep where that adds its own rows -- is behind us, and the later tiles touch neither its
+                # header nor its acc.  The two launches share the side stream: the middle one runs
+                # behind the early one
                 if self._finish_side is None:
                     self._finish_side = torch.cuda.Stream(device=self.device)
                 self._finish_side.wait_event(main.record_event())
-                finish("gf_steady_finish_window", self._finish_side, 1, split + 1)
+                if k == k_e:
+                    finish("gf_steady_finish_window", self._finish_side, *windows[0])
+                else:
+                    chunked(self._finish_side, windows[1], steady_chunk_blocks(N, 8), "_steady_mid_ws")
         if self.steady_used:
             # every switched problem's rows from its switch row to the end of the series: no row is stored, acc takes
             # their sums (event pairs of their own: factor_events stays one entry per tile)
             if split:
-                cb = self._steady_chunk_blocks
-                if cb is None:
-                    cb = 16
-                    while cb * 8 * 64 < N:
-                        cb *= 2
-                if self._steady_chunk_ws is None or self._steady_chunk_ws[1] != cb:
-                    ws = torch.empty((B, int(lib.gf_steady_chunk_size(N, cb))), dtype=torch.float64, device=self.device)
-                    self._steady_chunk_ws = (ws, cb)
-                finish("gf_steady_finish_chunked", main, split + 1, (1 << 63) - 1, cb, p(self._steady_chunk_ws[0]))
+                if mid_end:
+                    if self._simds is None:
+                        self._simds = 4 * torch.cuda.get_device_properties(self.device).multi_processor_count
+                    cb = steady_final_chunk_blocks(N, B, self._simds)
+                else:
+                    cb = steady_chunk_blocks(N, 8)
+                chunked(main, windows[-1], cb, "_steady_chunk_ws")
                 main.wait_stream(self._finish_side)
             else:
                 finish("gf_steady_finish", main)
-            # for the next plan, without a sync here: the earliest switch row (0: nothing armed), the row in front of
-            # which all but B/8 problems had switched (0: fewer than that switched at all), and the latest switch row
+            # for the next plan, without a sync here: the earliest switch row (0: nothing armed), the rows in front of
+            # which all but B/8 and all but B/64 problems had switched (0: fewer than that switched at all), and the
+            # latest switch row
             sw = self._steady[:, 0]
             swi = torch.where(sw > 0.0, sw, torch.full_like(sw, float("inf")))
-            fb = torch.stack([swi.min(), torch.kthvalue(swi, B - B // 8).values, sw.max()])
-            host = torch.zeros((3,), dtype=torch.float64, pin_memory=True)
+            fb = torch.stack([swi.min(), torch.kthvalue(swi, B - B // 8).values,
+                              torch.kthvalue(swi, B - B // 64).values, sw.max()])
+            host = torch.zeros((4,), dtype=torch.float64, pin_memory=True)
             host.copy_(torch.where(torch.isfinite(fb), fb, torch.zeros_like(fb)), non_blocking=True)
             done = torch.cuda.Event()
             done.record(main)
@@ -1301,6 +1390,9 @@ class StreamingBatch:
     STEADY_PROBE = 16
     #: smallest batch that takes the overlapped finishing schedule: below it the device is not full to begin with
     STEADY_OVERLAP_MIN_B = 64
+    #: smallest batch that takes a middle window: below it the last window would hold fewer than 8 problems, and the
+    #: B/8 stragglers' chunks all find a SIMD at once behind the last tile anyway
+    STEADY_MIDDLE_MIN_B = 512
 
     def _steady_plan(self, arm_from):
         """Row from whose tile on this evaluation runs the steady instance, None for the plain sweep throughout.
@@ -1312,19 +1404,15 @@ class StreamingBatch:
         The same feedback sets the split of the overlapped finishing schedule (_steady_split)."""
         fb = self._steady_feedback
         if fb is not None and fb[1].query():
-            (first, most, latest), self._steady_feedback = (int(v) for v in fb[0]), None
+            (first, most, mid, latest), self._steady_feedback = (int(v) for v in fb[0]), None
             if first > 0:
                 self._steady_from = max(0, first - self.STEADY_MIN_ROWS - self.tile_rows)
                 self._steady_skip = 0
             else:
                 self._steady_from, self._steady_skip = 0, self.STEADY_PROBE - 1
-            # the finishing schedule's split: the end of the tile in which all but B/8 problems had switched (a problem
-            # whose first tail row is sw leaves the sweep in the tile of row sw - 1); 0 where no problem is expected
-            # behind it
-            T = self.tile_rows
-            self._steady_split = ((most - 1) // T + 1) * T if most > 0 else 0
-            if latest <= self._steady_split:
-                self._steady_split = 0
+            # the finishing schedule's boundaries: the ends of the tiles in which all but B/8 and all but B/64 problems
+            # had switched; 0 where no problem is expected behind one (steady_boundaries)
+            self._steady_split, self._steady_mid = steady_boundaries(self.N, self.tile_rows, most, mid, latest)
         if self._steady_skip > 0:
             self._steady_skip -= 1
             return None

@@ -232,6 +232,12 @@ int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int blo
  *                           tile (N rows from global row n_first) in front of its switch row, all of them for a
  *                           problem that has not switched (then the same tree in the same order: the same bits as
  *                           gf_reduce_tile).  No other row of d, z is read.  work, acc, init as for gf_reduce_tile;
+ *   gf_steady_sweep_reduced : the two in one launch -- gf_steady_sweep, whose wave then adds the rows it stored to
+ *                           acc[b] itself: the additions of gf_reduce_tile_steady in its order, so acc, d, z, the state
+ *                           and `steady` hold the bits of the two calls (a problem that fails, or had failed, takes
+ *                           that reduction's stale rows too; its value is -inf either way).  No work buffer, and no
+ *                           workgroup beyond the sweep's own: for tiles in which most problems have no rows left.  A
+ *                           problem that had switched before the tile is left alone (init != 0: acc[b] = 0, 0, +inf);
  * and once per evaluation, behind the last tile's reduction on the same stream,
  *   gf_steady_finish      : the rows [switch row, N) of the WHOLE series (N rows; t, y from global row 0) of every
  *                           problem that has switched, in one launch of one wave per problem: the block filter of
@@ -265,6 +271,15 @@ int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block
                     int32_t *info, double *steady, int64_t arm_from, void *stream);
 int gf_reduce_tile_steady(int B, int64_t N, int64_t n_first, const double *d, const double *z,
                           const double *steady, double *work, double *acc, int init, void *stream);
+int gf_steady_sweep_reduced(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                            int gen_period, int variant,
+                            const double *ar, const double *cr, const double *ac,
+                            const double *bc, const double *cc, const double *dc,
+                            const double *diag_add, const double *cmax,
+                            const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                            const double *y, int64_t y_bs,
+                            double *d, double *z, double *S_state, double *F_state,
+                            int32_t *info, double *steady, int64_t arm_from, double *acc, int init, void *stream);
 int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
                      const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
                      const double *t, int64_t t_bs, const double *y, int64_t y_bs,
