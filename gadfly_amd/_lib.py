@@ -21,7 +21,8 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dens
            os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip"),
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
-           os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip")]
+           os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip"),
+           os.path.join(CSRC, "gadfly_lsfft.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -123,6 +124,11 @@ SIGNATURES = {
     "gf_ls_segments": (_int, [_i64]),
     "gf_ls_work": (_i64, [_i64, _i64, _int]),
     "gf_ls_power": (_int, [_int, _i64, _i64, _i64, _int, _int] + [_vp] * 8 + [_vp]),
+    "gf_lsfft_grid": (_i64, [_i64]),
+    "gf_lsfft_part": (_i64, [_int]),
+    "gf_lsfft_prepare": (_int, [_int, _int, _i64] + [_vp] * 10 + [_vp]),
+    "gf_lsfft_spread": (_int, [_int, _int, _i64, _i64, _i64] + [_vp] * 12 + [_vp]),
+    "gf_lsfft_finish": (_int, [_int, _i64, _int] + [_vp] * 10 + [_vp]),
     "gf_grad_work": (_i64, [_i64, _int]),
     "gf_loglike_grad": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
                         + [_vp] * 6 + [_vp]),

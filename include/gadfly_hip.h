@@ -651,6 +651,45 @@ int gf_ls_power(int R, int64_t n_max, int64_t n_total, int64_t out_total, int S_
                 const double *t, const double *y, double *work, double *power, void *stream);
 
 /*
+ * The same Lomb-Scargle power spectra (PowerSpectrum._lomb_scargle, gadfly/psd.py:589-601: what astropy's
+ * LombScargle(...).power(rfftfreq(n, d)) computes there, gadfly/psd.py:596-600) through a non-uniform FFT, in
+ * O(n log n): the seven sums from two type-1 transforms with real strengths, F_1(k) = sum_j e^{2 pi i k x_j}
+ * (k <= 2 [n/2]) and F_y(k) = sum_j y'_j e^{2 pi i k x_j} (k <= [n/2]), x = frac((t - t_0) df).  Points are spread
+ * onto a fine grid of n_f = gf_lsfft_grid(n) cells (the next 2-3-5-smooth integer >= 4 (2 [n/2] + 1) + 32) with
+ * the kernel exp(beta (sqrt(1 - z^2) - 1)) of width 16 cells, beta = 36.8, the caller transforms the grids (rfft)
+ * and gf_lsfft_finish deconvolves and forms the power with gf_ls_power's formula and degenerate limits.  The
+ * result agrees with gf_ls_power within its own test bar (rtol 1e-8, atol 1e-10 max).
+ * Layout: A time axes (axis a: the points ax_off[a] <= i < ax_off[a+1] of t, its fine grid the cells
+ * cell_off[a] <= c < cell_off[a+1] of all grids' cells, df[a] = 1/(n d)); R >= A series (series r: the points
+ * pt_off[r] <= i < pt_off[r+1] of y, on axis axis[r] of the same length; axes are numbered by their first series).
+ * All offset arrays are int64 device arrays, df, norm double device arrays.  The steps of one call:
+ *   gf_lsfft_prepare: key[i] <- cell_off[a] + floor(u_i), u[i] <- frac((t_i - t_0) df[a]) n_f (per axis point),
+ *     yc <- (y - y_0) - mean per series (centred on the first value, then the mean, as gf_ls_power does; the mean
+ *     from min(64, ceil(n/16384)) partial sums in order, part: gf_lsfft_part(R) doubles of scratch);
+ *   the caller sorts key (stable) into skey with the permutation perm (int64);
+ *   gf_lsfft_spread: start [cells + 1] (scratch) <- per-cell offsets into the sorted points; then
+ *     grid[gy_off[r] + c] <- sum_j y'_j phi, and where g1_off[r] >= 0 grid[g1_off[r] + c] <- sum_j phi (the grid
+ *     of ones of an axis is written by one of its series), c < n_f; each cell sums the points of its window in
+ *     sorted order (no atomics).  n_axes = ax_off[A], cells = cell_off[A], nf_max the largest n_f;
+ *   the caller transforms every grid: spec <- rfft(grid) (n_f/2 + 1 interleaved complex values each);
+ *   gf_lsfft_finish: power[out_off[r] + k - first] <- P(k df) norm[r], first <= k <= n_r/2, from the transforms
+ *     at sy_off[r] (of y') and s1_off[r] (of ones; offsets in complex values into spec, 16-byte aligned);
+ *     quad [128]: 64 Gauss-Legendre nodes on [0, 1], then their weights.
+ */
+int64_t gf_lsfft_grid(int64_t n);
+int64_t gf_lsfft_part(int R);
+int gf_lsfft_prepare(int A, int R, int64_t n_max, const int64_t *ax_off, const int64_t *cell_off, const double *df,
+                     const int64_t *pt_off, const double *t, const double *y, int64_t *key, double *u, double *yc,
+                     double *part, void *stream);
+int gf_lsfft_spread(int A, int R, int64_t n_axes, int64_t cells, int64_t nf_max, const int64_t *ax_off,
+                    const int64_t *cell_off, const int64_t *pt_off, const int64_t *axis, const int64_t *gy_off,
+                    const int64_t *g1_off, const int64_t *skey, const int64_t *perm, const double *u, const double *yc,
+                    int64_t *start, double *grid, void *stream);
+int gf_lsfft_finish(int R, int64_t n_max, int first, const int64_t *pt_off, const int64_t *out_off, const int64_t *axis,
+                    const int64_t *cell_off, const int64_t *sy_off, const int64_t *s1_off, const double *norm,
+                    const double *quad, const double *spec, double *power, void *stream);
+
+/*
  * Missing cadences of an evenly sampled light curve filled by linear interpolation: replaces
  * interpolate_missing_data (gadfly/interp.py:6-60; called at psd.py:495, :531 before every FFT).
  * t, f [N] ascending times and fluxes; cadences [N] int64 or NULL (then the cadence index of a
