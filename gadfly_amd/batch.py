@@ -19,7 +19,7 @@ Batch shapes:
 import numpy as np
 
 from . import _lib
-from .engine import StreamingBatch
+from .engine import CoefficientPack, StreamingBatch
 
 __all__ = ["BatchedLogLikelihood", "log_likelihood_batch", "sho_coefficient_pack",
            "BatchedSampler", "sample_batch", "predict_batch"]
@@ -81,7 +81,7 @@ def sho_coefficient_pack(S0, w0, Q, delta, eps=1e-5):
     return Jr, Jc, real, comp, diag_add, c
 
 
-class _Pack(tuple):
+class _Pack(CoefficientPack):
     """A coefficient pack of the engine that remembers whether its kernels are positive semi-definite by
     construction (sums of SHO terms with positive S0, w0, Q, possibly exposure-integrated)."""
     psd_safe = False
@@ -285,7 +285,7 @@ class BatchedLogLikelihood:
         return self.engine.B
 
     def pack(self, kernels):
-        pk = _Pack(self.engine.pack_coefficients([k.get_device_coefficients() for k in kernels]))
+        pk = _Pack(*self.engine.pack_coefficients([k.get_device_coefficients() for k in kernels]))
         pk.psd_safe = all(_sho_only(k, self._dt_min, self._t_abs_max) for k in kernels)
         pk.delta = self._deltas_of(kernels)
         return pk
@@ -293,7 +293,7 @@ class BatchedLogLikelihood:
     def pack_parameters(self, S0, w0, Q, delta):
         """Coefficient pack straight from (B, J) hyperparameter arrays (:func:`sho_coefficient_pack`):
         the vectorised form of :meth:`pack` for ``StellarOscillatorKernel``-type kernels."""
-        pk = _Pack(self.engine.pack_arrays(*sho_coefficient_pack(S0, w0, Q, delta)))
+        pk = _Pack(*self.engine.pack_arrays(*sho_coefficient_pack(S0, w0, Q, delta)))
         pk.psd_safe = bool(np.all(np.asarray(S0) > 0.0) and np.all(np.asarray(w0) > 0.0)
                            and np.all(np.asarray(Q) > 0.0)
                            and all(_exposure_resolved(float(dl), self._dt_min, self._t_abs_max)
@@ -793,7 +793,7 @@ class BatchedLogLikelihood:
         if eng._fused_ok() or eng._wide_ok():
             torch = eng.torch
             acc = eng.last_acc()
-            amax = eng._pack[2] if eng.diag is None else eng._pack[2] + eng._diag_amax
+            amax = eng._pack.diag_add if eng.diag is None else eng._pack.diag_add + eng._diag_amax
             # min pivot and largest diagonal of THIS evaluation (what calibrate() looks at; the
             # engine's own state may belong to a guard rerun of an older pack by then); a two-sweep
             # evaluation has the nominal pass' pivots only: margin (engine.TWO_SWEEP_MARGIN)
@@ -1131,7 +1131,7 @@ class BatchedSampler:
                 period = int(self._auto_period or eng.generator_period)
             dmin, info = self._sweeps(eps, out, period)
             if self.auto_generator_period:
-                amax = eng._pack[2] if eng._diag_amax is None else eng._pack[2] + eng._diag_amax
+                amax = eng._pack.diag_add if eng._diag_amax is None else eng._pack.diag_add + eng._diag_amax
                 ok = info == 0
                 if period > 1:
                     flag = (eng.generator_error_coefficient(period) * amax > self.generator_target * dmin) & ok

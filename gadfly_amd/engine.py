@@ -15,8 +15,10 @@ HBM layout (float64, row-major, all torch tensors on one device):
                                 hold 0 for U/V/W and 1 for P)
     c              (B, Wd)      decay rates per column (prediction hops only)
 """
+import contextlib
 import functools
 import math
+import typing
 
 import numpy as np
 
@@ -77,6 +79,85 @@ def _complexify_pack(Jr, Jc, real, comp, diag_add, c):
     c2[:, 0::2] = comp2[2, :, :J]
     c2[:, 1::2] = comp2[2, :, :J]
     return 0, J, np.zeros((2, B, 1)), comp2, diag_add, c2
+
+
+class CoefficientPack(typing.NamedTuple):
+    """The coefficients of B kernels as :class:`StreamingBatch` keeps them (``_make_pack``): five device arrays -- views
+    into one buffer -- and four host scalars.  A tuple still: slices and positional reads keep working."""
+    real: typing.Any            # (2, B, max(Jr, 1)): a, c of the real terms
+    comp: typing.Any            # (4, B, max(Jc, 1)): a, b, c, d of the complex terms
+    diag_add: typing.Any        # (B,): sum of the amplitudes plus the kernel's own diagonal shift
+    c: typing.Any               # (B, W): decay rate of every state column
+    cmax: typing.Any            # (B,): largest decay rate per problem
+    block: int                  # the short span's rows between forced resets of the scaled coordinates (every route)
+    dmax: float                 # max |d| over the batch, for the phase-range tests
+    stream_block: int           # the long span's rows between resets (the streamed sweep); 0: not allowed
+    wmax: float                 # max(largest decay rate, dmax): what the row generator's cadence test divides by
+
+
+def _bs(x):
+    """batch stride in elements (0 = shared)."""
+    return 0 if x.shape[0] == 1 else x.stride(0)
+
+
+def coefficient_pointers(pack):
+    """(ar, cr, ac, bc, cc, dc): the six coefficient pointers of every entry point that generates rows."""
+    p, real, comp = _lib.ptr, pack.real, pack.comp
+    return p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3])
+
+
+def series_arguments(t, diag, y, y_bs=None):
+    """(t, t_bs, diag, diag_bs, y, y_bs): the series' arrays with their batch strides; (None, 0) for a missing
+    diagonal.  `y_bs` overrides the stride of y (a view whose rows lie further apart than its shape says)."""
+    p = _lib.ptr
+    return (p(t), _bs(t), p(diag), 0 if diag is None else _bs(diag), p(y), _bs(y) if y_bs is None else y_bs)
+
+
+def kernel_and_series(pack, t, diag, y, y_bs=None):
+    """(ar ... dc, diag_add, cmax, t ... y_bs): the 14 arguments that name the kernels and the series, in the order
+    every sweep that generates its own rows takes them (the fused sweeps and gf_chunk_sweep)."""
+    p = _lib.ptr
+    return (*coefficient_pointers(pack), p(pack.diag_add), p(pack.cmax), *series_arguments(t, diag, y, y_bs))
+
+
+def sweep_options(pack, sweep_variant):
+    """(block, variant) of a streamed sweep: the long scaling span where the pack allows it (one-wave sweeps,
+    amplitudes in range), the short span's block otherwise."""
+    variant = int(sweep_variant)
+    if pack.stream_block:
+        return pack.stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
+    return pack.block, variant
+
+
+def sweep_head(pack, B, rows, n_first, Jr, Jc, block, period, variant, t, diag, y, d, z, S_state, F_state, info,
+               y_bs=None):
+    """The 27 arguments gf_loglike_fused, gf_loglike_steady, gf_steady_sweep, gf_steady_sweep_reduced and
+    gf_sample_fused share, B ... info, in the order of include/gadfly_hip.h."""
+    p = _lib.ptr
+    return (B, rows, n_first, Jr, Jc, block, period, variant, *kernel_and_series(pack, t, diag, y, y_bs),
+            p(d), p(z), p(S_state), p(F_state), p(info))
+
+
+def finish_head(pack, B, N, Jr, Jc, block, variant, t, y, info, steady, acc):
+    """The 18 arguments gf_steady_finish, gf_steady_finish_window and gf_steady_finish_chunked share, B ... acc."""
+    p = _lib.ptr
+    return (B, N, Jr, Jc, block, variant, *coefficient_pointers(pack)[2:], p(pack.cmax), p(t), _bs(t), p(y), _bs(y),
+            p(info), p(steady), p(acc))
+
+
+@contextlib.contextmanager
+def _timed(torch, enabled, stream, events, *extra):
+    """With `enabled` (an engine's time_factor), a HIP event pair around the block on `stream` (None: the current
+    one), appended to `events` as (start, end, *extra); nothing at all without."""
+    if not enabled:
+        yield
+        return
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    yield
+    e1.record(stream)
+    events.append((e0, e1) + extra)
 
 
 class DeviceBatch:
@@ -221,19 +302,13 @@ class DeviceBatch:
             if self.z is None:
                 self.z = torch.empty((B, N), **f64)
         p = _lib.ptr
-        if self.time_factor:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        self.info.zero_()
-        st = self.lib.gf_factor(
-            B, N, 0, self.W, ld, p(self.a), p(self.U), p(self.V), p(self.P),
-            p(y), yb, p(self.d), p(self.Wm) if keep_W else None,
-            p(self.z) if y is not None else None, None, None, p(self.info),
-            self._stream())
-        if self.time_factor:
-            e1.record()
-            self.factor_events.append((e0, e1))
+        with _timed(torch, self.time_factor, None, self.factor_events):
+            self.info.zero_()
+            st = self.lib.gf_factor(
+                B, N, 0, self.W, ld, p(self.a), p(self.U), p(self.V), p(self.P),
+                p(y), yb, p(self.d), p(self.Wm) if keep_W else None,
+                p(self.z) if y is not None else None, None, None, p(self.info),
+                self._stream())
         _lib.check(st, "gf_factor")
         return self.info
 
@@ -347,7 +422,7 @@ class ScaledFactor:
         self.device = owner.device
         self.B, self.N, self.W = owner.B, owner.N, owner.W
         self.chunk_len, self.nch = chunk_len, nch
-        self.block = int(owner._pack[5])        # scaling block of the stored rows: reset rows at its multiples
+        self.block = int(owner._pack.block)     # scaling block of the stored rows: reset rows at its multiples
         w = owner._tp
         self.Ut, self.Wt, self.de, self.Phi = w["Ut"], w["Wt"], w["de"], w["PhiT"]
         # own copy of the pivots: the shared buffer holds the nominal pass' values while a later
@@ -357,7 +432,7 @@ class ScaledFactor:
         # of the final pass, still in the owner's buffer unless it has run another evaluation since
         self._phi_ready = nch <= 1
         self._r_rows, self._r_generation = w["r"], getattr(owner, "_tp_generation", 0)
-        self.c = owner._pack[3]
+        self.c = owner._pack.c
         self.t = owner.t
         self.info = owner.info
         self._v1 = None
@@ -537,8 +612,8 @@ class WideFactor:
         self.de = torch.empty((B * N + 8,), **f64)[:B * N].view(B, N)
         self.d = torch.empty((B * N + 8,), **f64)[:B * N].view(B, N)
         self.z = torch.empty((B * N + 8,), **f64)[:B * N].view(B, N)
-        real, comp, diag_add, c, cmax, block, _ = owner._pack[:7]
-        self.c, self.t = c, owner.t
+        pack = owner._pack
+        self.c, self.t = pack.c, owner.t
         self.info = torch.zeros((B,), dtype=torch.int32, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
         # (the chunk-parallel SWEEPS on the stored factor are for one series; a batch is swept whole)
@@ -553,17 +628,14 @@ class WideFactor:
             self._tp_bufs = owner._wide_tp_bufs          # r rows of the TRUE factor, h / Phi scratch
         else:
             S = torch.zeros((B, int(lib.gf_fused_state_size(owner.Jr, owner.Jc))), **f64)
-            bs = owner._bs
             rc = lib.gf_chunk_sweep(
-                B, N, N, 1, 0, 1, owner.Jr, owner.Jc, block, int(owner.generator_period), _lib.GF_SWEEP_AUTO,
-                p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-                p(diag_add), p(cmax), p(owner.t), bs(owner.t), p(owner.diag),
-                0 if owner.diag is None else bs(owner.diag), p(owner.y), bs(owner.y),
+                B, N, N, 1, 0, 1, owner.Jr, owner.Jc, pack.block, int(owner.generator_period), _lib.GF_SWEEP_AUTO,
+                *kernel_and_series(pack, owner.t, owner.diag, owner.y),
                 p(self.d), p(self.z), None, p(self.Ut), p(self.Wt), p(self.de),
                 p(S), None, p(self.info), st)
             _lib.check(rc, "gf_chunk_sweep")
         self.P = torch.empty((B, N, self.ld), **f64)
-        rc = lib.gf_scaled_propagator(B, N, self.W, self.ld, p(c), p(self.de), p(self.P), st)
+        rc = lib.gf_scaled_propagator(B, N, self.W, self.ld, p(self.c), p(self.de), p(self.P), st)
         _lib.check(rc, "gf_scaled_propagator")
         self._v1 = None
         self._Phi = None
@@ -992,9 +1064,7 @@ class StreamingBatch:
         self.time_factor = False
         self.factor_events = []
 
-    @staticmethod
-    def _bs(x):
-        return 0 if x.shape[0] == 1 else x.stride(0)
+    _bs = staticmethod(_bs)
 
     def _alloc_bufs(self):
         torch = self.torch
@@ -1007,11 +1077,11 @@ class StreamingBatch:
 
     def _fused_ok(self):
         """Phases d*t must stay inside fm_sincos's range (|x| < 1e12: FM_SINCOS_RANGE of fastmath.h)."""
-        return self.allow_fused and self._pack[6] * self._tmax < SINCOS_RANGE
+        return self.allow_fused and self._pack.dmax * self._tmax < SINCOS_RANGE
 
     def _wide_ok(self):
         """The fused sweep for wide kernels (same phase range; log-likelihood streaming only)."""
-        return self.allow_wide and self._pack[6] * self._tmax < SINCOS_RANGE
+        return self.allow_wide and self._pack.dmax * self._tmax < SINCOS_RANGE
 
     # error of the log-likelihood ~ GEN_ERR * period * condition (measured: 1e-8 at period 16 and a
     # condition of 4e5, DESIGN.md 2.1a)
@@ -1037,7 +1107,10 @@ class StreamingBatch:
     def phase_quantum(self):
         """Half an ulp of the largest phase |d t| a rotation step may still see un-corrected: tiles and chunks that
         start beyond QMODE_PHASE follow the rounded phases exactly."""
-        return min(float(self._pack[6]) * self._tmax, self.QMODE_PHASE) * 2.0 ** -53
+        # (the field's own getter, which takes any tuple in the pack's order: tests/random_cases.py evaluates the
+        # period formulas on the host, on a stand-in whose pack is a plain tuple that ends with dmax)
+        dmax = CoefficientPack.dmax.__get__(self._pack)
+        return min(float(dmax) * self._tmax, self.QMODE_PHASE) * 2.0 ** -53
 
     def phase_error_coefficient(self):
         """Relative log-likelihood error per unit of condition number that a generator period > 1 adds through
@@ -1066,7 +1139,7 @@ class StreamingBatch:
         dmin = float(self.last_acc()[:, 2].min().item())
         if getattr(self, "_two_sweep_used", False):
             dmin /= self.TWO_SWEEP_MARGIN
-        amax = float(self._pack[2].max().item())
+        amax = float(self._pack.diag_add.max().item())
         if self._diag_amax is not None:
             amax += float(self._diag_amax.max().item())      # (a ragged batch sets it from its real rows)
         return amax / dmin if dmin > 0.0 else float("inf")
@@ -1136,7 +1209,7 @@ class StreamingBatch:
             host[o:o + a.size] = a.reshape(-1)
         buf = dev(host)
         real, comp, diag_add, c, cmax = (buf[o:o + a.size].view(a.shape) for a, o in zip(arrs, offs))
-        return real, comp, diag_add, c, cmax, block, dmax, stream_block, wmax
+        return CoefficientPack(real, comp, diag_add, c, cmax, block, dmax, stream_block, wmax)
 
     def pack_coefficients(self, coeffs_list):
         if len(coeffs_list) != self.B:
@@ -1159,23 +1232,18 @@ class StreamingBatch:
     def _build_tile(self, k, buf, stream):
         n0 = k * self.tile_rows
         rows = min(self.tile_rows, self.N - n0)
-        real, comp, diag_add, _, cmax, block, _ = self._pack[:7]
-        p = _lib.ptr
+        pack, p = self._pack, _lib.ptr
+        coeffs = coefficient_pointers(pack)
+        t_diag = series_arguments(self.t, self.diag, self.y)[:4]
         if self.scaled or self.scaled_wide:
             st = self.lib.gf_build_scaled(
-                self.B, rows, n0, self.Jr, self.Jc, self.ld,
-                p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-                p(diag_add), p(cmax), block, p(self.t), self._bs(self.t),
-                p(self.diag), 0 if self.diag is None else self._bs(self.diag),
-                p(buf["a"]), p(buf["U"]), p(buf["V"]), p(buf["de"]), stream.cuda_stream)
+                self.B, rows, n0, self.Jr, self.Jc, self.ld, *coeffs, p(pack.diag_add), p(pack.cmax), pack.block,
+                *t_diag, p(buf["a"]), p(buf["U"]), p(buf["V"]), p(buf["de"]), stream.cuda_stream)
             _lib.check(st, "gf_build_scaled")
             return
         st = self.lib.gf_build_matrices(
-            self.B, rows, n0, self.Jr, self.Jc, self.ld,
-            p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-            p(diag_add), p(self.t), self._bs(self.t),
-            p(self.diag), 0 if self.diag is None else self._bs(self.diag),
-            p(buf["a"]), p(buf["U"]), p(buf["V"]), p(buf["P"]), stream.cuda_stream)
+            self.B, rows, n0, self.Jr, self.Jc, self.ld, *coeffs, p(pack.diag_add),
+            *t_diag, p(buf["a"]), p(buf["U"]), p(buf["V"]), p(buf["P"]), stream.cuda_stream)
         _lib.check(st, "gf_build_matrices")
 
     @_on_device
@@ -1212,26 +1280,20 @@ class StreamingBatch:
             n0 = k * T
             rows = min(T, N - n0)
             main.wait_event(built[i])
-            if self.time_factor:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(main)
-            if self.scaled or self.scaled_wide:
-                st = lib.gf_factor_scaled(
-                    B, rows, n0, self.W, self.ld, p(self._pack[3]), p(buf["a"]),
-                    p(buf["U"]), p(buf["V"]), p(buf["de"]), self.y.data_ptr() + 8 * n0,
-                    self._bs(self.y), p(self.d), p(self.z), p(self.S_state),
-                    p(self.F_state), p(self.info), main.cuda_stream)
-            else:
-                st = lib.gf_factor(
-                    B, rows, n0, self.W, self.ld, p(buf["a"]), p(buf["U"]), p(buf["V"]),
-                    p(buf["P"]), self.y.data_ptr() + 8 * n0, self._bs(self.y),
-                    p(self.d), None, p(self.z), p(self.S_state), p(self.F_state),
-                    p(self.info), main.cuda_stream)
-            _lib.check(st, "gf_factor")
-            if self.time_factor:
-                e1.record(main)
-                self.factor_events.append((e0, e1, rows))
+            with _timed(torch, self.time_factor, main, self.factor_events, rows):
+                if self.scaled or self.scaled_wide:
+                    st = lib.gf_factor_scaled(
+                        B, rows, n0, self.W, self.ld, p(self._pack.c), p(buf["a"]),
+                        p(buf["U"]), p(buf["V"]), p(buf["de"]), self.y.data_ptr() + 8 * n0,
+                        self._bs(self.y), p(self.d), p(self.z), p(self.S_state),
+                        p(self.F_state), p(self.info), main.cuda_stream)
+                else:
+                    st = lib.gf_factor(
+                        B, rows, n0, self.W, self.ld, p(buf["a"]), p(buf["U"]), p(buf["V"]),
+                        p(buf["P"]), self.y.data_ptr() + 8 * n0, self._bs(self.y),
+                        p(self.d), None, p(self.z), p(self.S_state), p(self.F_state),
+                        p(self.info), main.cuda_stream)
+                _lib.check(st, "gf_factor")
             freed[i] = main.record_event()
             if k + nb < ntiles:          # refill this buffer with tile k + nb on the side stream
                 side.wait_event(freed[i])
@@ -1252,10 +1314,11 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         T, N, B = self.tile_rows, self.N, self.B
-        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack[:8]
-        period, variant = int(self.generator_period), int(self.sweep_variant)
-        if stream_block:                    # the long scaling span (one-wave sweeps, amplitudes in range)
-            block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
+        pack = self._pack
+        block, variant = sweep_options(pack, self.sweep_variant)
+        # (a tile's call takes its rows and first row in front of these: everything else is the evaluation's)
+        per_tile = sweep_head(pack, B, 0, 0, self.Jr, self.Jc, block, int(self.generator_period), variant, self.t,
+                              self.diag, self.y, self.d, self.z, self.S_state, self.F_state, self.info)[3:]
         self.kernel_used = "fused-wide" if self.W > 63 else "fused"
         arm_from = self._steady_arm_from()
         start = None if arm_from is None else self._steady_plan(arm_from)
@@ -1290,48 +1353,31 @@ class StreamingBatch:
 
         def finish(name, stream, *tail):
             """One finishing launch on `stream`, with an event pair of its own."""
-            if self.time_factor:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-            st = getattr(lib, name)(B, N, self.Jr, self.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]),
-                                    p(comp[3]), p(cmax), p(self.t), self._bs(self.t), p(self.y), self._bs(self.y),
-                                    p(self.info), p(self._steady), p(self.acc), *tail, stream.cuda_stream)
-            _lib.check(st, name)
-            if self.time_factor:
-                e1.record(stream)
-                self.finish_events.append((e0, e1))
+            with _timed(torch, self.time_factor, stream, self.finish_events):
+                head = finish_head(pack, B, N, self.Jr, self.Jc, block, variant, self.t, self.y, self.info,
+                                   self._steady, self.acc)
+                st = getattr(lib, name)(*head, *tail, stream.cuda_stream)
+                _lib.check(st, name)
 
         for k in range(ntiles):
             n0 = k * T
             rows = min(T, N - n0)
-            if self.time_factor:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(main)
-            args = (B, rows, n0, self.Jr, self.Jc, block, period, variant,
-                    p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-                    p(diag_add), p(cmax), p(self.t), self._bs(self.t),
-                    p(self.diag), 0 if self.diag is None else self._bs(self.diag),
-                    p(self.y), self._bs(self.y), p(self.d), p(self.z),
-                    p(self.S_state), p(self.F_state), p(self.info))
+            args = (B, rows, n0) + per_tile
             steady_tile = self.steady_used and n0 + rows > start    # (both instances hand over the same state)
             # behind the split ~90 % of the problems have no rows left: the sweep's own wave adds its tile to acc there
             # (gf_steady_sweep_reduced: the additions of gf_reduce_tile_steady, without its 3 B workgroups)
             reduced = steady_tile and split and k > k_e and self.steady_sweep_reduces
-            if reduced:
-                st = lib.gf_steady_sweep_reduced(*args, p(self._steady), arm_from, p(self.acc), 1 if k == 0 else 0,
-                                                 main.cuda_stream)
-                _lib.check(st, "gf_steady_sweep_reduced")
-            elif steady_tile:
-                st = lib.gf_steady_sweep(*args, p(self._steady), arm_from, main.cuda_stream)
-                _lib.check(st, "gf_steady_sweep")
-            else:
-                st = lib.gf_loglike_fused(*args, main.cuda_stream)
-                _lib.check(st, "gf_loglike_fused")
-            if self.time_factor:
-                e1.record(main)
-                self.factor_events.append((e0, e1, rows))
+            with _timed(torch, self.time_factor, main, self.factor_events, rows):
+                if reduced:
+                    st = lib.gf_steady_sweep_reduced(*args, p(self._steady), arm_from, p(self.acc), 1 if k == 0 else 0,
+                                                     main.cuda_stream)
+                    _lib.check(st, "gf_steady_sweep_reduced")
+                elif steady_tile:
+                    st = lib.gf_steady_sweep(*args, p(self._steady), arm_from, main.cuda_stream)
+                    _lib.check(st, "gf_steady_sweep")
+                else:
+                    st = lib.gf_loglike_fused(*args, main.cuda_stream)
+                    _lib.check(st, "gf_loglike_fused")
             if reduced:                     # (the sweep has added its rows)
                 pass
             elif steady_tile:               # the rows in front of each problem's switch row: the others were not stored
@@ -1472,9 +1518,9 @@ class StreamingBatch:
         an axis that is regular -- well inside the generator's own test |ddt| < 2e-6 / wmax -- and a diagonal that
         is constant from that row on."""
         if not (self.steady_state and self._fused_ok() and self.Jr == 0 and self.Jc <= 31
-                and (int(self.sweep_variant) & 0xff) != _lib.GF_SWEEP_COLUMN and len(self._pack) > 8):
+                and (int(self.sweep_variant) & 0xff) != _lib.GF_SWEEP_COLUMN):
             return None
-        wmax = float(self._pack[8])
+        wmax = float(self._pack.wmax)
         if not (wmax > 0.0) or wmax * self._tmax > self.QMODE_PHASE:
             return None
         arm, jit = self._steady_axis_scan()
@@ -1504,7 +1550,7 @@ class StreamingBatch:
             return (f"the fused sweeps take W <= 63 with any mix of terms and 64 <= W <= 176 with complex terms "
                     f"only (here W = {self.W}, Jr = {self.Jr}, Jc = {self.Jc})")
         return (f"the fused sweeps need phases max|d| * max|t| < {SINCOS_RANGE:g} rad "
-                f"(here {float(self._pack[6]) * self._tmax:.3g})")
+                f"(here {float(self._pack.dmax) * self._tmax:.3g})")
 
     @_on_device
     def sample_fused(self, eps, out):
@@ -1519,7 +1565,7 @@ class StreamingBatch:
         if reason is not None:
             raise NotImplementedError("batched sampling runs on the fused sweeps only: " + reason)
         torch = self.torch
-        lib, p = self.lib, _lib.ptr
+        lib = self.lib
         T, N, B = self.tile_rows, self.N, self.B
         for x in (eps, out):
             if (x.dtype != torch.float64 or x.device != self.device or tuple(x.shape) != (B, N)
@@ -1529,25 +1575,19 @@ class StreamingBatch:
         if B > 1 and (int(out.stride(0)) != bs or bs < N):
             raise ValueError("eps and out must share one batch stride")
         main = torch.cuda.current_stream(self.device)
-        real, comp, diag_add, _, cmax, block, _, stream_block = self._pack[:8]
-        period, variant = int(self.generator_period), int(self.sweep_variant)
-        if stream_block:                    # the long scaling span (one-wave sweeps, amplitudes in range)
-            block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
+        block, variant = sweep_options(self._pack, self.sweep_variant)
         self.S_state.zero_()
         self.F_state.zero_()
         info = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        # (eps and out where the log-likelihood's sweep has y and z, with the stride of their own)
+        per_tile = sweep_head(self._pack, B, 0, 0, self.Jr, self.Jc, block, int(self.generator_period), variant,
+                              self.t, self.diag, eps, self.d, out, self.S_state, self.F_state, info, y_bs=bs)[3:]
         self.kernel_used = "sample-wide" if self.W > 63 else "sample"
         dmin = None
         for k in range((N + T - 1) // T):
             n0 = k * T
             rows = min(T, N - n0)
-            st = lib.gf_sample_fused(
-                B, rows, n0, self.Jr, self.Jc, block, period, variant,
-                p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-                p(diag_add), p(cmax), p(self.t), self._bs(self.t),
-                p(self.diag), 0 if self.diag is None else self._bs(self.diag),
-                p(eps), bs, p(self.d), p(out),
-                p(self.S_state), p(self.F_state), p(info), main.cuda_stream)
+            st = lib.gf_sample_fused(B, rows, n0, *per_tile, main.cuda_stream)
             _lib.check(st, "gf_sample_fused")
             # (rows of a problem that has failed are stale here: its info says so, its dmin means nothing)
             m = self.d.view(-1)[:B * rows].view(B, rows).amin(dim=1)
@@ -1560,7 +1600,7 @@ class StreamingBatch:
 
     def _tp_chunking(self, chunk_len, store=False):
         N, B = self.N, self.B
-        block = self._pack[5]
+        block = self._pack.block
         if chunk_len is None:
             # B * nch ~ 2048 waves = 2 per SIMD, the occupancy the sweep kernels are built for; below ~512 rows per
             # chunk the extra tree levels cost more than the sweeps save.  (+ 1: the last chunk sits out the nominal
@@ -1587,7 +1627,7 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         N, B = self.N, self.B
-        real, comp, diag_add, _, cmax, block, _ = self._pack[:7]
+        pack = self._pack
         chunk_len, nch = self._tp_chunking(chunk_len, store)
         opts = (int(self.generator_period), int(self.sweep_variant))
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -1625,20 +1665,19 @@ class StreamingBatch:
         w["info"].zero_()
         # nominal passes start every chunk from zero by themselves: the state slots are outputs only
         zopts = (opts[0], opts[1] | _lib.GF_SWEEP_ZERO_START)
-        coeffs = (p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]))
-        tyd = (p(self.t), self._bs(self.t), p(self.diag),
-               0 if self.diag is None else self._bs(self.diag), p(self.y), self._bs(self.y))
+        # what every gf_chunk_sweep of this evaluation takes between its options and its outputs
+        series = kernel_and_series(pack, self.t, self.diag, self.y)
         none3 = (None, None, None)
         ci = w["info"].view(B, nch)
 
         def transition(first, count, Ut, de, phi="Phi"):
             rc = lib.gf_chunk_transition(B, N, chunk_len, nch, first, count, self.Jr, self.Jc,
-                                         int(self.sweep_variant), p(self._pack[3]), p(de), p(w["d"]), p(w["z"]),
+                                         int(self.sweep_variant), p(pack.c), p(de), p(w["d"]), p(w["z"]),
                                          p(w["r"]), p(Ut), p(w[phi]), p(w["G"]), p(w["m"]), st)
             _lib.check(rc, "gf_chunk_transition")
 
         if self.two_sweep and not store and nch > 1 and B * nch <= 65535:
-            return self._tp_two_sweep(w, chunk_len, nch, zopts, coeffs, tyd, transition, st)
+            return self._tp_two_sweep(w, chunk_len, nch, zopts, series, transition, st)
         # chunk 0 starts from the zero state: its nominal pass IS its final pass (not when the factor is
         # stored: the final pass also writes the w~ rows)
         skip_first = nch > 1 and not store
@@ -1646,8 +1685,8 @@ class StreamingBatch:
         if nch > 1:
             # nominal pass (u~ rows and reset spans stored for the transition sweep).  Nothing of the LAST
             # chunk's map is ever needed: it is left out
-            rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, 0, nch - 1, self.Jr, self.Jc, block, *zopts, *coeffs,
-                                    p(diag_add), p(cmax), *tyd, p(w["d"]), p(w["z"]), p(w["r"]),
+            rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, 0, nch - 1, self.Jr, self.Jc, pack.block, *zopts, *series,
+                                    p(w["d"]), p(w["z"]), p(w["r"]),
                                     p(w["Un"]), None, p(w["den"]), p(w["S"]), p(w["F"]), p(w["info"]), st)
             _lib.check(rc, "gf_chunk_sweep")
             self._clear_slots(w["S"], nch, nch - 1)
@@ -1665,9 +1704,8 @@ class StreamingBatch:
             w["info"].zero_()
         stores = (p(w["Ut"]), p(w["Wt"]), p(w["de"])) if store else none3
         f0 = 1 if skip_first else 0         # (chunk 0's d, z rows stay where the nominal pass wrote them)
-        rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, f0, nch - f0, self.Jr, self.Jc, block,
-                                *(zopts if nch == 1 else opts), *coeffs,
-                                p(diag_add), p(cmax), *tyd, p(w["d"]), p(w["z"]),
+        rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, f0, nch - f0, self.Jr, self.Jc, pack.block,
+                                *(zopts if nch == 1 else opts), *series, p(w["d"]), p(w["z"]),
                                 p(w["r"]) if (store and nch > 1) else None, *stores,
                                 p(w["S"]), p(w["F"]), p(w["info"]), st)
         _lib.check(rc, "gf_chunk_sweep")
@@ -1679,28 +1717,32 @@ class StreamingBatch:
         self._tp_generation = getattr(self, "_tp_generation", 0) + 1
         rc = lib.gf_reduce_tile(B, N, p(w["d"]), p(w["z"]), p(w["work"]), p(w["acc"]), 1, st)
         _lib.check(rc, "gf_reduce_tile")
-        # a chunk that failed marks its problem with the FIRST non-positive pivot (celerite2 and the
-        # sequential sweep stop there; chunks after a failed one ran from meaningless start states)
-        big = torch.iinfo(torch.int32).max
-        first = torch.where(ci > 0, ci, torch.full_like(ci, big)).min(dim=1).values
-        self.info.copy_(torch.where(first == big, torch.zeros_like(first), first))
+        self.info.copy_(self._first_failing_row(ci))
         out = torch.empty((B,), **f64)
         rc = lib.gf_loglike_finish(B, N, p(w["acc"]), p(self.info), p(out), None, st)
         _lib.check(rc, "gf_loglike_finish")
         self._tp_used, self._last_wide_tp, self._two_sweep_used = True, False, False
         return out, chunk_len, nch
 
-    def _tp_two_sweep(self, w, chunk_len, nch, opts, coeffs, tyd, transition, st):
+    def _first_failing_row(self, ci):
+        """(B,) from the chunks' info ci (B, nch): a chunk that failed marks its problem with the FIRST non-positive
+        pivot, 0 where none failed (celerite2 and the sequential sweep stop there; chunks after a failed one ran
+        from meaningless start states)."""
+        torch = self.torch
+        big = torch.iinfo(torch.int32).max
+        first = torch.where(ci > 0, ci, torch.full_like(ci, big)).min(dim=1).values
+        return torch.where(first == big, torch.zeros_like(first), first)
+
+    def _tp_two_sweep(self, w, chunk_len, nch, opts, series, transition, st):
         """Log-likelihood from TWO sweeps: the nominal pass over all chunks (its rows reduced as they are), the
         transition sweep of the chunks 1 ... nch - 1, the combine for the start states, and per chunk the
         corrections  log det(I - X G)  and  e^T G v - 2 m^T e - m^T X m  (gf_chunk_corrections) -- no final pass."""
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         N, B = self.N, self.B
-        real, comp, diag_add, _, cmax, block, _ = self._pack[:7]
         self._tp_generation = getattr(self, "_tp_generation", 0) + 1
-        rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, 0, nch, self.Jr, self.Jc, block, *opts, *coeffs,
-                                p(diag_add), p(cmax), *tyd, p(w["d"]), p(w["z"]), p(w["r"]),
+        rc = lib.gf_chunk_sweep(B, N, chunk_len, nch, 0, nch, self.Jr, self.Jc, self._pack.block, *opts, *series,
+                                p(w["d"]), p(w["z"]), p(w["r"]),
                                 p(w["Un"]), None, p(w["den"]), p(w["S"]), p(w["F"]), p(w["info"]), st)
         _lib.check(rc, "gf_chunk_sweep")
         rc = lib.gf_reduce_tile(B, N, p(w["d"]), p(w["z"]), p(w["work"]), p(w["acc"]), 1, st)
@@ -1717,10 +1759,7 @@ class StreamingBatch:
         _lib.check(rc, "gf_chunk_corrections")
         # a chunk of the nominal pass that failed: the first such row (exact for chunk 0; later chunks start
         # from zero, where pivots are never smaller than the true ones: the caller's final pass decides)
-        ci = w["info"].view(B, nch)
-        big = torch.iinfo(torch.int32).max
-        first = torch.where(ci > 0, ci, torch.full_like(ci, big)).min(dim=1).values
-        self.info.copy_(torch.where(first == big, torch.zeros_like(first), first))
+        self.info.copy_(self._first_failing_row(w["info"].view(B, nch)))
         out = torch.empty((B,), dtype=torch.float64, device=self.device)
         rc = lib.gf_loglike_finish(B, N, p(w["acc"]), p(self.info), p(out), None, st)
         _lib.check(rc, "gf_loglike_finish")
@@ -1845,7 +1884,7 @@ class StreamingBatch:
         torch = self.torch
         lib, p = self.lib, _lib.ptr
         B, N = self.B, self.N
-        real, comp, diag_add, c, cmax, block, _ = self._pack[:7]
+        pack = self._pack
         L, nch = self._wide_chunking(chunk_len)
         keep = stores is not None and nch > 1
         ws = self._wide_ws(L, nch, keep=stores is not None)
@@ -1856,15 +1895,13 @@ class StreamingBatch:
             Ut, Wt, de = stores
         dbar, zbar, rbar, h, S, Phi, cinfo = (ws[k] for k in ("dbar", "zbar", "rbar", "h", "S", "Phi", "cinfo"))
         opts = (int(self.generator_period), _lib.GF_SWEEP_AUTO)
-        coeffs = (p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]))
-        tyd = (p(self.t), self._bs(self.t), p(self.diag),
-               0 if self.diag is None else self._bs(self.diag), p(self.y), self._bs(self.y))
+        series = kernel_and_series(pack, self.t, self.diag, self.y)
 
         def sweep(first, count, dd, zz, r_out, st_rows, zero_start=False):
             # (zero_start: a nominal pass -- the state slots are outputs only, nothing has to be cleared)
             variant = opts[1] | (_lib.GF_SWEEP_ZERO_START if zero_start else 0)
-            rc = lib.gf_chunk_sweep(B, N, L, nch, first, count, self.Jr, self.Jc, block, opts[0], variant,
-                                    *coeffs, p(diag_add), p(cmax), *tyd, p(dd), p(zz), r_out, *st_rows,
+            rc = lib.gf_chunk_sweep(B, N, L, nch, first, count, self.Jr, self.Jc, pack.block, opts[0], variant,
+                                    *series, p(dd), p(zz), r_out, *st_rows,
                                     p(S), None, p(cinfo), st)
             _lib.check(rc, "gf_chunk_sweep")
 
@@ -1877,15 +1914,13 @@ class StreamingBatch:
             acc = ws["acc"]
             sweep(0, nch, dbar, zbar, p(rbar), (p(Ut), None, p(de)), zero_start=True)
             _lib.check(lib.gf_reduce_tile(B, N, p(dbar), p(zbar), p(ws["red"]), p(acc), 1, st), "gf_reduce_tile")
-            rc = lib.gf_chunk_transition_wide(B, N, L, nch, 1, nch - 1, self.Jc, p(c), p(de), p(dbar),
+            rc = lib.gf_chunk_transition_wide(B, N, L, nch, 1, nch - 1, self.Jc, p(pack.c), p(de), p(dbar),
                                               p(rbar), p(Ut), p(h), p(Phi), st)
             _lib.check(rc, "gf_chunk_transition_wide")
             rc = lib.gf_wide_combine(B, N, L, nch, self.Jc, p(h), p(dbar), p(zbar), p(Phi), p(S), p(acc),
                                      p(ws["work"]), st)
             _lib.check(rc, "gf_wide_combine")
-            big = torch.iinfo(torch.int32).max
-            first = torch.where(ci > 0, ci, torch.full_like(ci, big)).min(dim=1).values
-            self.info.copy_(torch.where(first == big, torch.zeros_like(first), first))
+            self.info.copy_(self._first_failing_row(ci))
             out = torch.empty((B,), dtype=torch.float64, device=self.device)
             logdet = torch.empty_like(out)
             _lib.check(lib.gf_loglike_finish(B, N, p(acc), p(self.info), p(out), p(logdet), st),
@@ -1902,7 +1937,7 @@ class StreamingBatch:
             self._clear_slots(S, nch, nch - 1)
             # 2. closed-loop transitions and the rows h (not for the first chunk either: from a zero start
             #    state its map acts through its end state alone)
-            rc = lib.gf_chunk_transition_wide(B, N, L, nch, 1, nch - 2, self.Jc, p(c), p(de), p(dbar),
+            rc = lib.gf_chunk_transition_wide(B, N, L, nch, 1, nch - 2, self.Jc, p(pack.c), p(de), p(dbar),
                                               p(rbar), p(Ut), p(h), p(Phi), st)
             _lib.check(rc, "gf_chunk_transition_wide")
             # 3. chunk maps (Phi, G, Xbar, Ybar, m) and their tree combine: S <- true start states
@@ -1924,10 +1959,7 @@ class StreamingBatch:
         if skip_first:
             ci[:, 0] = ci0
         self._wide_tp_bufs = dict(r=rbar, h=h, Phi=Phi) if keep else None
-        # a chunk that failed marks its problem with the FIRST non-positive pivot
-        big = torch.iinfo(torch.int32).max
-        first = torch.where(ci > 0, ci, torch.full_like(ci, big)).min(dim=1).values
-        flag = torch.where(first == big, torch.zeros_like(first), first)
+        flag = self._first_failing_row(ci)
         if info is not None:
             info.copy_(flag)
         self.info.copy_(flag)

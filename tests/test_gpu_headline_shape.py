@@ -30,7 +30,7 @@ def _coeffs(hps):
 
 def _check_route(eng):
     assert eng.kernel_used == "fused" and not eng._tp_used
-    assert eng._pack[7] == 64 and eng.generator_period == 64
+    assert eng._pack.stream_block == 64 and eng.generator_period == 64
 
 
 @pytest.mark.parametrize("axis", ["zero", "bkjd"])
@@ -48,10 +48,10 @@ def test_headline_configuration_against_the_oracle(hip, axis):
     ev = gadfly_amd.BatchedLogLikelihood(kernels, t, y, yerr=30.0)
     eng = ev.engine
     eng.force_streaming = True
-    assert (eng._pack[6] * eng._tmax > 4.0e6) == (axis == "bkjd")          # qmode on the BKJD axis only
+    assert (eng._pack.dmax * eng._tmax > 4.0e6) == (axis == "bkjd")          # qmode on the BKJD axis only
     ev.evaluate()                                                            # warm-up
     cond, period = ev.calibrate()
-    assert period == 64 and eng._pack[7] == 64, (cond, period)
+    assert period == 64 and eng._pack.stream_block == 64, (cond, period)
     outs, refs = [], []
     for step in (1, 2):
         hps, arr = _proposal(base, step)

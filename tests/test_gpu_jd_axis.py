@@ -58,7 +58,7 @@ def test_fused_routes_on_a_jd_axis(hip, J, N, kw):
     co = prob["kernel"].get_device_coefficients()
     ref = _ref(prob)
     eng = StreamingBatch([co], t, y, diag=prob["diag_user"], tile_rows=1024)
-    assert eng._pack[6] * eng._tmax > 3.5e9 and eng._fused_ok()        # beyond round 3's range, still fused
+    assert eng._pack.dmax * eng._tmax > 3.5e9 and eng._fused_ok()        # beyond round 3's range, still fused
     assert eng.generator_period == 4                                    # the default: rotation steps are allowed
     cond = None
     for period in (4, 1, 64):
@@ -96,7 +96,7 @@ def test_wide_routes_on_a_jd_axis(hip, J, N):
     co = prob["kernel"].get_device_coefficients()
     ref = _ref(prob)
     eng = StreamingBatch([co, co], t, y, diag=prob["diag_user"], tile_rows=1024)
-    assert eng._pack[6] * eng._tmax > 3.5e9 and eng._wide_ok() and not eng._fused_ok()
+    assert eng._pack.dmax * eng._tmax > 3.5e9 and eng._wide_ok() and not eng._fused_ok()
     for period in (1, 64):
         eng.generator_period = period
         ll = eng.log_likelihood().cpu().numpy()

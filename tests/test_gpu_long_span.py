@@ -27,7 +27,7 @@ def _coeffs(J, scale=1.0, fast=None):
 def _check(co, t, y, diag, block_expected, tol=1e-8):
     eng = StreamingBatch([co, co], t, y, diag=diag)
     eng.generator_period = 1
-    assert eng._pack[7] == block_expected
+    assert eng._pack.stream_block == block_expected
     ll = eng.log_likelihood().cpu().numpy()
     ref, info = cref.loglike(co[:6], t, diag + co[6], y)
     assert info == 0
@@ -44,7 +44,7 @@ def test_fast_term_long_span(fast):
     y = 100.0 * rng.normal(size=N)
     block = 64 if 1.5 * 63 * fast <= 128.0 else (32 if 1.5 * 31 * fast <= 128.0 else 16)
     eng = _check(_coeffs(30, fast=fast), t, y, np.full(N, 900.0), block)
-    assert eng._pack[5] <= 16                 # the other routes keep the short span's block
+    assert eng._pack.block <= 16                 # the other routes keep the short span's block
 
 
 def test_gap_and_jitter_long_span():
@@ -73,4 +73,4 @@ def test_out_of_range_amplitudes_fall_back(scale):
     rng = np.random.Generator(np.random.PCG64(10))
     y = 100.0 * np.sqrt(scale) * rng.normal(size=N)
     eng = _check(_coeffs(30, scale=scale), t, y, np.full(N, 900.0 * scale), 0)
-    assert eng._pack[5] == 16
+    assert eng._pack.block == 16

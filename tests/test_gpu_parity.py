@@ -326,7 +326,7 @@ def test_fused_kernels_take_large_phases(hip):
         co = prob["kernel"].get_device_coefficients()
         eng = StreamingBatch([co], t, prob["y"], diag=prob["diag_user"], tile_rows=512)
         eng.generator_period = 1
-        assert 1.6e6 < eng._pack[6] * eng._tmax < 1e12
+        assert 1.6e6 < eng._pack.dmax * eng._tmax < 1e12
         assert eng._fused_ok() or eng._wide_ok()
         ref, info = cref.loglike(co[:6], t, prob["diag_user"] + co[6], prob["y"])
         ll = float(eng.log_likelihood()[0])

@@ -57,7 +57,7 @@ def test_random_problem(hip, seed):
     while per < 16 and 1.6e-15 * (2 * per) * cond <= 1e-9:
         per *= 2
     eng.generator_period = 1 if seed % 2 == 0 else per
-    tag = (seed, prob["kind"], prob["J"], N, tile, eng._pack[5], eng._fused_ok(), eng.generator_period)
+    tag = (seed, prob["kind"], prob["J"], N, tile, eng._pack.block, eng._fused_ok(), eng.generator_period)
     ll = float(eng.log_likelihood()[0])
     assert int(eng.info[0]) == 0, tag
     assert abs(ll - ref) <= RTOL_LL * abs(ref), (tag, ll, ref)
@@ -65,7 +65,7 @@ def test_random_problem(hip, seed):
     Yd = torch.as_tensor(Y).cuda().reshape(1, N, 3)
     ai_ref = cref.solve_upper(t, c, U, W_ref, cref.solve_lower(t, c, U, W_ref, Y) / d_ref[:, None])
     if eng._fused_ok():
-        L = int(rng.choice([64, 128, 256, 512])) * max(1, eng._pack[5] // 64)
+        L = int(rng.choice([64, 128, 256, 512])) * max(1, eng._pack.block // 64)
         eng.tree_min_chunks = int(rng.choice([2, 1 << 30]))              # tree or sequential combine
         ll_tp = float(eng.log_likelihood_time_parallel(chunk_len=L)[0])
         assert abs(ll_tp - ref) <= RTOL_LL * abs(ref), (tag, L, ll_tp, ref)
@@ -212,14 +212,14 @@ def test_random_problem_at_the_product_period(hip, seed):
     # the streamed sweep's estimate is the oracle's condition; the period is never longer than it allows
     assert abs(cond - cond_ref) <= 1e-6 * cond_ref and per == eng.period_for_condition(cond), (cond, cond_ref)
     assert eng.generator_period == per <= eng.period_for_condition(cond_ref)
-    tag = (seed, prob["kind"], axis, prob["J"], N, tile, eng._pack[5], eng._fused_ok(), per, cond)
+    tag = (seed, prob["kind"], axis, prob["J"], N, tile, eng._pack.block, eng._fused_ok(), per, cond)
     ll = float(eng.log_likelihood()[0])
     assert int(eng.info[0]) == 0 and eng.generator_period == per, tag
     assert abs(ll - ref) <= RTOL_LL * abs(ref), (tag, ll, ref)
     if not eng._fused_ok():
         return
     assert eng.kernel_used == "fused"
-    L = int(rng.choice([64, 128, 256, 512])) * max(1, eng._pack[5] // 64)
+    L = int(rng.choice([64, 128, 256, 512])) * max(1, eng._pack.block // 64)
     for two in (False, True):
         eng.two_sweep = two
         ll_tp = float(eng.log_likelihood_time_parallel(chunk_len=L)[0])

@@ -43,7 +43,7 @@ def test_random_walker_batch(hip, seed):
     dmin, amax = float(dmin.min()), float(amax.max())
     cond = amax / dmin
     per = int(eng.generator_period)
-    tag = (seed, prob["kind"], prob["route"], prob["J"], prob["n_over"], B, N, prob["tile"], eng._pack[5], per, cond)
+    tag = (seed, prob["kind"], prob["route"], prob["J"], prob["n_over"], B, N, prob["tile"], eng._pack.block, per, cond)
     assert eng._tp_used == tp and (tp or eng.kernel_used == "fused"), tag
     if pd0.all():
         cond_ref = float(np.max([m[1].max() for m in orc[0]["mats"]]) / np.min([d.min() for d in orc[0]["d"]]))

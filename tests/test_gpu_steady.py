@@ -114,8 +114,8 @@ def test_scaling_block_below_64(hip):
     assert np.all(info == 0)
     got = ev.evaluate()
     sw = ev.engine.steady_switch_rows()
-    print(f"block {ev.engine._pack[7]}: switch rows {sw.tolist()}, error vs oracle {_rel(got, ref).max():.2e}")
-    assert ev.engine.steady_used and ev.engine._pack[7] == 16
+    print(f"block {ev.engine._pack.stream_block}: switch rows {sw.tolist()}, error vs oracle {_rel(got, ref).max():.2e}")
+    assert ev.engine.steady_used and ev.engine._pack.stream_block == 16
     assert np.all(sw >= 19 * 64 + 1) and np.all((sw - 1) % 64 == 0) and np.all(sw < N - 3 * T), sw.tolist()
     assert _rel(got, ref).max() <= RTOL_LL
     assert ev.steady_reruns == 0

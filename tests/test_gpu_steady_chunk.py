@@ -15,6 +15,7 @@ import pytest
 
 from tests.steady_cases import ANCHOR, ARM, B_FIN, J_ALL, SW, T, _fast_terms, _rel
 from tests.steady_group_cases import J_GROUP, LONGEST_G, N_G, series
+from tests.steady_raw import finish_head
 from tests.test_gpu_steady import _evaluator, _series
 from tests.test_gpu_steady_group import raws  # noqa: F401  (the module fixture of the raw entry points)
 from tests.test_steady_fold_host import FLOOR
@@ -35,16 +36,10 @@ def _chunked(r, N, hdr_, acc_, y=None, y_bs=None, window=(0, I64_MAX), ws=None):
     import torch
     from gadfly_amd import _lib
     eng, lib, p = r["eng"], r["lib"], r["p"]
-    _, comp, _, _, cmax, block, _, stream_block = eng._pack[:8]
-    variant = int(eng.sweep_variant)
-    if stream_block:
-        block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
     if ws is None:
         ws = torch.full((eng.B, int(lib.gf_steady_chunk_size(N, CHUNK_BLOCKS))), float("nan"), **r["f64"])
-    st = lib.gf_steady_finish_chunked(
-        eng.B, N, eng.Jr, eng.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(cmax),
-        p(eng.t), eng._bs(eng.t), p(eng.y if y is None else y), eng._bs(eng.y) if y is None else y_bs,
-        p(eng.info), p(hdr_), p(acc_), int(window[0]), int(window[1]), CHUNK_BLOCKS, p(ws), r["stream"])
+    head = finish_head(eng, N, hdr_, acc_, y=y, y_bs=y_bs)
+    st = lib.gf_steady_finish_chunked(*head, int(window[0]), int(window[1]), CHUNK_BLOCKS, p(ws), r["stream"])
     _lib.check(st, "gf_steady_finish_chunked")
     return ws
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.random_cases import oracle_loglikes
+from tests.steady_raw import finish_head, sweep_head
 from tests.test_gpu_steady import RTOL_LL, _evaluator, _fast_terms, _rel, _series
 from tests.test_steady_host import GRID, LAG, COUNT, _switch_row, _two_terms
 
@@ -82,10 +83,6 @@ def test_raw_entry_points_against_the_per_tile_route(hip):
     ev.auto_generator_period, eng.generator_period = False, 1
     ev.evaluate()                           # (packs the coefficients; its own result is not used)
     lib, p, B = eng.lib, _lib.ptr, eng.B
-    real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-    variant = int(eng.sweep_variant)
-    if stream_block:
-        block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
     stream = torch.cuda.current_stream(eng.device).cuda_stream
     f64 = dict(dtype=torch.float64, device=eng.device)
 
@@ -100,11 +97,7 @@ def test_raw_entry_points_against_the_per_tile_route(hip):
         for k, n0 in enumerate(range(0, N, T)):
             rows = min(T, N - n0)
             sweep = lib.gf_steady_sweep if new else lib.gf_loglike_steady
-            st = sweep(B, rows, n0, eng.Jr, eng.Jc, block, 1, variant,
-                       p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(diag_add), p(cmax),
-                       p(eng.t), eng._bs(eng.t), p(eng.diag), 0 if eng.diag is None else eng._bs(eng.diag),
-                       p(eng.y), eng._bs(eng.y), p(eng.d), p(eng.z), p(eng.S_state), p(eng.F_state), p(eng.info),
-                       p(steady), 0, stream)
+            st = sweep(*sweep_head(eng, rows, n0), p(steady), 0, stream)
             _lib.check(st, "sweep")
             if new:
                 st = lib.gf_reduce_tile_steady(B, rows, n0, p(eng.d), p(eng.z), p(steady), p(eng.work), p(acc),
@@ -113,9 +106,7 @@ def test_raw_entry_points_against_the_per_tile_route(hip):
                 st = lib.gf_reduce_tile(B, rows, p(eng.d), p(eng.z), p(eng.work), p(acc), 1 if k == 0 else 0, stream)
             _lib.check(st, "reduce")
         if new:
-            st = lib.gf_steady_finish(B, N, eng.Jr, eng.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]),
-                                      p(comp[3]), p(cmax), p(eng.t), eng._bs(eng.t), p(eng.y), eng._bs(eng.y),
-                                      p(eng.info), p(steady), p(acc), stream)
+            st = lib.gf_steady_finish(*finish_head(eng, N, steady, acc), stream)
             _lib.check(st, "gf_steady_finish")
         torch.cuda.synchronize()
         assert np.all(eng.info.cpu().numpy() == 0)

@@ -14,6 +14,7 @@ import pytest
 
 from tests.steady_cases import ANCHOR, ARM, B_FIN, RTOL_LL, SW, T, _evaluator, _rel, _run
 from tests.steady_group_cases import J_GROUP, LONGEST_G, N_G, TAILS_G, case
+from tests.steady_raw import finish_head, sweep_head
 from tests.test_gpu_steady_instances import ULP_LOGD, _ulps
 from tests.test_steady_tail_host import RTOL_Z
 
@@ -40,10 +41,6 @@ def raws(hip):
         ev.evaluate()                       # (packs the coefficients; its own result is not used)
         assert eng.B == B_FIN and eng.Jr == 0 and eng.Jc == J and eng.tile_rows == T
         lib, p, B = eng.lib, _lib.ptr, eng.B
-        real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-        variant = int(eng.sweep_variant)
-        if stream_block:
-            block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
         stream = torch.cuda.current_stream(eng.device).cuda_stream
         f64 = dict(dtype=torch.float64, device=eng.device)
         eng.S_state.zero_()
@@ -55,11 +52,7 @@ def raws(hip):
         acc = torch.full((B, 3), float("nan"), **f64)
         for k, n0 in enumerate(range(0, N_G, T)):
             rows = min(T, N_G - n0)
-            st = lib.gf_steady_sweep(B, rows, n0, eng.Jr, eng.Jc, block, 1, variant,
-                                     p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]),
-                                     p(diag_add), p(cmax), p(eng.t), eng._bs(eng.t), p(eng.diag),
-                                     0 if eng.diag is None else eng._bs(eng.diag), p(eng.y), eng._bs(eng.y), p(eng.d),
-                                     p(eng.z), p(eng.S_state), p(eng.F_state), p(eng.info), p(steady), ARM, stream)
+            st = lib.gf_steady_sweep(*sweep_head(eng, rows, n0), p(steady), ARM, stream)
             _lib.check(st, "gf_steady_sweep")
             st = lib.gf_reduce_tile_steady(B, rows, n0, p(eng.d), p(eng.z), p(steady), p(eng.work), p(acc),
                                            1 if k == 0 else 0, stream)
@@ -71,9 +64,7 @@ def raws(hip):
         assert np.all(hdr[:, 2] == 0.0)
 
         def finish(N, hdr_, acc_, y=None, y_bs=None, window=None):
-            head = (B, N, eng.Jr, eng.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(cmax),
-                    p(eng.t), eng._bs(eng.t), p(eng.y if y is None else y), eng._bs(eng.y) if y is None else y_bs,
-                    p(eng.info), p(hdr_), p(acc_))
+            head = finish_head(eng, N, hdr_, acc_, y=y, y_bs=y_bs)
             if window is None:
                 _lib.check(lib.gf_steady_finish(*head, stream), "gf_steady_finish")
             else:

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests.steady_cases import ANCHOR, ARM, B_FIN, J_ALL, LONGEST, N_LONG, RTOL_LL, SW, T, _evaluator, _rel, _run, case
+from tests.steady_raw import finish_head, sweep_head
 from tests.test_steady_tail_host import RTOL_Z
 
 pytestmark = pytest.mark.gpu
@@ -39,10 +40,6 @@ def raws(hip):
         ev.evaluate()                       # (packs the coefficients; its own result is not used)
         assert eng.B == B_FIN and eng.Jr == 0 and eng.Jc == J and eng.tile_rows == T
         lib, p = eng.lib, _lib.ptr
-        real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-        variant = int(eng.sweep_variant)
-        if stream_block:
-            block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
         stream = torch.cuda.current_stream(eng.device).cuda_stream
         f64 = dict(dtype=torch.float64, device=eng.device)
 
@@ -55,17 +52,11 @@ def raws(hip):
             return torch.zeros((eng.B, int(lib.gf_steady_size())), **f64)
 
         def sweep(entry, steady, n0, rows):
-            st = entry(eng.B, rows, n0, eng.Jr, eng.Jc, block, 1, variant,
-                       p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(diag_add), p(cmax),
-                       p(eng.t), eng._bs(eng.t), p(eng.diag), 0 if eng.diag is None else eng._bs(eng.diag),
-                       p(eng.y), eng._bs(eng.y), p(eng.d), p(eng.z), p(eng.S_state), p(eng.F_state), p(eng.info),
-                       p(steady), ARM, stream)
+            st = entry(*sweep_head(eng, rows, n0), p(steady), ARM, stream)
             _lib.check(st, "sweep")
 
         def finish(N, steady, acc):
-            st = lib.gf_steady_finish(eng.B, N, eng.Jr, eng.Jc, block, variant, p(comp[0]), p(comp[1]), p(comp[2]),
-                                      p(comp[3]), p(cmax), p(eng.t), eng._bs(eng.t), p(eng.y), eng._bs(eng.y),
-                                      p(eng.info), p(steady), p(acc), stream)
+            st = lib.gf_steady_finish(*finish_head(eng, N, steady, acc), stream)
             _lib.check(st, "gf_steady_finish")
 
         made[J] = dict(case=c, ev=ev, eng=eng, lib=lib, p=p, f64=f64, stream=stream, start=start, sweep=sweep,

@@ -7,6 +7,7 @@ argument errors."""
 import numpy as np
 import pytest
 
+from tests.steady_raw import finish_head, sweep_head
 from tests.test_gpu_steady import _evaluator, _series
 from tests.test_gpu_steady_finish import N_FIN, T_FIN
 from tests.test_steady_host import _switch_row, _two_terms
@@ -59,10 +60,6 @@ def raw(hip):
     ev.auto_generator_period, eng.generator_period = False, 1
     ev.evaluate()                           # (packs the coefficients; its own result is not used)
     lib, p, B = eng.lib, _lib.ptr, eng.B
-    real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-    variant = int(eng.sweep_variant)
-    if stream_block:
-        block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
     stream = torch.cuda.current_stream(eng.device).cuda_stream
     f64 = dict(dtype=torch.float64, device=eng.device)
     steady0 = torch.zeros((B, int(lib.gf_steady_size())), **f64)
@@ -74,11 +71,7 @@ def raw(hip):
     eng.z.fill_(float("nan"))
     for k, n0 in enumerate(range(0, N, T)):
         rows = min(T, N - n0)
-        st = lib.gf_steady_sweep(B, rows, n0, eng.Jr, eng.Jc, block, 1, variant,
-                                 p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(diag_add),
-                                 p(cmax), p(eng.t), eng._bs(eng.t), p(eng.diag),
-                                 0 if eng.diag is None else eng._bs(eng.diag), p(eng.y), eng._bs(eng.y), p(eng.d),
-                                 p(eng.z), p(eng.S_state), p(eng.F_state), p(eng.info), p(steady0), 0, stream)
+        st = lib.gf_steady_sweep(*sweep_head(eng, rows, n0), p(steady0), 0, stream)
         _lib.check(st, "gf_steady_sweep")
         st = lib.gf_reduce_tile_steady(B, rows, n0, p(eng.d), p(eng.z), p(steady0), p(eng.work), p(acc0),
                                        1 if k == 0 else 0, stream)
@@ -88,10 +81,7 @@ def raw(hip):
     sw = steady0[:, 0].cpu().numpy().astype(np.int64)
 
     def call(buf, acc, window, **over):
-        a = dict(B=B, N=N, Jr=eng.Jr, Jc=eng.Jc, block=block, ac=p(comp[0]), info=p(eng.info), steady=p(buf))
-        a.update(over)
-        head = (a["B"], a["N"], a["Jr"], a["Jc"], a["block"], variant, a["ac"], p(comp[1]), p(comp[2]), p(comp[3]),
-                p(cmax), p(eng.t), eng._bs(eng.t), p(eng.y), eng._bs(eng.y), a["info"], a["steady"], p(acc))
+        head = finish_head(eng, N, buf, acc, **over)
         if window is None:
             return lib.gf_steady_finish(*head, stream)
         return lib.gf_steady_finish_window(*head, int(window[0]), int(window[1]), stream)

@@ -12,6 +12,7 @@ reduced tile and which enters the later ones with info != 0."""
 import numpy as np
 import pytest
 
+from tests.steady_raw import sweep_head
 from tests.test_gpu_steady import _evaluator, _fast_terms, _series
 from tests.test_gpu_steady_finish import N_FIN, T_FIN
 from tests.test_gpu_steady_overlap import _oracle_tiles, _spread_batch
@@ -42,10 +43,6 @@ class _Raw:
     def run(self, tiling, reduced_from, arm_from=0):
         """The tiles (n_first, rows) in order; the one call from tile `reduced_from` on (None: never)."""
         torch, eng, lib, p, B = self.torch, self.eng, self.lib, self.p, self.B
-        real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-        variant = int(eng.sweep_variant)
-        if stream_block:
-            block, variant = stream_block, variant | self._lib.GF_SWEEP_LONG_SPAN
         steady = torch.zeros((B, int(lib.gf_steady_size())), **self.f64)
         acc = torch.full((B, 3), float("nan"), **self.f64)
         d = torch.full((B * self.max_rows,), float("nan"), **self.f64)
@@ -56,11 +53,7 @@ class _Raw:
         eng.info.zero_()
         for k, (n0, rows) in enumerate(tiling):
             assert 0 < rows <= self.max_rows and n0 + rows <= eng.N
-            args = (B, rows, n0, eng.Jr, eng.Jc, block, 1, variant,
-                    p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(diag_add), p(cmax),
-                    p(eng.t), eng._bs(eng.t), p(eng.diag), 0 if eng.diag is None else eng._bs(eng.diag),
-                    p(eng.y), eng._bs(eng.y), p(d), p(z), p(eng.S_state), p(eng.F_state), p(eng.info), p(steady),
-                    arm_from)
+            args = (*sweep_head(eng, rows, n0, d=p(d), z=p(z)), p(steady), arm_from)
             init = 1 if k == 0 else 0
             if reduced_from is not None and k >= reduced_from:
                 self._lib.check(lib.gf_steady_sweep_reduced(*args, p(acc), init, self.stream), "gf_steady_sweep_reduced")
@@ -167,20 +160,14 @@ def test_failing_problem_takes_what_the_reduction_takes(hip):
 def test_argument_errors(spread):
     r, a, _ = spread(3)
     eng, lib, p = r.eng, r.lib, r.p
-    real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-    variant = int(eng.sweep_variant)
-    if stream_block:
-        block, variant = stream_block, variant | r._lib.GF_SWEEP_LONG_SPAN
     acc = r.torch.full((r.B, 3), float("nan"), **r.f64)
     steady = r.torch.zeros((r.B, int(lib.gf_steady_size())), **r.f64)
 
     def call(**over):
         v = dict(steady=p(steady), acc=p(acc), rows=64, n0=0)
         v.update(over)
-        return lib.gf_steady_sweep_reduced(
-            r.B, v["rows"], v["n0"], eng.Jr, eng.Jc, block, 1, variant, p(real[0]), p(real[1]), p(comp[0]), p(comp[1]),
-            p(comp[2]), p(comp[3]), p(diag_add), p(cmax), p(eng.t), eng._bs(eng.t), None, 0, p(eng.y), eng._bs(eng.y),
-            p(eng.d), p(eng.z), p(eng.S_state), p(eng.F_state), p(eng.info), v["steady"], 0, v["acc"], 1, r.stream)
+        head = sweep_head(eng, v["rows"], v["n0"], diag=None, diag_bs=0)
+        return lib.gf_steady_sweep_reduced(*head, v["steady"], 0, v["acc"], 1, r.stream)
 
     for over, text in [(dict(acc=None), "null pointer"), (dict(steady=None), "null pointer"),
                        (dict(rows=0), "empty problem"), (dict(n0=-64), "n_first")]:

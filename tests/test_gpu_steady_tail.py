@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.random_cases import oracle_loglikes
+from tests.steady_raw import sweep_head
 from tests.test_gpu_steady import RTOL_LL, _evaluator, _fast_terms, _rel, _series
 
 pytestmark = pytest.mark.gpu
@@ -54,10 +55,6 @@ def test_raw_entry_point_tile_by_tile(hip):
     ev.auto_generator_period, eng.generator_period = False, 1
     ev.evaluate()                           # (packs the coefficients; its own result is not used)
     lib, p, B = eng.lib, _lib.ptr, eng.B
-    real, comp, diag_add, _, cmax, block, _, stream_block = eng._pack[:8]
-    variant = int(eng.sweep_variant)
-    if stream_block:
-        block, variant = stream_block, variant | _lib.GF_SWEEP_LONG_SPAN
     steady = torch.zeros((B, int(lib.gf_steady_size())), dtype=torch.float64, device=eng.device)
     eng.S_state.zero_()
     eng.F_state.zero_()
@@ -65,12 +62,7 @@ def test_raw_entry_point_tile_by_tile(hip):
     z, d = np.empty((B, N)), np.empty((B, N))
     stream = torch.cuda.current_stream(eng.device).cuda_stream
     for n0 in range(0, N, T):
-        st = lib.gf_loglike_steady(
-            B, T, n0, eng.Jr, eng.Jc, block, 1, variant,
-            p(real[0]), p(real[1]), p(comp[0]), p(comp[1]), p(comp[2]), p(comp[3]), p(diag_add), p(cmax),
-            p(eng.t), eng._bs(eng.t), p(eng.diag), 0 if eng.diag is None else eng._bs(eng.diag),
-            p(eng.y), eng._bs(eng.y), p(eng.d), p(eng.z), p(eng.S_state), p(eng.F_state), p(eng.info),
-            p(steady), 0, stream)
+        st = lib.gf_loglike_steady(*sweep_head(eng, T, n0), p(steady), 0, stream)
         _lib.check(st, "gf_loglike_steady")
         torch.cuda.synchronize()
         z[:, n0:n0 + T] = eng.z.reshape(-1)[:B * T].view(B, T).cpu().numpy()
@@ -104,7 +96,7 @@ def test_one_moved_stamp_raises_the_flag(hip, where):
     t, y = _series(N, seed=31)
     hps = [_fast_terms(2, k0) for k0 in range(3)]
     ev, coeffs = _evaluator(hps, t, y, T)
-    wmax = float(ev.engine._pack[8])
+    wmax = float(ev.engine._pack.wmax)
     t = t.copy()
     t[row] += 10.0 * 2e-6 / wmax
     ev, coeffs = _evaluator(hps, t, y, T)

@@ -31,7 +31,7 @@ for N in (16384, 131072):
                 ll = float(eng.log_likelihood()[0])
                 errs.append(abs(ll - ref) / abs(ref))
             cond = eng.condition_estimate()
-            q = eng._pack[6] * eng._tmax * 2.0 ** -53
-            print(f"J={J} N={N:7d} yerr={yerr:4.0f} off={off:9.3g} phase={eng._pack[6] * eng._tmax:9.3g} cond={cond:9.3g} "
+            q = eng._pack.dmax * eng._tmax * 2.0 ** -53
+            print(f"J={J} N={N:7d} yerr={yerr:4.0f} off={off:9.3g} phase={eng._pack.dmax * eng._tmax:9.3g} cond={cond:9.3g} "
                   f"err p1={errs[0]:.1e} p4={errs[1]:.1e} p64={errs[2]:.1e} | q*cond/sqrtN={q * cond / np.sqrt(N):.1e} "
                   f"q*cond={q * cond:.1e} gen64={1.6e-15 * 64 * cond:.1e}", flush=True)
