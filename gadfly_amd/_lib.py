@@ -72,6 +72,8 @@ SIGNATURES = {
     "gf_reduce_tile_steady": (_int, [_int, _i64, _i64] + [_vp] * 5 + [_int, _vp]),
     "gf_steady_sweep_reduced": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int] + [_vp] * 8
                                 + [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_vp, _i64, _vp, _int] + [_vp]),
+    "gf_steady_sweep_rank1": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _int] + [_vp] * 8
+                              + [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_vp, _i64, _vp, _int, _vp] + [_vp]),
     "gf_steady_finish": (_int, [_int, _i64, _int, _int, _int, _int] + [_vp] * 5 + [_vp, _i64, _vp, _i64]
                          + [_vp] * 3 + [_vp]),
     "gf_steady_finish_window": (_int, [_int, _i64, _int, _int, _int, _int] + [_vp] * 5 + [_vp, _i64, _vp, _i64]

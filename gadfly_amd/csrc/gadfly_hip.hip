@@ -2243,6 +2243,213 @@ k_steady_chunk_sum(const int B, const int64_t N, const int32_t *__restrict__ inf
 }
 
 // ------------------------------------------------------------------------------------
+// k_steady_rank1: the rows IN FRONT of the steady switch in O(W) per row (gf_steady_sweep_rank1).
+//
+// On an axis that is regular from row 0 with a constant diagonal the recurrence, in the frame that rotates with the
+// terms' phasors, is a time-invariant Riccati iteration from S_0 = 0, and S_n+1 - S_n keeps rank one (Chandrasekhar /
+// Morf-Sidhu-Kailath): pivot, gain and forward solve need vectors of one entry per complex term, never the W x W
+// state.  With <p, q> = sum_k Re(conj(p_k) q_k), u0 = a - i b, lambda = exp(-(c + i d) Delta), a0 = the matrix' diagonal:
+//   start  r = 1, d = a0, Y = lambda r, sigma = 1 / d, f = 0;
+//   row n  k = r / d ;  z_n = y_n - <u0, f> ;  f <- lambda (f + k z_n)
+//          beta = <u0, Y> ;  r <- r - sigma beta Y ;  d' = d - sigma beta^2 ;  Y <- lambda (Y - beta k)
+//          sigma <- sigma d / d' ;  d <- d'
+// k is the derotated gain G of the switch rule and of the tail directly, f + k z the tail's state s.  No time stamp
+// enters: no row generator, no block scaling (|lambda| < 1), no resets.  Delta is the cadence of the WHOLE axis (dt[b],
+// from the caller): an error of the cadence is a phase error n w dDelta at row n.
+// One complex term per lane, complex values in register pairs, on BOTH half-waves: lane (h, c) holds r, Y and k of
+// term c, and X = f on the lower half-wave, X = Y on the upper one.  Both updates are X <- lambda (X + k m) with
+// m = z_n below and m = -beta above, and both dot products are <u0, X>: one tree over the half-waves (five DPP steps)
+// gives <u0, f> in lane 31 and beta in lane 63.  1 / d' is formed beside the tree of the next row: the chain from row
+// to row is X -> tree -> X.
+// The contract towards everything downstream is k_factor7<.., STEADY>'s: rows in front of the switch row in d and z,
+// the rule on the same anchors with the same ring (real parts in the lower half-wave's slots, imaginary parts in the
+// upper one's, the pivot in lane 63's: Jc <= 31, so term 31 is a pad), the same header at the switch, info, acc.
+// Between tiles the state lies in the problem's S_state slot (R1_* below), which this route does not otherwise use.
+// ------------------------------------------------------------------------------------
+constexpr int R1_RR = 0, R1_RI = 64, R1_YR = 128, R1_YI = 192, R1_XR = 256, R1_XI = 320;   // [64] per lane
+constexpr int R1_D = 384, R1_SG = 385;                                                    // d, sigma
+
+// sums over the lower and over the upper half-wave, broadcast
+__device__ __forceinline__ void half_wave_sums(double v, double &lo, double &up) {
+    v += dpp_get<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
+    v += dpp_get<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
+    v += dpp_get<0x141, 0xf>(v);   // row_half_mirror
+    v += dpp_get<0x140, 0xf>(v);   // row_mirror       -> every lane holds its 16-lane row sum
+    v += dpp_get<0x142, 0xf>(v);   // row_bcast15: rows 1, 3 += total of rows 0, 2
+    lo = read_lane(v, 31);
+    up = read_lane(v, 63);
+}
+
+__global__ void __launch_bounds__(64, 2)
+k_steady_rank1(const int64_t N, const int64_t n_first, const int Jc, const double gap,
+               const double *__restrict__ ac_, const double *__restrict__ bc_,
+               const double *__restrict__ cc_, const double *__restrict__ dc_,
+               const double *__restrict__ diag_add_, const double *__restrict__ cmax_,
+               const double *__restrict__ t_, const int64_t t_bs,
+               const double *__restrict__ diag_, const int64_t diag_bs,
+               const double *__restrict__ y_, const int64_t y_bs,
+               double *__restrict__ d_, double *__restrict__ z_, double *__restrict__ S_state,
+               int32_t *__restrict__ info, double *__restrict__ steady_, const int64_t arm_from,
+               const double *__restrict__ dt_, double *acc_, const int acc_init) {
+    const int lane = threadIdx.x, pr = blockIdx.x;
+    const int h = lane >> 5, c = lane & 31;         // half-wave (0: X = f, 1: X = Y), term
+    int64_t tile_lim = 0;                           // (acc_: as k_factor7's steady instance leaves, label tile_sums)
+#define R1_EXIT(lim) do { if (acc_) { tile_lim = (lim); goto tile_sums; } return; } while (0)
+  {
+    if (info[pr] != 0) R1_EXIT(steady_rows_stored(steady_, pr, N, n_first));
+    double *__restrict__ hdr = steady_ + (size_t)pr * ST_SIZE;
+    if (hdr[ST_SW] > 0.0) R1_EXIT(steady_rows_stored(steady_, pr, N, n_first));
+    const double *__restrict__ tg = t_ + (size_t)pr * t_bs + n_first;
+    const double *__restrict__ yg = y_ + (size_t)pr * y_bs + n_first;
+    double *__restrict__ dg = d_ + (size_t)pr * N;
+    double *__restrict__ zg = z_ + (size_t)pr * N;
+    double *__restrict__ Sg = S_state + (size_t)pr * (64 * 64);
+    const bool term = c < Jc, fl = lane == 63;
+    const size_t ck = (size_t)pr * Jc + (term ? c : 0);
+    const double ck_c = term ? cc_[ck] : 0.0, ck_d = term ? dc_[ck] : 0.0;
+    const double ck_a = term ? ac_[ck] : 0.0, ck_b = term ? bc_[ck] : 0.0;
+    const double wmax = wave_max(fmax(ck_c, fabs(ck_d)));
+    const double gthr = gap / cmax_[pr], jthr = 2e-6 / wmax;        // the tail's thresholds (RowGen::init's)
+    const double delta = dt_[pr];
+    double lr, li;                                  // lambda, as the tail's set-up forms it
+    {
+        double sn, cs;
+        fm_sincos(ck_d * delta, &sn, &cs);
+        const double e = fm_exp(-ck_c * delta);
+        lr = e * cs;
+        li = -e * sn;
+    }
+    double rr, ri, Yr, Yi, Xr, Xi, d, sg;
+    if (n_first == 0) {                             // from the coefficients (pad terms: r = Y = 0 for good)
+        d = (diag_ ? diag_[(size_t)pr * diag_bs] : 0.0) + diag_add_[pr];     // a0 (diag_add holds the sum of the a_k)
+        sg = fast_rcp(d);
+        rr = term ? 1.0 : 0.0;
+        ri = 0.0;
+        Yr = term ? lr : 0.0;
+        Yi = term ? li : 0.0;
+        Xr = h ? Yr : 0.0;
+        Xi = h ? Yi : 0.0;
+    } else {
+        rr = Sg[R1_RR + lane]; ri = Sg[R1_RI + lane];
+        Yr = Sg[R1_YR + lane]; Yi = Sg[R1_YI + lane];
+        Xr = Sg[R1_XR + lane]; Xi = Sg[R1_XI + lane];
+        d = Sg[R1_D]; sg = Sg[R1_SG];
+    }
+    constexpr double thr = ST_THR;
+    int cnt = __builtin_amdgcn_readfirstlane((int)hdr[ST_CNT]);
+    int fill = __builtin_amdgcn_readfirstlane((int)hdr[ST_FILL]);
+    int32_t fail = 0;
+    double inv = fast_rcp(d);
+    double kr = rr * inv, ki = ri * inv;
+    const int64_t last = N - 1;
+    // The rows in blocks of 64 (local: a tile may start anywhere): t, its predecessor and y of the rows nb + lane come
+    // by one lane-parallel load each, a block ahead; the row takes its y by readlane, and the block's 64 spacings are
+    // tested at once, as the tail tests them (global row 0 has none).  Nothing a row waits for is loaded in the row.
+    auto row_of = [&](const int64_t cb) { const int64_t i = cb + lane; return i < last ? i : last; };
+    double t_nx, tp_nx, y_nx;
+    {
+        const int64_t i = row_of(0);
+        t_nx = tg[i];
+        tp_nx = (n_first + i > 0) ? tg[i - 1] : t_nx - delta;
+        y_nx = yg[i];
+    }
+    const int g0lo = (int)(n_first & (ST_GRID - 1));
+    __builtin_amdgcn_s_setprio(GF_CHAIN_PRIO);
+    for (int64_t nb = 0; nb < N && !fail; nb += 64) {
+        const int lim = (int)(N - nb < 64 ? N - nb : 64);
+        double yv = y_nx;
+        // the block's y has arrived HERE: left to the row loop, its first use puts a vector-memory wait into every row,
+        // and that counter holds the rows' own stores of d and z too
+        asm volatile("" : "+v"(yv));
+        {
+            const double dt = t_nx - tp_nx;
+            const bool bad = (dt > gthr) || !(fabs(dt - delta) < jthr);
+            if (__any(bad) && lane == 0) hdr[ST_VIOL] = 1.0;
+            const int64_t i = row_of(nb + 64);
+            t_nx = tg[i];
+            tp_nx = (n_first + i > 0) ? tg[i - 1] : t_nx - delta;
+            y_nx = yg[i];
+        }
+        for (int j = 0; j < lim; ++j) {
+            const double yy = read_lane(yv, j);
+            double sf, beta;
+            half_wave_sums(fma(ck_a, Xr, -(ck_b * Xi)), sf, beta);      // Re((a + i b) X): <u0, f> below, <u0, Y> above
+            const double zn = yy - sf;
+            if (!(d > 0.0)) {
+                const int64_t gf = n_first + nb + j + 1;
+                fail = (int32_t)(gf > 0x7fffffff ? 0x7fffffff : gf);
+                break;
+            }
+            if (lane == 0) { dg[nb + j] = d; zg[nb + j] = zn; }
+            const double m = h ? -beta : zn;
+            const double sr = fma(kr, m, Xr), si = fma(ki, m, Xi);      // below: s = f + k z, the tail's state
+            if (((g0lo + j) & (ST_GRID - 1)) == 0) {
+                const int64_t n = nb + j, gn = n_first + n;
+                if (gn >= arm_from) {
+                    // an anchor of the rule: k_factor7's test on the same ring
+                    const double x = fl ? d : (h ? ki : kr);
+                    double *__restrict__ slot = hdr + ST_RING + (size_t)((gn / ST_GRID) & (ST_LAG - 1)) * 64 + lane;
+                    const double xo = *slot;
+                    *slot = x;
+                    const double dx = fl ? 0.0 : fabs(x - xo);
+                    const double mdx = wave_max(dx), mx = wave_max(fl ? 0.0 : fabs(x));
+                    const double dold = read_lane(xo, 63);
+                    const bool ok = fill >= ST_LAG && mdx <= thr * mx && fabs(d - dold) <= thr * d;
+                    cnt = ok ? cnt + 1 : 0;
+                    fill = fill < ST_LAG ? fill + 1 : fill;
+                    if (lane == 0) { hdr[ST_CNT] = (double)cnt; hdr[ST_FILL] = (double)fill; }
+                    if (cnt >= ST_COUNT && gn >= ST_DLAG) { // the switch: what k_steady_finish and k_steady_tail start from
+                        if (h == 0) {
+                            hdr[ST_GR + c] = kr;
+                            hdr[ST_GI + c] = ki;
+                            hdr[ST_SR + c] = sr;
+                            hdr[ST_SI + c] = si;
+                        }
+                        if (lane == 0) {
+                            hdr[ST_SW] = (double)(gn + 1);
+                            hdr[ST_D] = d;
+                            hdr[ST_DT] = (tg[n] - tg[n - ST_DLAG]) * (1.0 / ST_DLAG);     // (gn >= 1024)
+                        }
+                        R1_EXIT(n + 1);             // (row n + 1 is the tail's first; rows 0 .. n were stored)
+                    }
+                }
+            }
+            Xr = fma(lr, sr, -(li * si));
+            Xi = fma(lr, si, li * sr);
+            const double sb = sg * beta;
+            rr = fma(-sb, Yr, rr);
+            ri = fma(-sb, Yi, ri);
+            const double dn = fma(-sb, beta, d);
+            const double wr = fma(-beta, kr, Yr), wi = fma(-beta, ki, Yi);      // (k: the old gain)
+            Yr = fma(lr, wr, -(li * wi));
+            Yi = fma(lr, wi, li * wr);
+            inv = fast_rcp(dn);
+            sg = sg * d * inv;
+            d = dn;
+            kr = rr * inv;
+            ki = ri * inv;
+        }
+    }
+    if (fail) {
+        if (lane == 0) info[pr] = fail;
+        R1_EXIT(N);                                 // (not switched: the reduction takes the tile's N rows, stale ones too)
+    }
+    Sg[R1_RR + lane] = rr; Sg[R1_RI + lane] = ri;
+    Sg[R1_YR + lane] = Yr; Sg[R1_YI + lane] = Yi;
+    Sg[R1_XR + lane] = Xr; Sg[R1_XI + lane] = Xi;
+    if (lane == 0) { Sg[R1_D] = d; Sg[R1_SG] = sg; }
+    R1_EXIT(N);                                     // the end of the tile, not switched: all its rows
+  }
+#undef R1_EXIT
+tile_sums:
+    // as k_factor7's steady instance: lane 0's stores of d and z ordered before the wave's loads of them
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    steady_tile_sums(d_ + (size_t)pr * N, z_ + (size_t)pr * N, N, tile_lim, acc_ + (size_t)pr * RED_NACC, acc_init, lane);
+}
+
+// ------------------------------------------------------------------------------------
 // Closed-loop transition sweeps of the time-parallel evaluation, W <= 63 (k_phi7: k_factor7's lane tiling,
 // complex terms only; k_phi: one column per lane, any terms), DESIGN.md 4.3:
 //     Phi <- (I - w~ u~^T) Phi  (E Phi at reset rows),  h_n = Phi^T u~_n,
@@ -6396,6 +6603,34 @@ int gf_steady_sweep_reduced(int B, int64_t N, int64_t n_first, int Jr, int Jc, i
                         diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
                         nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false,
                         acc, init ? 1 : 0);
+}
+
+int gf_steady_sweep_rank1(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                          int gen_period, int variant,
+                          const double *ar, const double *cr, const double *ac,
+                          const double *bc, const double *cc, const double *dc,
+                          const double *diag_add, const double *cmax,
+                          const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                          const double *y, int64_t y_bs,
+                          double *d, double *z, double *S_state, double *F_state,
+                          int32_t *info, double *steady, int64_t arm_from, double *acc, int init,
+                          const double *dt, void *stream) {
+    const char *who = "gf_steady_sweep_rank1";
+    (void)ar; (void)cr; (void)F_state;  // (the arguments of gf_steady_sweep_reduced: no real terms, no forward-solve slot)
+    if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
+    if (block < 1 || block > 64 || (block & (block - 1))) return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
+    if (n_first < 0 || (n_first % block) != 0) return set_err("%s: n_first=%lld must be a non-negative multiple of block=%lld", who, n_first, block);
+    if (!t || !y || !d || !z || !S_state || !info || !diag_add || !cmax || !ac || !bc || !cc || !dc || !steady || !dt)
+        return set_err("%s: null pointer", who);
+    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
+    if (check_sweep_options(who, gen_period, variant & ~(GF_SWEEP_ZERO_START | GF_SWEEP_LONG_SPAN), Jr, Jc)) return -1;
+    if ((variant & GF_SWEEP_ZERO_START) || !sweep_tiled(variant & ~GF_SWEEP_LONG_SPAN, Jr, Jc) || Jc < 1 || arm_from < 0)
+        return set_err("%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%lld)", who, Jc);
+    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
+    hipLaunchKernelGGL(k_steady_rank1, dim3(B), dim3(64), 0, (hipStream_t)stream, N, n_first, Jc, gap, ac, bc, cc, dc,
+                       diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, info, steady, arm_from, dt,
+                       acc, init ? 1 : 0);
+    return check_launch(who);
 }
 
 #define GF_SF_CASE(R) case R: hipLaunchKernelGGL((k_steady_finish<R>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc, sw_lo, sw_hi); break;

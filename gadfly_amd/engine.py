@@ -131,8 +131,8 @@ def sweep_options(pack, sweep_variant):
 
 def sweep_head(pack, B, rows, n_first, Jr, Jc, block, period, variant, t, diag, y, d, z, S_state, F_state, info,
                y_bs=None):
-    """The 27 arguments gf_loglike_fused, gf_loglike_steady, gf_steady_sweep, gf_steady_sweep_reduced and
-    gf_sample_fused share, B ... info, in the order of include/gadfly_hip.h."""
+    """The 27 arguments gf_loglike_fused, gf_loglike_steady, gf_steady_sweep, gf_steady_sweep_reduced,
+    gf_steady_sweep_rank1 and gf_sample_fused share, B ... info, in the order of include/gadfly_hip.h."""
     p = _lib.ptr
     return (B, rows, n_first, Jr, Jc, block, period, variant, *kernel_and_series(pack, t, diag, y, y_bs),
             p(d), p(z), p(S_state), p(F_state), p(info))
@@ -1021,6 +1021,12 @@ class StreamingBatch:
         # behind the split the sweep's own wave adds its tile to acc (gf_steady_sweep_reduced); False: the separate
         # reduction on every tile, for comparisons (the same bits)
         self.steady_sweep_reduces = True
+        # the rows in front of the switch as a rank-one recursion, O(W) per row (gf_steady_sweep_rank1):
+        # on an axis that is regular with a constant diagonal from row 0 (_rank1_ok).  False: the full rows, as before
+        self.steady_rank1 = True
+        self.rank1_used = False             # the last streamed evaluation swept its rows by the recursion
+        self._rank1_dt = None               # [B] cadence of each problem's axis over the whole series: once per evaluator
+        self._rank1_cond = None             # max a / min d of the last steady evaluation whose feedback has arrived
         T = int(min(max(int(tile_rows), 1), self.N))
         if T < self.N:
             T = max(64, T // 64 * 64)         # tiles start on a reset row (any block <= 64)
@@ -1260,7 +1266,7 @@ class StreamingBatch:
         self.info.zero_()
         self._tp_used, self._last_wide_tp = False, False     # (whose `acc` the last evaluation filled)
         self._two_sweep_used = False
-        self.steady_used = False
+        self.steady_used = self.rank1_used = False
         if self._fused_ok() or self._wide_ok():
             return self._log_likelihood_fused(main)
         if self.bufs is None:
@@ -1322,6 +1328,14 @@ class StreamingBatch:
         self.kernel_used = "fused-wide" if self.W > 63 else "fused"
         arm_from = self._steady_arm_from()
         start = None if arm_from is None else self._steady_plan(arm_from)
+        # the rank-one route: every tile from row 0 on, whatever the plan's start row (its feedback still sets the
+        # finishing schedule); an evaluation in which nothing arms runs the recursion to the end
+        self.rank1_used = arm_from is not None and self._rank1_ok(arm_from)
+        if self.rank1_used:
+            start = 0
+            if self._rank1_dt is None:
+                span = (self.t[:, -1] - self.t[:, 0]) / float(max(N - 1, 1))
+                self._rank1_dt = span.expand(B).contiguous()
         self.steady_used = start is not None
         if self.steady_used:
             if self._steady is None:
@@ -1368,7 +1382,11 @@ class StreamingBatch:
             # (gf_steady_sweep_reduced: the additions of gf_reduce_tile_steady, without its 3 B workgroups)
             reduced = steady_tile and split and k > k_e and self.steady_sweep_reduces
             with _timed(torch, self.time_factor, main, self.factor_events, rows):
-                if reduced:
+                if self.rank1_used:
+                    st = lib.gf_steady_sweep_rank1(*args, p(self._steady), 0, p(self.acc) if reduced else None,
+                                                   1 if k == 0 else 0, p(self._rank1_dt), main.cuda_stream)
+                    _lib.check(st, "gf_steady_sweep_rank1")
+                elif reduced:
                     st = lib.gf_steady_sweep_reduced(*args, p(self._steady), arm_from, p(self.acc), 1 if k == 0 else 0,
                                                      main.cuda_stream)
                     _lib.check(st, "gf_steady_sweep_reduced")
@@ -1420,8 +1438,8 @@ class StreamingBatch:
             sw = self._steady[:, 0]
             swi = torch.where(sw > 0.0, sw, torch.full_like(sw, float("inf")))
             fb = torch.stack([swi.min(), torch.kthvalue(swi, B - B // 8).values,
-                              torch.kthvalue(swi, B - B // 64).values, sw.max()])
-            host = torch.zeros((4,), dtype=torch.float64, pin_memory=True)
+                              torch.kthvalue(swi, B - B // 64).values, sw.max(), self._rank1_conditions().max()])
+            host = torch.zeros((5,), dtype=torch.float64, pin_memory=True)
             host.copy_(torch.where(torch.isfinite(fb), fb, torch.zeros_like(fb)), non_blocking=True)
             done = torch.cuda.Event()
             done.record(main)
@@ -1450,7 +1468,9 @@ class StreamingBatch:
         The same feedback sets the split of the overlapped finishing schedule (_steady_split)."""
         fb = self._steady_feedback
         if fb is not None and fb[1].query():
-            (first, most, mid, latest), self._steady_feedback = (int(v) for v in fb[0]), None
+            (first, most, mid, latest), self._steady_feedback = (int(v) for v in fb[0][:4]), None
+            if len(fb[0]) > 4:              # (the condition estimate rides behind the four switch-row figures)
+                self._rank1_cond = float(fb[0][4])
             if first > 0:
                 self._steady_from = max(0, first - self.STEADY_MIN_ROWS - self.tile_rows)
                 self._steady_skip = 0
@@ -1463,6 +1483,36 @@ class StreamingBatch:
             self._steady_skip -= 1
             return None
         return max(arm_from, self._steady_from)
+
+    #: the rank-one route's limits (tests/test_rank1_host.py).  Stamp jitter, in units of 1 / wmax: the
+    #: recursion knows one cadence, and at 1e-7 its log-likelihood was measured within 1.4e-11 of the oracle's.
+    RANK1_JITTER = 1e-7
+    #: max a / min d: r and d of the recursion are running differences, so its error grows with the conditioning;
+    #: 1.5e-12 measured at 1.06e5 (7e-11 at 2.8e6)
+    RANK1_COND_LIMIT = 1e5
+    #: shortest series that takes the route (four default tiles).  The recursion's rows agree with the full rows to
+    #: rounding, not bit for bit, and on short series a problem that never arms stays bit-identical with the plain
+    #: sweep (tests/test_gpu_steady.py pins that at 4096 rows, tests/test_gpu_steady_finish.py at 16 421, in a mixed
+    #: batch); the rows the route saves are those of long series.  (tests/test_gpu_rank1.py lowers it on its engines)
+    RANK1_MIN_ROWS = 32768
+
+    def _rank1_ok(self, arm_from):
+        """The streamed sweep takes the rank-one recursion: an axis that is regular and a diagonal that is constant
+        from row 0 (arm_from = 0), stamp jitter below RANK1_JITTER / wmax, and the last condition estimate that has
+        arrived below RANK1_COND_LIMIT (none yet: the evaluation's own guard decides, steady_violations)."""
+        if not (self.steady_rank1 and arm_from == 0 and self.N >= self.RANK1_MIN_ROWS):
+            return False
+        if not (self._steady_axis_scan()[1] < self.RANK1_JITTER / float(self._pack.wmax)):
+            return False
+        return self._rank1_cond is None or self._rank1_cond < self.RANK1_COND_LIMIT
+
+    def _rank1_conditions(self):
+        """(B,) device tensor: max a / min d per problem of the evaluation whose sums stand in acc (0 for a problem
+        without a positive min pivot: failed, -inf either way)."""
+        torch = self.torch
+        dmin = self.acc[:, 2]
+        amax = self._pack.diag_add if self._diag_amax is None else self._pack.diag_add + self._diag_amax
+        return torch.where(dmin > 0.0, amax / dmin, torch.zeros_like(dmin))
 
     #: rows the steady mode needs behind arm_from to be worth arming: its rule looks back over 16 + 4 anchors
     STEADY_MIN_ROWS = 20 * 64
@@ -1538,8 +1588,14 @@ class StreamingBatch:
     def steady_violations(self):
         """(B,) bool device tensor: problems whose frozen rows met a gap or an off-cadence spacing in the last
         streamed evaluation (their values are invalid: BatchedLogLikelihood.resolve() repeats them); None when
-        the steady mode did not run."""
-        return (self._steady[:, 2] != 0.0) if self.steady_used else None
+        the steady mode did not run.  On the rank-one route also the problems whose own max a / min d exceeded
+        RANK1_COND_LIMIT: repeated in the same way."""
+        if not self.steady_used:
+            return None
+        viol = self._steady[:, 2] != 0.0
+        if self.rank1_used:
+            viol = viol | (self._rank1_conditions() > self.RANK1_COND_LIMIT)
+        return viol
 
     def _fused_refusal(self):
         """Why neither fused sweep takes this batch (None when one does): what a caller that has no slower
@@ -2013,7 +2069,7 @@ class StreamingBatch:
         few long series (B * N large per problem, B small) unless told otherwise."""
         auto = time_parallel is None
         force = getattr(self, "force_streaming", False)
-        self.steady_used = False            # (only the streamed sweep sets it)
+        self.steady_used = self.rank1_used = False      # (only the streamed sweep sets them)
         if auto:
             # chunking costs ~3.5x the flops: it pays while the batch alone fills less than
             # ~1/8 of the 2048 wave slots (``force_streaming``: benchmarks of the streamed sweep)

@@ -280,6 +280,32 @@ int gf_steady_sweep_reduced(int B, int64_t N, int64_t n_first, int Jr, int Jc, i
                             const double *y, int64_t y_bs,
                             double *d, double *z, double *S_state, double *F_state,
                             int32_t *info, double *steady, int64_t arm_from, double *acc, int init, void *stream);
+/*
+ * gf_steady_sweep_rank1 : the rows in front of the switch row in O(W) per row, for an axis that is regular and a
+ *     diagonal that is constant FROM ROW 0 of the series (arm_from = 0 promised for every tile; Jr = 0, Jc <= 31).  In
+ *     the frame that rotates with the phasors the recurrence is then a time-invariant Riccati iteration from a zero
+ *     state whose increments keep rank one: pivot, gain and forward solve from three complex vectors of one entry per
+ *     term (r, Y, f) and two scalars, no W x W state.  The arguments of gf_steady_sweep_reduced and
+ *         dt[B] : the cadence of each problem's axis over the WHOLE series, (t_last - t_first) / (rows - 1) (a local
+ *                 cadence will not do: its error is a phase error that grows with the row).
+ *     The contract is gf_steady_sweep's with acc = NULL and gf_steady_sweep_reduced's with acc: one wave per problem,
+ *     the rows in front of the switch row stored in d and z, the same switch rule on the same anchors with the same
+ *     ring in `steady`, the same slots at the switch (the gf_steady_finish family and gf_loglike_steady's tail read
+ *     them), info[b] = first failing row + 1, problems that failed or had switched left alone.  EVERY tile of the
+ *     evaluation from global row 0 on goes through this entry point: between tiles the state lies in the problem's
+ *     S_state slot (F_state, ar, cr are not read).  Every spacing of a tile's rows is tested as the tail tests it
+ *     (steady[b][2]).  The rows agree with gf_steady_sweep's to rounding, not bit for bit.
+ */
+int gf_steady_sweep_rank1(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
+                          int gen_period, int variant,
+                          const double *ar, const double *cr, const double *ac,
+                          const double *bc, const double *cc, const double *dc,
+                          const double *diag_add, const double *cmax,
+                          const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                          const double *y, int64_t y_bs,
+                          double *d, double *z, double *S_state, double *F_state,
+                          int32_t *info, double *steady, int64_t arm_from, double *acc, int init,
+                          const double *dt, void *stream);
 int gf_steady_finish(int B, int64_t N, int Jr, int Jc, int block, int variant,
                      const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
                      const double *t, int64_t t_bs, const double *y, int64_t y_bs,

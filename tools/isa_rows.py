@@ -7,6 +7,8 @@
     python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: its full row loop, AND
                                                    # k_steady_tail<60>, k_steady_finish<60>: the block loop, per 64-row
                                                    # block and per row
+    python tools/isa_rows.py --asm out.s --rank1   # k_steady_rank1: every block of its row loop
+    python tools/isa_rows.py --asm out.s --compare parent.s    # which kernels' instructions differ between two listings
 
 Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
 most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
@@ -163,8 +165,76 @@ def steady_tail(lines, rows, kernel="k_steady_tail"):
               f"{g['mfma'] / 16:.2f} MFMA, {dyn['lds'] + g['lds'] / 16:.0f} LDS")
 
 
+def functions(lines):
+    """name -> instruction lines of every function of a listing, with the per-function label numbers taken out (a
+    function added in front renumbers the labels of all that follow)."""
+    out, name, body = {}, None, []
+    for ln in lines:
+        if name is None:
+            m = re.match(r"^(_Z\S+):", ln)
+            if m:
+                name, body = m.group(1), []
+        elif ln.startswith(".Lfunc_end"):
+            out[name], name = body, None
+        else:
+            s = ln.split(";")[0].strip()
+            if s and (not s.startswith(".") or s.startswith(".LBB")):     # instructions and block labels
+                body.append(re.sub(r"\.LBB\d+_", ".LBB_", s))
+    return out
+
+
+def compare(lines, other):
+    """Which kernels' instructions differ between two listings (registers included: the operands are compared)."""
+    a, b = functions(lines), functions(other)
+    changed = sorted(k for k in a.keys() & b.keys() if a[k] != b[k])
+    print(f"{len(a)} functions in this listing, {len(b)} in the other; {len(a.keys() & b.keys())} in both, "
+          f"{len(changed)} of them differ")
+    for k in changed:
+        print(f"  differs: {k}")
+    for k in sorted(a.keys() - b.keys()):
+        print(f"  only here: {k} ({len(a[k])} lines)")
+    for k in sorted(b.keys() - a.keys()):
+        print(f"  only in the other: {k}")
+
+
+def rank1(lines):
+    """k_steady_rank1: every block of its row loop (the loop around the block with the half-wave tree: row_bcast:15)."""
+    start = next(i for i, ln in enumerate(lines) if re.match(r"^_Z\S*14k_steady_rank1\S*:", ln))
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    body = lines[start:end]
+    bl = blocks(body)
+    vgpr = next((ln.split(",")[-1].strip() for ln in lines if ".num_vgpr," in ln and "k_steady_rank1" in ln), "?")
+    total = counts([op for b in bl for op in b["ins"]])
+    print(f"k_steady_rank1: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, {total['scratch']} scratch "
+          f"(spill) in all; {vgpr} VGPRs")
+    tree = [i for i, b in enumerate(bl) if b["ins"].count("v_mov_b32_dpp") == 10]    # five steps of one double
+    reg = tree[0]
+    i0, i1 = row_loop_outer(bl, reg)
+    print(f"row loop: blocks {bl[i0]['name']} .. {bl[i1]['name']} (`tree`: the half-wave sums)")
+    print(f"{'block':>14} {'VALU':>5} {'fma':>4} {'dpp':>4} {'SALU':>5} {'br':>3} {'store':>5} {'load':>5}  role")
+    for k in range(i0, i1 + 1):
+        b = bl[k]
+        if not b["ins"]:
+            continue
+        c = counts(b["ins"])
+        fma = sum(op.startswith(("v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64")) for op in b["ins"])
+        print(f"{b['name']:>14} {c['valu']:5d} {fma:4d} {b['ins'].count('v_mov_b32_dpp'):4d} {c['salu']:5d} "
+              f"{c['branch']:3d} {sum(op.startswith('global_store') for op in b['ins']):5d} {c['gload']:5d}  "
+              f"{'tree' if k == reg else ''}")
+
+
+def row_loop_outer(bl, reg):
+    """Largest [header, latch] range closed by a backward branch to the header of the loop that contains `reg`."""
+    idx = {b["name"]: i for i, b in enumerate(bl)}
+    head = max(i for i in range(reg + 1) if any(idx.get(t) == i for j in range(reg, len(bl)) for t in bl[j]["targets"]))
+    latch = max(j for j in range(reg, len(bl)) if any(idx.get(t) == head for t in bl[j]["targets"]))
+    return head, latch
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rank1", action="store_true", help="k_steady_rank1: the blocks of its row loop")
+    ap.add_argument("--compare", help="a second listing: name the kernels whose instructions differ from it")
     ap.add_argument("--asm", help="existing device assembly listing (default: compile gadfly_hip.hip)")
     ap.add_argument("--kernel", default="k_factor7")
     ap.add_argument("--rows", type=int, default=60)
@@ -178,7 +248,13 @@ def main():
         asm = os.path.join(tempfile.mkdtemp(prefix="isa_rows_"), "gadfly_hip.s")
         compile_asm(asm)
     lines = open(asm).read().splitlines()
-    rowstore = (a.rowstore if a.kernel == "k_factor7" else None)
+    if a.compare:
+        compare(lines, open(a.compare).read().splitlines())
+    if a.rank1:
+        rank1(lines)
+    if a.compare or a.rank1:
+        return 0
+    rowstore =(a.rowstore if a.kernel == "k_factor7" else None)
     body = kernel_body(lines, a.kernel, a.rows, rowstore, a.sample, a.steady)
     tag = kernel_tag(a.kernel, a.rows, rowstore, a.sample, a.steady)
     bl = blocks(body)
