@@ -22,7 +22,7 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dens
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
            os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip"),
-           os.path.join(CSRC, "gadfly_lsfft.hip")]
+           os.path.join(CSRC, "gadfly_lsfft.hip"), os.path.join(CSRC, "gadfly_gradtp.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -134,6 +134,10 @@ SIGNATURES = {
     "gf_grad_work": (_i64, [_i64, _int]),
     "gf_loglike_grad": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]
                         + [_vp] * 6 + [_vp]),
+    "gf_grad_chunk_len": (_i64, [_int, _i64, _int]),
+    "gf_grad_chunked_work": (_i64, [_i64, _int, _i64]),
+    "gf_loglike_grad_chunked": (_int, [_int, _i64, _i64, _int, _int] + [_vp] * 7
+                                + [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_vp]),
     "gf_solve_batch_seg": (_i64, [_i64, _int]),
     "gf_solve_batch_work": (_i64, [_i64, _int, _i64]),
     "gf_solve_batch": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_int, _int] + [_vp] * 6

@@ -589,6 +589,59 @@ class GaussianProcess:
             return float(out[0].item())
         return -0.5 * self._do_norm(y, resid=True) - self._norm
 
+    def _sho_parameters(self):
+        """((1, J) arrays S0, w0, Q, delta) of an exposure-integrated sum of SHO terms (every kernel gadfly builds)."""
+        from .terms import SHOTerm, TermConvolution
+        k = self.kernel
+        terms = getattr(k.term, "terms", (k.term,)) if isinstance(k, TermConvolution) else ()
+        if not len(terms) or not all(isinstance(x, SHOTerm) for x in terms) or not k.delta > 0.0:
+            raise NotImplementedError("gradients are implemented for exposure-integrated sums of SHO terms "
+                                      "(TermConvolution over SHOTerm's, e.g. StellarOscillatorKernel)")
+        return tuple(np.array([[getattr(x, n) for x in terms]], dtype=np.float64) for n in ("S0", "w0", "Q")) + (
+            float(k.delta),)
+
+    def value_and_grad(self, y, wrt=("S0", "w0", "Q"), chunk_len=None):
+        """Marginalised log-likelihood of ``y`` and its gradient with respect to the kernel's SHO hyperparameters:
+        ``(value, grads)``, grads a dict holding the names of ``wrt`` -- ``"S0"``, ``"w0"``, ``"Q"`` as (J,) arrays in
+        the order of the kernel's terms, ``"mean"`` (a constant mean) and ``"diag"`` (a constant added to the
+        diagonal) as scalars.  The time axis, diagonal and mean are those of :meth:`compute`, on the device; the
+        series is cut into chunks that are swept concurrently (``chunk_len`` rows each, None: the
+        library's default).  What ``BatchedLogLikelihood([kernel], t, y, ...).value_and_grad(..., time_parallel=True)``
+        returns for its one problem, to the bit.  Celerite widths up to 63 (NotImplementedError beyond)."""
+        from . import grad as _grad
+        from .batch import sho_coefficient_pack
+        if _units.has_unit(y):
+            y = self._flux_to_ppm(y)
+        y = self._process_input(y, require_vector=True)
+        wrt = tuple(wrt)
+        unknown = set(wrt) - {"S0", "w0", "Q", "mean", "diag"}
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        co = self.kernel.get_device_coefficients()
+        _grad.check_width(len(co[0]) + 2 * len(co[2]))
+        S0, w0, Q, delta = self._sho_parameters()
+        torch = _lib.require_device()
+        if self._t_dev is None:
+            self._t_dev = self._to_device(self._t)
+            const = getattr(self, "_diag_const", None)
+            self._diag_dev = (self._to_device(self._diag) if const is None else
+                              torch.full((self._size,), const, dtype=torch.float64, device=self._device_of()))
+        eng = StreamingBatch([co], self._t_dev, self._resid_to_device(y), diag=self._diag_dev, device=self._device,
+                             axis_stats=getattr(self, "_axis_stats", None))
+        Jr, Jc, real, comp, diag_add = sho_coefficient_pack(S0, w0, Q, delta)[:5]
+        res = _grad.coefficient_gradients(eng, Jr, Jc, real, comp, diag_add, chunk_len=chunk_len, time_parallel=True)
+        #: device time, rows per chunk and one-wave re-runs of the last :meth:`value_and_grad`
+        self.last_grad_device_ms, self.last_grad_chunk_len = res["device_ms"], res["chunk_len"]
+        out = {}
+        if {"S0", "w0", "Q"} & set(wrt):
+            g = _grad.parameter_vjp(S0, w0, Q, delta, res["real"], res["comp"], res["diag_add"])
+            out.update({k: v[0] for k, v in zip(("S0", "w0", "Q"), g) if k in wrt})
+        if "mean" in wrt:
+            out["mean"] = float(res["mean"][0])
+        if "diag" in wrt:
+            out["diag"] = float(res["diag_add"][0])
+        return float(res["ll"][0]), out
+
     def apply_inverse(self, y, *, inplace=False):
         """``K^-1 y`` (the mean is not applied)."""
         if _units.has_unit(y):

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .rowcall import GroupedCall, check_pack_batch, group_plan
 
-__all__ = ["sho_coefficient_pack_torch", "check_width", "check_pack_batch", "workspace_plan",
+__all__ = ["sho_coefficient_pack_torch", "check_width", "check_pack_batch", "workspace_plan", "default_chunk_len",
            "coefficient_gradients", "parameter_vjp", "LogLikelihood", "DEFAULT_WORKSPACE_BYTES"]
 
 #: default cap on the gradient workspace of one call (the batch is split into groups beneath it)
@@ -69,28 +69,51 @@ def check_width(W):
             f"has W = {W}")
 
 
-def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES):
-    """(doubles per problem, problems per group, number of groups) of a gradient call."""
+def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, chunk_len=None):
+    """(doubles per problem, problems per group, number of groups) of a gradient call: the one-wave route's, or,
+    with ``chunk_len``, the time-parallel route's at that chunk length."""
     check_width(W)
-    return group_plan(_lib.load().gf_grad_work(int(N), int(W)), B, cap_bytes,
-                      f"no gradient workspace for N = {N}, W = {W}")
+    lib = _lib.load()
+    per = (lib.gf_grad_work(int(N), int(W)) if chunk_len is None
+           else lib.gf_grad_chunked_work(int(N), int(W), int(chunk_len)))
+    return group_plan(per, B, cap_bytes, f"no gradient workspace for N = {N}, W = {W}")
 
 
-def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES):
+def default_chunk_len(B, N, W):
+    """Rows per chunk of the time-parallel route for a batch of B series of N rows (``gf_grad_chunk_len``)."""
+    check_width(W)
+    return int(_lib.load().gf_grad_chunk_len(int(B), int(N), int(W)))
+
+
+def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES,
+                          chunk_len=None, time_parallel=False):
     """Run ``gf_loglike_grad`` over an engine's data (t, y - mean, diag on the device) for stacked host
     coefficient arrays of its ORIGINAL term structure.  Returns a dict of numpy arrays: ``ll`` (B,),
     ``real`` (2, B, Jr) = d/d(a, c), ``comp`` (4, B, Jc) = d/d(a, b, c, d), ``diag_add`` (B,), ``mean`` (B,),
     ``info`` (B,), the plan (``workspace_bytes``, ``groups``, ``group_size``) and ``device_ms``, the summed
-    device time of the gf_loglike_grad launches (HIP events around each)."""
+    device time of the gf_loglike_grad launches (HIP events around each).
+
+    ``time_parallel``: the chunked route (``gf_loglike_grad_chunked``, for one long series or a few) in chunks of
+    ``chunk_len`` rows (None: :func:`default_chunk_len`); the result also holds ``chunk_len`` and ``reruns``, the
+    number of problems it flagged.  Those are run again through ``gf_loglike_grad``, so that log L, info and the NaN
+    gradients of a matrix that is not positive definite are the one-wave route's."""
     W = Jr + 2 * Jc
     if (Jr, Jc) != engine._struct0:
         raise ValueError("coefficient pack does not match the batch structure")
     B, N = engine.B, engine.N
     check_pack_batch(B, Jr, Jc, real, comp, diag_add)
-    plan = workspace_plan(N, W, B, cap_bytes)
+    if not time_parallel and chunk_len is not None:
+        raise ValueError("chunk_len belongs to the time-parallel route (time_parallel=True)")
+    name, head = "gf_loglike_grad", (N,)
+    if time_parallel:
+        chunk_len = default_chunk_len(B, N, W) if chunk_len is None else int(chunk_len)
+        if chunk_len < 1:
+            raise ValueError(f"chunk_len = {chunk_len}")
+        name, head = "gf_loglike_grad_chunked", (N, min(chunk_len, N))
+    plan = workspace_plan(N, W, B, cap_bytes, head[1] if time_parallel else None)
     f64 = dict(dtype=torch.float64, device=engine.device)
     with torch.cuda.device(engine.device):
-        rc = GroupedCall(engine, "gf_loglike_grad", plan, (real, comp, diag_add))
+        rc = GroupedCall(engine, name, plan, (real, comp, diag_add))
         ll = torch.empty((B,), **f64)
         info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
         g_diag = torch.empty((B,), **f64)
@@ -102,15 +125,25 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
         def group(g):
             gr = torch.zeros((2, g.nb, lr), **f64)
             gc = torch.zeros((4, g.nb, lc), **f64)
-            g.launch(g.nb, N, Jr, Jc, *g.coef[0], *g.data, *g.work, g.at(ll), gr.data_ptr(), gc.data_ptr(),
+            g.launch(g.nb, *head, Jr, Jc, *g.coef[0], *g.data, *g.work, g.at(ll), gr.data_ptr(), gc.data_ptr(),
                      g.at(g_diag), g.at(g_mean), g.at(info), g.stream)
             g_real[:, g.b0:g.b0 + g.nb] = gr.cpu().numpy()
             g_comp[:, g.b0:g.b0 + g.nb] = gc.cpu().numpy()
 
-        events = rc.run(group)
+        events = list(rc.run(group))
+        extra = {}
+        if time_parallel:
+            flagged = np.flatnonzero(info.cpu().numpy() != 0)
+            extra = dict(chunk_len=head[1], reruns=len(flagged))
+            if len(flagged):
+                # one problem per group: the one-wave kernel, whose bits do not depend on the batch around a problem
+                per = workspace_plan(N, W, 1, cap_bytes)[0]
+                head = (N,)
+                one = GroupedCall(engine, "gf_loglike_grad", (per, 1, B), (real, comp, diag_add))
+                events += one.run(group, only=flagged)
         return dict(ll=ll.cpu().numpy(), real=g_real[:, :, :Jr], comp=g_comp[:, :, :Jc],
                     diag_add=g_diag.cpu().numpy(), mean=g_mean.cpu().numpy(), info=info.cpu().numpy(),
-                    device_ms=sum(a.elapsed_time(b) for a, b in events), **rc.plan)
+                    device_ms=sum(a.elapsed_time(b) for a, b in events), **rc.plan, **extra)
 
 
 #: terms of each kind (overdamped, underdamped) padded to a multiple of this in the chain rule's layout
@@ -174,14 +207,15 @@ def parameter_vjp(S0, w0, Q, delta, g_real, g_comp, g_diag_add):
 
 
 class LogLikelihood(torch.autograd.Function):
-    """``LogLikelihood.apply(S0, w0, Q, evaluator, delta)``: the (B,) log-likelihoods of a
+    """``LogLikelihood.apply(S0, w0, Q, evaluator, delta[, time_parallel])``: the (B,) log-likelihoods of a
     :class:`gadfly_amd.BatchedLogLikelihood` at (B, J) tensors of SHO hyperparameters, differentiable with
-    respect to S0, w0 and Q (the device gradient of :meth:`BatchedLogLikelihood.value_and_grad`)."""
+    respect to S0, w0 and Q (the device gradient of :meth:`BatchedLogLikelihood.value_and_grad`, by its
+    time-parallel route where ``time_parallel`` is true)."""
 
     @staticmethod
-    def forward(ctx, S0, w0, Q, evaluator, delta):
+    def forward(ctx, S0, w0, Q, evaluator, delta, time_parallel=False):
         host = [x.detach().cpu().numpy() for x in (S0, w0, Q)]
-        ll, g = evaluator.value_and_grad(*host, delta)
+        ll, g = evaluator.value_and_grad(*host, delta, time_parallel=bool(time_parallel))
         ctx.save_for_backward(*(torch.as_tensor(g[k], dtype=S0.dtype, device=S0.device)
                                 for k in ("S0", "w0", "Q")))
         return torch.as_tensor(ll, dtype=S0.dtype, device=S0.device)
@@ -190,4 +224,4 @@ class LogLikelihood(torch.autograd.Function):
     def backward(ctx, grad_output):
         gS0, gw0, gQ = ctx.saved_tensors
         go = grad_output[:, None]
-        return go * gS0, go * gw0, go * gQ, None, None
+        return go * gS0, go * gw0, go * gQ, None, None, None

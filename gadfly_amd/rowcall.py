@@ -119,13 +119,17 @@ class GroupedCall:
         e1.record()
         self.events.append((e0, e1))
 
-    def run(self, call):
-        """``call(self)`` for each group in turn; returns the pairs of HIP events around the launches."""
+    def run(self, call, only=None):
+        """``call(self)`` for each group in turn -- ``only``: for the groups of these indices --; returns the pairs
+        of HIP events around the launches."""
         eng = self.engine
         t, y, dg = eng.t, eng.y, eng.diag
         tbs, ybs = eng._bs(t), eng._bs(y)
         dbs = 0 if dg is None else eng._bs(dg)
+        only = None if only is None else {int(i) for i in only}
         for b0 in range(0, self.B, self.group):
+            if only is not None and b0 // self.group not in only:
+                continue
             self.b0, self.nb = b0, min(self.group, self.B - b0)
             # (the uploaded slices are held until the next group's replace them: the launch is enqueued by then)
             self._held, self.coef = zip(*[self._upload(pk) for pk in self.packs])

@@ -782,6 +782,32 @@ int gf_loglike_grad(int B, int64_t N, int Jr, int Jc,
                     int32_t *info, void *stream);
 
 /*
+ * The same log-likelihoods and gradients, time-parallel: every series is cut into chunks of
+ * chunk_len rows (the last may be shorter; values above N mean N, one chunk) that are swept concurrently, one wave per
+ * (problem, chunk) -- a nominal pass from zero states and gf_chunk_combine[_tree] for the true start state of every chunk, a
+ * forward pass from those, and three reverse sweeps stitched by two scans over the chunks (across a chunk the adjoint
+ * recurrence is affine, its linear part the chunk's closed-loop transition).  For one long series, or a few; many short
+ * ones are gf_loglike_grad's.  W = Jr + 2 Jc <= 63 (-3 beyond).
+ *   gf_grad_chunk_len(B, N, W)   the default chunk length (0 for a shape the call would refuse)
+ *   coefficients, t, diag, y, their strides and every output as gf_loglike_grad, in the same layout
+ *   work: work_bs >= gf_grad_chunked_work(N, W, chunk_len) doubles per problem (chunk maps, start states, the
+ *     checkpoints and one segment's staged rows of every chunk, adjoint sources, partial sums); B * work_bs in all.
+ *     The arrays lie one after the other over the problems of the call, not problem by problem
+ *   a problem with a non-positive pivot in any pass: ll = -inf, every gradient NaN, info > 0 -- the 1-based row of the
+ *     sequential recurrence's first failing pivot whenever the nominal pass was clean.  The other problems are unaffected
+ * No atomics: results are bit-identical from run to run; a problem's bits depend on its own data, N and chunk_len alone.
+ */
+int64_t gf_grad_chunk_len(int B, int64_t N, int W);
+int64_t gf_grad_chunked_work(int64_t N, int W, int64_t chunk_len);
+int gf_loglike_grad_chunked(int B, int64_t N, int64_t chunk_len, int Jr, int Jc,
+                            const double *ar, const double *cr, const double *ac, const double *bc,
+                            const double *cc, const double *dc, const double *diag_add,
+                            const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                            const double *y, int64_t y_bs, double *work, int64_t work_bs,
+                            double *ll, double *g_real, double *g_comp, double *g_diag, double *g_mean,
+                            int32_t *info, void *stream);
+
+/*
  * alpha = K^-1 y and the conditional means of B problems: what celerite2's
  * GaussianProcess.apply_inverse (driver.factor + solve_lower + solve_upper) and predict(y[, kernel=component]) at the
  * observed times (general_matmul_lower + general_matmul_upper at t* = t) give one kernel at a time, on the plain

@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Latency of BatchedLogLikelihood.value_and_grad against evaluate() on the same batch: one JSON line
 per shape, medians of 5 calls -- (a) walkers B = 2048, N = 1e5, J = 30; (b) cfg3-shaped B = 256, N = 65 000, J = 20;
-(c) one star B = 1, N = 1e5, J = 30.  `--shapes a,c` runs a subset, `--reps` sets the count.
+(c) one star B = 1, N = 1e5, J = 30; (d) one star B = 1, N = 1e6, J = 30 (not in the default set: its one-wave leg
+takes about ten seconds a call).  `--shapes a,c` runs a subset, `--reps` sets the count.  `--time-parallel` adds, for
+the shapes b, c and d, the legs of the time-parallel route (value_and_grad(..., time_parallel=True)) in
+the same session: a line with route = "time_parallel" at the default chunk length and, for (c), one per chunk length
+of `--grid` (speedup = the one-wave route's grad_device_ms of this session over the leg's).
 
 grad_device_ms: the gf_loglike_grad launches alone (HIP events around each, summed over the groups);
 grad_api_ms: the whole call as a caller sees it (coefficient pack, launches, copies, the host chain rule);
@@ -20,7 +24,7 @@ import torch  # noqa: E402
 import gadfly_amd  # noqa: E402
 from gadfly_amd.synth import solar_like_hyperparameters, uniform_times  # noqa: E402
 
-SHAPES = {"a": (2048, 100_000, 30), "b": (256, 65_000, 20), "c": (1, 100_000, 30)}
+SHAPES = {"a": (2048, 100_000, 30), "b": (256, 65_000, 20), "c": (1, 100_000, 30), "d": (1, 1_000_000, 30)}
 
 
 def median_ms(fn, reps):
@@ -50,6 +54,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="a,b,c")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--time-parallel", action="store_true")
+    ap.add_argument("--grid", default="64,128,256,512,1024,2048")
     args = ap.parse_args()
     rng = np.random.Generator(np.random.PCG64(2024))
     for name in args.shapes.split(","):
@@ -79,6 +85,28 @@ def main():
                               evaluate_api_ms=round(ev_api, 3), device_ratio=round(gr_dev / ev_dev, 2),
                               api_ratio=round(gr_api / ev_api, 2), workspace_bytes=int(ws), groups=int(groups),
                               group_size=int(group_size), reps=args.reps)), flush=True)
+        if not args.time_parallel or name == "a":
+            continue
+        ll1, g1 = ev.value_and_grad(S0, w0, Q, delta)
+        for L in [None] + ([int(x) for x in args.grid.split(",") if x] if name == "c" else []):
+
+            def run_tp():
+                ev.value_and_grad(S0, w0, Q, delta, time_parallel=True, chunk_len=L)
+                return ev.last_grad_device_ms
+
+            tp_api, tp_dev = median_ms(run_tp, args.reps)
+            ll, g = ev.value_and_grad(S0, w0, Q, delta, time_parallel=True, chunk_len=L)
+            ws, groups, group_size = ev.last_grad_plan
+            scaled = max(float(np.max(np.abs(th * (g[k] - g1[k]))) / max(1.0, float(np.max(np.abs(th * g1[k])))))
+                         for k, th in (("S0", S0), ("w0", w0), ("Q", Q)))
+            print(json.dumps(dict(shape=name, route="time_parallel", B=B, N=N, J=J, W=2 * J,
+                                  chunk_len=int(ev.last_grad_chunk_len), default_chunk_len=L is None,
+                                  chunks=-(-N // int(ev.last_grad_chunk_len)), grad_device_ms=round(tp_dev, 3),
+                                  grad_api_ms=round(tp_api, 2), one_wave_device_ms=round(gr_dev, 2),
+                                  speedup=round(gr_dev / tp_dev, 1), reruns=int(ev.last_grad_reruns),
+                                  ll_rel_vs_one_wave=float(np.max(np.abs(ll - ll1) / np.abs(ll1))),
+                                  grad_scaled_vs_one_wave=scaled, workspace_bytes=int(ws), groups=int(groups),
+                                  group_size=int(group_size), reps=args.reps)), flush=True)
 
 
 if __name__ == "__main__":
