@@ -438,8 +438,11 @@ int gf_scaled_propagator(int B, int64_t N, int W, int ld, const double *c, const
 int gf_chunk_transition_wide(int B, int64_t N, int64_t chunk_len, int nch, int chunk_first, int chunk_count, int Jc,
                              const double *c, const double *de, const double *dbar, const double *rbar,
                              const double *Ut, double *h_out, double *Phi_out, void *stream);
-/* (W = Jr + 2 Jc <= 63, the width of the states: the 64 x 64 slots are zero beyond it, and the combines'
- * pivoted solves and matrix products are carried out on the leading W rows and columns only) */
+/* (W = Jr + 2 Jc, the width of the states, 1 .. 64: the 64 x 64 slots are zero beyond it, and the combines'
+ * pivoted solves and matrix products are carried out on the leading W rows and columns only.  The sweeps and
+ * gf_chunk_corrections stop at W = 63; the combines themselves take the full slot, W = 64, and are tested there
+ * (tests/test_gpu_chunk_combine.py).  Slot 0 of the outputs is zero; the last chunk's Phi, G, m and nominal end
+ * state are never read into a result.) */
 int gf_chunk_combine(int B, int nch, int W, const double *Phi, const double *G, const double *m,
                      double *S_state, double *F_state, void *stream);
 int64_t gf_chunk_combine_tree_work(int B, int P, int nch);

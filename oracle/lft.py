@@ -1,7 +1,10 @@
 """
 TEST INFRASTRUCTURE (oracle): numpy restatement of the chunk-map algebra of the exact time-parallel
 factorisation, used by tests/ to check the library's dense combine
-(gf_lft_tree_scan / gf_wide_combine, gadfly_amd/csrc/gadfly_dense.hip).  Never imported by the product.
+(gf_lft_tree_scan / gf_wide_combine, gadfly_amd/csrc/gadfly_dense.hip) and, as the float64 yardstick beside the 80-bit
+restatement tests/lft_ref.py, the 64 x 64-slot combines gf_chunk_combine / gf_chunk_combine_tree
+(gadfly_amd/csrc/gadfly_hip.hip; tests/test_gpu_chunk_combine.py, whose real maps feed gf_chunk_corrections in
+tests/test_gpu_chunk_corrections.py).  Never imported by the product.
 
 A chunk of rows maps its start state (X, Y) -- X = S + pending rank-1 update of celerite2's `factor`
 recurrence, Y the same for `solve_lower` (celerite2.driver.factor and solve_lower,
