@@ -394,7 +394,13 @@ int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block
  * Same argument conventions (gen_period and variant included: pass the SAME values to all
  * calls of one evaluation) and padding rules as gf_loglike_fused; the row arrays gf_chunk_transition
  * reads (Ut, rbar, dbar, zbar, de) must be readable EIGHT rows past the end (they are fetched ahead by
- * LDS-DMA).  Width 1..63, phases |d t| < 1e12.  gf_chunk_sweep works on the chunks chunk_first ..
+ * LDS-DMA; what those rows hold never reaches a result, NaN included).  Beyond the width gf_chunk_transition
+ * writes: Phi ones on the diagonal W <= j < ROWS = 4 ceil(W / 4) (the sweep carries ROWS state rows from
+ * Phi = I and nothing touches the padding ones) and zeros everywhere else; G and m zeros.  The ones are harmless
+ * to every consumer: the LFT combines work on the leading W x W only, and in the linear combines they multiply
+ * state rows that are zero (tests/test_gpu_chunk_transition.py pins the layout, tests/
+ * test_gpu_chunk_linear_combine.py feeds its maps in it).  A row with dbar <= 0 adds nothing to G, m and
+ * the pending update.  Width 1..63, phases |d t| < 1e12.  gf_chunk_sweep works on the chunks chunk_first ..
  * chunk_first + chunk_count - 1 of every problem (state slots and rows of the others are left alone): the
  * nominal pass leaves out the last chunk, a final pass that stores no factor the first one (whose nominal
  * pass was exact).  A slot whose info entry is non-zero on entry is skipped as well.
@@ -438,7 +444,8 @@ int gf_scaled_propagator(int B, int64_t N, int W, int ld, const double *c, const
 int gf_chunk_transition_wide(int B, int64_t N, int64_t chunk_len, int nch, int chunk_first, int chunk_count, int Jc,
                              const double *c, const double *de, const double *dbar, const double *rbar,
                              const double *Ut, double *h_out, double *Phi_out, void *stream);
-/* (W = Jr + 2 Jc, the width of the states, 1 .. 64: the 64 x 64 slots are zero beyond it, and the combines'
+/* (W = Jr + 2 Jc, the width of the states, 1 .. 64: the 64 x 64 slots are zero beyond it -- but for the padding
+ * ones on Phi's diagonal that gf_chunk_transition leaves, above, which nothing here reads --, and the combines'
  * pivoted solves and matrix products are carried out on the leading W rows and columns only.  The sweeps and
  * gf_chunk_corrections stop at W = 63; the combines themselves take the full slot, W = 64, and are tested there
  * (tests/test_gpu_chunk_combine.py).  Slot 0 of the outputs is zero; the last chunk's Phi, G, m and nominal end
@@ -451,16 +458,32 @@ int gf_chunk_combine_tree(int B, int P, int nch, int W, double *Phi, double *G, 
 
 /*
  * Triangular sweeps on the stored scaled factor, time-parallel (same modes as gf_solve):
- *   gf_chunk_linear(store=0)   local pass: every chunk from a ZERO state (F_state need not be
- *                              initialised), leaves its end state there; nothing else is written.
+ *   gf_chunk_linear(store=0)   local pass: every chunk from a ZERO state, leaves its end state in its
+ *                              F_state slot; nothing else is written (Z is not touched).  The pass
+ *                              reads nothing of F_state, but it WRITES only the state rows
+ *                              i < ROWS = 4 ceil(W / 4) of every slot (R = 1: all 64 rows;
+ *                              GF_MATMUL_LOWER with R >= 16: the rows below 16 ceil(W / 16)), and the
+ *                              solves' combines multiply ALL 64 rows of every slot by the rows of Phi
+ *                              (zeros there, but 0 x NaN = NaN).  So for GF_SOLVE_LOWER / GF_SOLVE_UPPER
+ *                              with R > 1 and W <= 60 the caller ZEROES the rows ROWS .. 63 of every
+ *                              slot (elements [i * R + r], i >= ROWS) before the local pass; everything
+ *                              else of F_state -- and all of it for R = 1, for W > 60 and for
+ *                              GF_MATMUL_LOWER, whose diagonal combine keeps the rows apart -- may hold
+ *                              anything, NaN included (tests/test_gpu_chunk_linear_combine.py,
+ *                              test_f_state_contract).
  *   gf_chunk_linear_combine    F_state slot c <- true start state of chunk c.  GF_SOLVE_LOWER /
  *                              GF_SOLVE_UPPER need Phi [B*nch][64*64], the chunk transitions of the
  *                              TRUE factor (gf_chunk_transition run on the final pass' d, z, r
  *                              rows; the backward sweep uses its transpose); GF_MATMUL_LOWER
  *                              needs c, de and D_work [B*nch][64] instead.
- *   gf_chunk_linear(store=1)   final pass: Z rows.
+ *   gf_chunk_linear(store=1)   final pass: Z rows (every chunk's END state replaces its start state in
+ *                              F_state).
  * Y, Z are [B][N][R] (Z may alias Y); F_state is [B*nch][64*R]; scale != 0 divides the input
- * rows by d (solves) or multiplies them by sqrt(d) (GF_MATMUL_LOWER), as in gf_solve.
+ * rows by d (solves) or multiplies them by sqrt(d) (GF_MATMUL_LOWER), as in gf_solve.  chunk_len is any
+ * length >= 1 with (nch - 1) chunk_len < N <= nch chunk_len; W = 1 .. 63; R >= 1 with no upper limit (the
+ * right-hand sides are swept in tiles of 64, or of 32 / 64 on the matrix pipe: GF_MATMUL_LOWER with R >= 16;
+ * engine.ScaledFactor sends at most 64 at a time, tests/test_gpu_chunk_linear.py runs 65).  The combines take
+ * any R as well; gf_chunk_diag_scan stops at 64.
  */
 int gf_chunk_linear(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int R,
                     int scale, int store, const double *c,
