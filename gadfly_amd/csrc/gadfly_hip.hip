@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <utility>
-#include <tuple>
 #include <type_traits>
 #include <stdint.h>
 #include <stdio.h>
@@ -75,25 +74,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int set_err_impl(const char *fmt, const char *a = "", long long x = 0, long long y = 0) {
-    snprintf(g_err, sizeof(g_err), fmt, a, x, y);
-    return -1;
-}
-
-// conversions in a format literal; set_err() refuses to compile when they do not match the arguments
-// (a missing argument would be read from the defaulted `x` as a char*)
-constexpr int fmt_conversions(const char *f) {
-    int n = 0;
-    for (; *f; ++f)
-        if (*f == '%') { if (f[1] == '%') ++f; else ++n; }
-    return n;
-}
-#define set_err(fmt, ...)                                                                              \
-    (static_cast<void>(sizeof(char[fmt_conversions(fmt) ==                                             \
-                                   (int)std::tuple_size<decltype(std::make_tuple(__VA_ARGS__))>::value \
-                                   ? 1 : -1])),                                                        \
-     set_err_impl(fmt, __VA_ARGS__))
-
 int check_launch(const char *what) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -104,7 +84,7 @@ int check_launch(const char *what) {
 }
 }  // namespace
 
-// the same two services for the library's other translation units (gf_internal.h)
+// what every translation unit of the library reports through, this one included (gf_internal.h)
 int gf_internal_error(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -6250,6 +6230,69 @@ int dispatch_factorw(const FactorWArgs &A, const FactorWPtrs &P, int W, int grid
     return -1;
 }
 
+// Kernels that exist per value of an int template argument: dispatch_among calls f with
+// std::integral_constant<int, V> for the V that equals v, and says whether there was one.
+template <int... V, class F>
+constexpr bool dispatch_among(int v, F &&f) {
+    return ((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
+// the one-wave kernels' row count: the width rounded up to a multiple of 4 (the ladder is written here alone)
+template <class F>
+constexpr bool dispatch_rows(int rows, F &&f) {
+    return dispatch_among<4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64>(rows, f);
+}
+// A wrong instance for a width is a fault on the device, not a failed assertion: every multiple of 4 in 4 .. 64
+// selects the instance of that many rows, and no other count (0, 2 and 68 among them) selects any.
+constexpr bool dispatch_rows_exact() {
+    for (int rows = -4; rows <= 72; ++rows) {
+        int got = -1;
+        dispatch_rows(rows, [&](auto r) { got = decltype(r)::value; });
+        if (got != ((rows >= 4 && rows <= 64 && rows % 4 == 0) ? rows : -1)) return false;
+    }
+    return true;
+}
+static_assert(dispatch_rows_exact(), "dispatch_rows: rows must select the instance R == rows, in 4, 8, .., 64 only");
+
+// Argument checks the entry points share: 0, or -1 with "<who>: ..." recorded.
+int check_block(const char *who, int block) {
+    if (block < 1 || block > 64 || (block & (block - 1)))
+        return gf_internal_error(-1, "%s: block=%d must be a power of two in 1..64", who, block);
+    return 0;
+}
+int check_n_first(const char *who, int64_t n_first, int block) {        // (behind check_block)
+    if (n_first < 0 || (n_first % block) != 0)
+        return gf_internal_error(-1, "%s: n_first=%lld must be a non-negative multiple of block=%d", who,
+                                 (long long)n_first, block);
+    return 0;
+}
+// nch chunks of chunk_len rows cover the N rows, none of them empty; more than one chunk: chunk_len is a multiple
+// of `quantum` (the sweeps: their scaling block; the transitions: 64; 1: any length)
+int check_chunking(const char *who, int64_t N, int64_t chunk_len, int nch, int quantum) {
+    if (nch < 1 || chunk_len < 1 || (nch > 1 && (chunk_len % quantum) != 0) || (int64_t)nch * chunk_len < N
+        || (int64_t)(nch - 1) * chunk_len >= N)
+        return gf_internal_error(-1, "%s: bad chunking (chunk_len=%lld, nch=%d)", who, (long long)chunk_len, nch);
+    return 0;
+}
+int check_chunk_range(const char *who, int chunk_first, int chunk_count, int nch) {
+    if (chunk_first < 0 || chunk_count < 0 || chunk_first + chunk_count > nch)
+        return gf_internal_error(-1, "%s: bad chunk range (first=%d, count=%d)", who, chunk_first, chunk_count);
+    return 0;
+}
+int check_ld(const char *who, int W, int ld) {
+    if (ld < W || (ld & 15))
+        return gf_internal_error(-1, "%s: ld=%d must be a multiple of 16 and >= W=%d", who, ld, W);
+    return 0;
+}
+int check_width_ld(const char *who, int W, int ld) {
+    if (W < 1 || W > GF_MAX_WIDTH)
+        return gf_internal_error(-1, "%s: width %d unsupported (max %d)", who, W, GF_MAX_WIDTH);
+    return check_ld(who, W, ld);
+}
+// the reset gap of a sweep with this scaling block (`variant`: its GF_SWEEP_LONG_SPAN bit)
+double sweep_gap(int block, int variant) {
+    return (block > 1) ? ((variant & GF_SWEEP_LONG_SPAN) ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -6296,19 +6339,18 @@ int gf_build_matrices(int B, int64_t N, int64_t n_first, int Jr, int Jc, int ld,
                       const double *diag, int64_t diag_bs,
                       double *a, double *U, double *V, double *P, void *stream) {
     const int W = Jr + 2 * Jc;
-    if (B < 1 || N < 1) return set_err("gf_build_matrices: empty problem (B=%s%lld, N=%lld)", "", B, N);
-    if (W < 1 || W > GF_MAX_WIDTH) return set_err("gf_build_matrices: width %s%lld unsupported (max %lld)", "", W, GF_MAX_WIDTH);
-    if (ld < W || (ld & 15)) return set_err("gf_build_matrices: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
-    if (!t || !U || !V || (a && !diag_add)) return set_err("gf_build_matrices: null pointer%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_build_matrices: empty problem (B=%d, N=%lld)", B, (long long)N);
+    if (check_width_ld("gf_build_matrices", W, ld)) return -1;
+    if (!t || !U || !V || (a && !diag_add)) return gf_internal_error(-1, "gf_build_matrices: null pointer");
     BuildArgs A;
-    if (n_first < 0) return set_err("gf_build_matrices: negative n_first%s", "");
+    if (n_first < 0) return gf_internal_error(-1, "gf_build_matrices: negative n_first");
     A.N = N; A.n_first = n_first; A.Jr = Jr; A.Jc = Jc; A.ld = ld; A.units = Jr + Jc + (ld - W);
     A.ar = ar; A.cr = cr; A.ac = ac; A.bc = bc; A.cc = cc; A.dc = dc; A.diag_add = diag_add;
     A.t = t; A.t_bs = t_bs; A.diag = diag; A.diag_bs = diag_bs;
     A.a = a; A.U = U; A.V = V; A.P = P;
     const int64_t total = N * A.units;
     const int64_t blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffLL) return set_err("gf_build_matrices: problem too large%s", "");
+    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_build_matrices: problem too large");
     hipLaunchKernelGGL(k_build, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, A);
     return check_launch("gf_build_matrices");
 }
@@ -6335,13 +6377,12 @@ int gf_factor(int B, int64_t N, int64_t n_first, int W, int ld,
               const double *y, int64_t y_bs,
               double *d, double *Wm, double *z,
               double *S_state, double *F_state, int32_t *info, void *stream) {
-    if (B < 1 || N < 1) return set_err("gf_factor: empty problem (B=%s%lld, N=%lld)", "", B, N);
-    if (W < 1 || W > GF_MAX_WIDTH) return set_err("gf_factor: width %s%lld unsupported (max %lld)", "", W, GF_MAX_WIDTH);
-    if (ld < W || (ld & 15)) return set_err("gf_factor: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
-    if (!a || !U || !V || !P || !d || !info) return set_err("gf_factor: null pointer%s", "");
-    if (z && !y) return set_err("gf_factor: z requested without y%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_factor: empty problem (B=%d, N=%lld)", B, (long long)N);
+    if (check_width_ld("gf_factor", W, ld)) return -1;
+    if (!a || !U || !V || !P || !d || !info) return gf_internal_error(-1, "gf_factor: null pointer");
+    if (z && !y) return gf_internal_error(-1, "gf_factor: z requested without y");
     FactorArgs A;
-    if (F_state && !S_state) return set_err("gf_factor: F_state without S_state%s", "");
+    if (F_state && !S_state) return gf_internal_error(-1, "gf_factor: F_state without S_state");
     A.N = N; A.chunk_len = N; A.n_first = n_first; A.W = W; A.ld = ld;
     A.a = a; A.U = U; A.V = V; A.P = P; A.y = y; A.y_bs = y_bs;
     A.d = d; A.Wm = Wm; A.z = z;
@@ -6365,36 +6406,33 @@ int gf_build_scaled(int B, int64_t N, int64_t n_first, int Jr, int Jc, int ld,
                     const double *diag, int64_t diag_bs,
                     double *a, double *Ut, double *Vt, double *de, void *stream) {
     const int W = Jr + 2 * Jc;
-    if (B < 1 || N < 1) return set_err("gf_build_scaled: empty problem (B=%s%lld, N=%lld)", "", B, N);
-    if (!gf_scaled_supported(W) && !gf_scaled_wide_supported(W)) return set_err("gf_build_scaled: width %s%lld unsupported", "", W);
-    if (ld < W || (ld & 15)) return set_err("gf_build_scaled: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
-    if (block < 1 || block > 64 || (block & (block - 1))) return set_err("gf_build_scaled: block=%s%lld must be a power of two in 1..64", "", block);
-    if (n_first < 0 || (n_first % block) != 0) return set_err("gf_build_scaled: n_first=%s%lld must be a non-negative multiple of block=%lld", "", n_first, block);
-    if (!t || !a || !Ut || !Vt || !de || !diag_add || !cmax) return set_err("gf_build_scaled: null pointer%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_build_scaled: empty problem (B=%d, N=%lld)", B, (long long)N);
+    if (!gf_scaled_supported(W) && !gf_scaled_wide_supported(W)) return gf_internal_error(-1, "gf_build_scaled: width %d unsupported", W);
+    if (check_ld("gf_build_scaled", W, ld) || check_block("gf_build_scaled", block)
+        || check_n_first("gf_build_scaled", n_first, block)) return -1;
+    if (!t || !a || !Ut || !Vt || !de || !diag_add || !cmax) return gf_internal_error(-1, "gf_build_scaled: null pointer");
     Build2Args A;
     A.N = N; A.n_first = n_first; A.Jr = Jr; A.Jc = Jc; A.ld = ld; A.units = Jr + Jc + (ld - W);
-    A.block = block; A.gap = (block > 1) ? SC_SPAN / (double)(block - 1) : 0.0;
+    A.block = block; A.gap = sweep_gap(block, GF_SWEEP_AUTO);
     A.ar = ar; A.cr = cr; A.ac = ac; A.bc = bc; A.cc = cc; A.dc = dc; A.diag_add = diag_add; A.cmax = cmax;
     A.t = t; A.t_bs = t_bs; A.diag = diag; A.diag_bs = diag_bs;
     A.a = a; A.Ut = Ut; A.Vt = Vt; A.de = de;
     const int64_t blocks = (N + B2_ROWS - 1) / B2_ROWS;
-    if (blocks > 0x7fffffffLL) return set_err("gf_build_scaled: problem too large%s", "");
+    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_build_scaled: problem too large");
     hipLaunchKernelGGL(k_build2, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, A);
     return check_launch("gf_build_scaled");
 }
-
-#define GF_F2_CASE(R) case R: hipLaunchKernelGGL((k_factor2<R>), dim3(B), dim3(64), 0, st, N, n_first, ld, W, c, a, Ut, Vt, de, y, y_bs, d, z, S_state, F_state, info); break;
 
 int gf_factor_scaled(int B, int64_t N, int64_t n_first, int W, int ld, const double *c,
                      const double *a, const double *Ut, const double *Vt, const double *de,
                      const double *y, int64_t y_bs,
                      double *d, double *z, double *S_state, double *F_state,
                      int32_t *info, void *stream) {
-    if (B < 1 || N < 1) return set_err("gf_factor_scaled: empty problem (B=%s%lld, N=%lld)", "", B, N);
-    if (!gf_scaled_supported(W) && !gf_scaled_wide_supported(W)) return set_err("gf_factor_scaled: width %s%lld unsupported", "", W);
-    if (ld < W || (ld & 15)) return set_err("gf_factor_scaled: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_factor_scaled: empty problem (B=%d, N=%lld)", B, (long long)N);
+    if (!gf_scaled_supported(W) && !gf_scaled_wide_supported(W)) return gf_internal_error(-1, "gf_factor_scaled: width %d unsupported", W);
+    if (check_ld("gf_factor_scaled", W, ld)) return -1;
     if (!c || !a || !Ut || !Vt || !de || !y || !d || !z || !S_state || !F_state || !info)
-        return set_err("gf_factor_scaled: null pointer%s", "");
+        return gf_internal_error(-1, "gf_factor_scaled: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (W > 64) {                       // state: gf_state_size(W) / gf_state_cols(W) doubles per problem
         Factor2wArgs A;
@@ -6403,13 +6441,11 @@ int gf_factor_scaled(int B, int64_t N, int64_t n_first, int W, int ld, const dou
         A.d = d; A.z = z; A.S_state = S_state; A.F_state = F_state; A.info = info;
         return dispatch_factor2w(A, B, st);
     }
-    const int rows = (W + 3) / 4 * 4;
-    switch (rows) {
-        GF_F2_CASE(4) GF_F2_CASE(8) GF_F2_CASE(12) GF_F2_CASE(16) GF_F2_CASE(20) GF_F2_CASE(24)
-        GF_F2_CASE(28) GF_F2_CASE(32) GF_F2_CASE(36) GF_F2_CASE(40) GF_F2_CASE(44) GF_F2_CASE(48)
-        GF_F2_CASE(52) GF_F2_CASE(56) GF_F2_CASE(60) GF_F2_CASE(64)
-        default: return set_err("gf_factor_scaled: internal dispatch error%s", "");
-    }
+    if (!dispatch_rows((W + 3) / 4 * 4, [&](auto r) {
+            hipLaunchKernelGGL((k_factor2<decltype(r)::value>), dim3(B), dim3(64), 0, st, N, n_first, ld, W, c, a, Ut, Vt,
+                               de, y, y_bs, d, z, S_state, F_state, info);
+        }))
+        return gf_internal_error(-1, "gf_factor_scaled: internal dispatch error");
     return check_launch("gf_factor_scaled");
 }
 
@@ -6439,106 +6475,126 @@ static bool sweep_tiled(int variant, int Jr, int Jc) {
     return variant != GF_SWEEP_COLUMN && Jr == 0 && Jc <= 31;
 }
 
-#define GF_F3_ARGS dim3(B * chunk_count), dim3(64), 0, st, N, n_first, chunk_len, nch, chunk_first, chunk_count, Jr, Jc, (block | (gen_period << 8) | zero_start), gap, ar, cr, ac, bc, cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, r_out, Ut_out, Wt_out, de_out, S_state, F_state, info
-#define GF_F7_NOSTEADY (double *)nullptr, (int64_t)0, (double *)nullptr, 0
-#define GF_S3_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_factor7<R, false, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R, true>), GF_F3_ARGS); break;
-#define GF_F3_CASE(R) case R: if (tiled && rowstore) hipLaunchKernelGGL((k_factor7<R, true>), GF_F3_ARGS, GF_F7_NOSTEADY); else if (steady) hipLaunchKernelGGL((k_factor7<R, false, false, true>), GF_F3_ARGS, steady, arm_from, acc, acc_init); else if (tiled) hipLaunchKernelGGL((k_factor7<R, false>), GF_F3_ARGS, GF_F7_NOSTEADY); else hipLaunchKernelGGL((k_factor3<R>), GF_F3_ARGS); break;
-#define GF_ST_CASE(R) case R: hipLaunchKernelGGL((k_steady_tail<R>), dim3(B), dim3(64), 0, st, N, n_first, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, d, z, info, steady); break;
-
 static int check_sweep_options(const char *who, int gen_period, int variant, int Jr, int Jc) {
     if (gen_period < 1 || gen_period > 64 || (gen_period & (gen_period - 1)))
-        return set_err("%s: gen_period=%lld must be a power of two in 1..64", who, gen_period);
+        return gf_internal_error(-1, "%s: gen_period=%d must be a power of two in 1..64", who, gen_period);
     if (variant < GF_SWEEP_AUTO || variant > GF_SWEEP_TILED)
-        return set_err("%s: unknown sweep variant %lld", who, variant);
+        return gf_internal_error(-1, "%s: unknown sweep variant %d", who, variant);
     if (variant == GF_SWEEP_TILED && !(Jr == 0 && Jc <= 31))
-        return set_err("%s: GF_SWEEP_TILED needs complex terms only (Jr = 0) and Jc <= 31 (Jc=%lld)", who, Jc);
+        return gf_internal_error(-1, "%s: GF_SWEEP_TILED needs complex terms only (Jr = 0) and Jc <= 31 (Jc=%d)", who, Jc);
     return 0;
 }
 
-static int fused_launch(const char *who, int B, int64_t N, int64_t n_first, int64_t chunk_len, int nch,
-                        int chunk_first, int chunk_count,
-                        int Jr, int Jc, int block, int gen_period, int variant,
-                        const double *ar, const double *cr, const double *ac,
-                        const double *bc, const double *cc, const double *dc,
-                        const double *diag_add, const double *cmax,
-                        const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
-                        const double *y, int64_t y_bs,
-                        double *d, double *z, double *r_out, double *Ut_out, double *Wt_out,
-                        double *de_out, double *S_state, double *F_state,
-                        int32_t *info, void *stream, bool sample = false,
-                        double *steady = nullptr, int64_t arm_from = 0, bool tail = true,
-                        double *acc = nullptr, int acc_init = 0) {
-    const int W = Jr + 2 * Jc;
-    if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
-    // the sampling sweeps (y = eps, z = the draw by global row with y's batch stride): streamed tiles only
-    if (sample && (nch > 1 || r_out || Ut_out || Wt_out || de_out || (variant & GF_SWEEP_ZERO_START) || (B > 1 && y_bs < 1)))
-        return set_err("%s: one chunk, no row outputs, and a batch stride for eps / out (eps_bs=%lld)", who, y_bs);
+// One call of a fused sweep.  sweep_call() fills what the seven sweep entry points share, their leading arguments;
+// the rest stands for the streamed log-likelihood sweep (one chunk, no rows stored) until an entry point says otherwise.
+struct SweepCall {
+    const char *who;
+    int B, Jr, Jc, block, gen_period, variant;
+    int64_t N, n_first;
+    const double *ar, *cr, *ac, *bc, *cc, *dc, *diag_add, *cmax;        // kernel coefficients
+    const double *t, *diag, *y;                                         // series, with their batch strides
+    int64_t t_bs, diag_bs, y_bs;
+    double *d, *z, *S_state, *F_state;
+    int32_t *info;
+    hipStream_t st;
+    int64_t chunk_len;                                                  // chunks of a time-parallel pass ...
+    int nch = 1, chunk_first = 0, chunk_count = 1;
+    double *r_out = nullptr, *Ut_out = nullptr, *Wt_out = nullptr, *de_out = nullptr;      // ... and the rows it stores
+    bool sample = false;                // y = eps, z = the draw by global row with y's batch stride
+    double *steady = nullptr;           // steady mode: the switch records, armed from row arm_from on
+    int64_t arm_from = 0;
+    bool tail = true;                   // k_steady_tail behind the sweep, for the tile's rows behind the switch row
+    double *acc = nullptr;              // the sweep's own sums (acc_init != 0 overwrites them, 0 accumulates): the
+    int acc_init = 0;                   // steady instance without its tail kernel only
+};
+
+static SweepCall sweep_call(const char *who, int B, int64_t N, int64_t n_first, int Jr, int Jc, int block, int gen_period,
+                            int variant, const double *ar, const double *cr, const double *ac, const double *bc,
+                            const double *cc, const double *dc, const double *diag_add, const double *cmax,
+                            const double *t, int64_t t_bs, const double *diag, int64_t diag_bs, const double *y,
+                            int64_t y_bs, double *d, double *z, double *S_state, double *F_state, int32_t *info,
+                            void *stream) {
+    SweepCall c;
+    c.who = who; c.B = B; c.N = N; c.n_first = n_first; c.Jr = Jr; c.Jc = Jc;
+    c.block = block; c.gen_period = gen_period; c.variant = variant;
+    c.ar = ar; c.cr = cr; c.ac = ac; c.bc = bc; c.cc = cc; c.dc = dc; c.diag_add = diag_add; c.cmax = cmax;
+    c.t = t; c.t_bs = t_bs; c.diag = diag; c.diag_bs = diag_bs; c.y = y; c.y_bs = y_bs;
+    c.d = d; c.z = z; c.S_state = S_state; c.F_state = F_state; c.info = info; c.st = (hipStream_t)stream;
+    c.chunk_len = N;
+    return c;
+}
+
+static int launch_sweep(const SweepCall &c) {
+    const char *who = c.who;
+    const int W = c.Jr + 2 * c.Jc;
+    const bool rowstore = c.r_out || c.Ut_out || c.Wt_out || c.de_out;
+    if (c.B < 1 || c.N < 1) return gf_internal_error(-1, "%s: empty problem (N=%lld)", who, (long long)c.N);
+    // the sampling sweeps: streamed tiles only
+    if (c.sample && (c.nch > 1 || rowstore || (c.variant & GF_SWEEP_ZERO_START) || (c.B > 1 && c.y_bs < 1)))
+        return gf_internal_error(-1, "%s: one chunk, no row outputs, and a batch stride for eps / out (eps_bs=%lld)", who,
+                                 (long long)c.y_bs);
     // (u~ rows / reset spans and the w~ rows are stored independently: a nominal pass needs no w~ rows)
-    if ((Ut_out != nullptr) != (de_out != nullptr) || (Wt_out && !Ut_out))
-        return set_err("%s: Ut_out and de_out go together, Wt_out needs them", who);
-    if (!gf_fused_supported(Jr, Jc))
-        return set_err("%s: width %lld unsupported (1..63 any terms; 64..176 complex terms only)", who, W);
-    if (block < 1 || block > 64 || (block & (block - 1))) return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
-    if (n_first < 0 || (n_first % block) != 0) return set_err("%s: n_first=%lld must be a non-negative multiple of block=%lld", who, n_first, block);
-    if (nch < 1 || chunk_len < 1 || (nch > 1 && (chunk_len % block) != 0) || (int64_t)nch * chunk_len < N
-        || (int64_t)(nch - 1) * chunk_len >= N)
-        return set_err("%s: bad chunking (chunk_len=%lld, nch=%lld)", who, chunk_len, nch);
-    if (chunk_first < 0 || chunk_count < 0 || chunk_first + chunk_count > nch)
-        return set_err("%s: bad chunk range (first=%lld, count=%lld)", who, chunk_first, chunk_count);
-    if (!t || !y || !d || !z || !S_state || (!F_state && W <= 63) || !info || !diag_add || !cmax)
-        return set_err("%s: null pointer", who);
-    const int zero_start = (variant & GF_SWEEP_ZERO_START) ? (1 << 30) : 0;
-    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
-    variant &= ~(GF_SWEEP_ZERO_START | GF_SWEEP_LONG_SPAN);
-    if (long_span && (W > 63 || nch > 1 || r_out || Ut_out || Wt_out || de_out))
-        return set_err("%s: GF_SWEEP_LONG_SPAN is for the streamed one-wave sweep only (W <= 63, one chunk, no row outputs)", who);
-    if (check_sweep_options(who, gen_period, W > 63 ? GF_SWEEP_AUTO : variant, Jr, Jc)) return -1;
-    if (chunk_count == 0) return 0;
-    const bool tiled = sweep_tiled(variant, Jr, Jc);
-    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;
-    hipStream_t st = (hipStream_t)stream;
-    if (steady && (W > 63 || !tiled || r_out || Ut_out || Wt_out || de_out || sample || zero_start || nch > 1 || arm_from < 0))
-        return set_err("%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%lld)", who, Jc);
-    if (acc && (!steady || tail))       // the sweep's own sums: the steady instance without its tail kernel only
-        return set_err("%s: acc goes with the steady sweep alone", who);
+    if ((c.Ut_out != nullptr) != (c.de_out != nullptr) || (c.Wt_out && !c.Ut_out))
+        return gf_internal_error(-1, "%s: Ut_out and de_out go together, Wt_out needs them", who);
+    if (!gf_fused_supported(c.Jr, c.Jc))
+        return gf_internal_error(-1, "%s: width %d unsupported (1..63 any terms; 64..176 complex terms only)", who, W);
+    if (check_block(who, c.block) || check_n_first(who, c.n_first, c.block)
+        || check_chunking(who, c.N, c.chunk_len, c.nch, c.block)
+        || check_chunk_range(who, c.chunk_first, c.chunk_count, c.nch)) return -1;
+    if (!c.t || !c.y || !c.d || !c.z || !c.S_state || (!c.F_state && W <= 63) || !c.info || !c.diag_add || !c.cmax)
+        return gf_internal_error(-1, "%s: null pointer", who);
+    const int zero_start = (c.variant & GF_SWEEP_ZERO_START) ? (1 << 30) : 0;
+    const bool long_span = (c.variant & GF_SWEEP_LONG_SPAN) != 0;
+    const int variant = c.variant & ~(GF_SWEEP_ZERO_START | GF_SWEEP_LONG_SPAN);
+    if (long_span && (W > 63 || c.nch > 1 || rowstore))
+        return gf_internal_error(-1, "%s: GF_SWEEP_LONG_SPAN is for the streamed one-wave sweep only (W <= 63, one chunk, no row outputs)", who);
+    if (check_sweep_options(who, c.gen_period, W > 63 ? GF_SWEEP_AUTO : variant, c.Jr, c.Jc)) return -1;
+    if (c.chunk_count == 0) return 0;
+    const bool tiled = sweep_tiled(variant, c.Jr, c.Jc);
+    const double gap = sweep_gap(c.block, c.variant);
+    const int block_sub = c.block | (c.gen_period << 8) | zero_start;
+    if (c.steady && (W > 63 || !tiled || rowstore || c.sample || zero_start || c.nch > 1 || c.arm_from < 0))
+        return gf_internal_error(-1, "%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%d)", who, c.Jc);
+    if (c.acc && (!c.steady || c.tail))
+        return gf_internal_error(-1, "%s: acc goes with the steady sweep alone", who);
     if (W > 63) {                       // wide kernels: one workgroup per (problem, chunk), k_factorw
         FactorWArgs A;
-        A.N = N; A.n_first = n_first; A.chunk_len = chunk_len; A.nch = nch; A.ch0 = chunk_first; A.nsel = chunk_count; A.Jc = Jc;
-        A.block_sub = block | (gen_period << 8) | zero_start; A.gap = gap;
-        A.t_bs = t_bs; A.diag_bs = diag_bs; A.y_bs = y_bs;
+        A.N = c.N; A.n_first = c.n_first; A.chunk_len = c.chunk_len; A.nch = c.nch; A.ch0 = c.chunk_first;
+        A.nsel = c.chunk_count; A.Jc = c.Jc; A.block_sub = block_sub; A.gap = gap;
+        A.t_bs = c.t_bs; A.diag_bs = c.diag_bs; A.y_bs = c.y_bs;
         FactorWPtrs P;
-        P.ac = ac; P.bc = bc; P.cc = cc; P.dc = dc; P.diag_add = diag_add; P.cmax = cmax;
-        P.t = t; P.diag = diag; P.y = y;
-        P.d = d; P.z = z; P.r_out = r_out; P.Ut_out = Ut_out; P.Wt_out = Wt_out; P.de_out = de_out;
-        P.S_state = S_state; P.info = info;
-        if (dispatch_factorw(A, P, W, B * chunk_count, sample, st)) return set_err("%s: internal dispatch error (wide)", who);
+        P.ac = c.ac; P.bc = c.bc; P.cc = c.cc; P.dc = c.dc; P.diag_add = c.diag_add; P.cmax = c.cmax;
+        P.t = c.t; P.diag = c.diag; P.y = c.y;
+        P.d = c.d; P.z = c.z; P.r_out = c.r_out; P.Ut_out = c.Ut_out; P.Wt_out = c.Wt_out; P.de_out = c.de_out;
+        P.S_state = c.S_state; P.info = c.info;
+        if (dispatch_factorw(A, P, W, c.B * c.chunk_count, c.sample, c.st))
+            return gf_internal_error(-1, "%s: internal dispatch error (wide)", who);
         return check_launch(who);
     }
+    // what every one-wave instance takes; k_factor7 then its four steady-mode arguments
+    auto launch = [&](auto kernel, auto... steady_mode) {
+        hipLaunchKernelGGL(kernel, dim3(c.B * c.chunk_count), dim3(64), 0, c.st, c.N, c.n_first, c.chunk_len, c.nch,
+                           c.chunk_first, c.chunk_count, c.Jr, c.Jc, block_sub, gap, c.ar, c.cr, c.ac, c.bc, c.cc, c.dc,
+                           c.diag_add, c.cmax, c.t, c.t_bs, c.diag, c.diag_bs, c.y, c.y_bs, c.d, c.z, c.r_out,
+                           c.Ut_out, c.Wt_out, c.de_out, c.S_state, c.F_state, c.info, steady_mode...);
+    };
     const int rows = (W + 3) / 4 * 4;
-    const bool rowstore = r_out || Ut_out || Wt_out || de_out;
-    if (sample) {
-        switch (rows) {
-            GF_S3_CASE(4) GF_S3_CASE(8) GF_S3_CASE(12) GF_S3_CASE(16) GF_S3_CASE(20) GF_S3_CASE(24)
-            GF_S3_CASE(28) GF_S3_CASE(32) GF_S3_CASE(36) GF_S3_CASE(40) GF_S3_CASE(44) GF_S3_CASE(48)
-            GF_S3_CASE(52) GF_S3_CASE(56) GF_S3_CASE(60) GF_S3_CASE(64)
-            default: return set_err("%s: internal dispatch error", who);
-        }
-        return check_launch(who);
-    }
-    switch (rows) {
-        GF_F3_CASE(4) GF_F3_CASE(8) GF_F3_CASE(12) GF_F3_CASE(16) GF_F3_CASE(20) GF_F3_CASE(24)
-        GF_F3_CASE(28) GF_F3_CASE(32) GF_F3_CASE(36) GF_F3_CASE(40) GF_F3_CASE(44) GF_F3_CASE(48)
-        GF_F3_CASE(52) GF_F3_CASE(56) GF_F3_CASE(60) GF_F3_CASE(64)
-        default: return set_err("%s: internal dispatch error", who);
-    }
-    if (steady && tail) {               // the rows of this tile behind each problem's switch row (same stream)
+    double *const none = nullptr;
+    if (!dispatch_rows(rows, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            if (c.steady)      launch(k_factor7<R, false, false, true>, c.steady, c.arm_from, c.acc, c.acc_init);
+            else if (!tiled)   c.sample ? launch(k_factor3<R, true>) : launch(k_factor3<R>);
+            else if (c.sample) launch(k_factor7<R, false, true>, none, (int64_t)0, none, 0);
+            else if (rowstore) launch(k_factor7<R, true>, none, (int64_t)0, none, 0);
+            else               launch(k_factor7<R, false>, none, (int64_t)0, none, 0);
+        }))
+        return gf_internal_error(-1, "%s: internal dispatch error", who);
+    if (c.steady && c.tail) {           // the rows of this tile behind each problem's switch row (same stream)
         if (const int e = check_launch(who)) return e;
-        switch (rows) {
-            GF_ST_CASE(4) GF_ST_CASE(8) GF_ST_CASE(12) GF_ST_CASE(16) GF_ST_CASE(20) GF_ST_CASE(24)
-            GF_ST_CASE(28) GF_ST_CASE(32) GF_ST_CASE(36) GF_ST_CASE(40) GF_ST_CASE(44) GF_ST_CASE(48)
-            GF_ST_CASE(52) GF_ST_CASE(56) GF_ST_CASE(60) GF_ST_CASE(64)
-            default: return set_err("%s: internal dispatch error", who);
-        }
+        dispatch_rows(rows, [&](auto r) {
+            hipLaunchKernelGGL((k_steady_tail<decltype(r)::value>), dim3(c.B), dim3(64), 0, c.st, c.N, c.n_first, c.Jc,
+                               gap, c.ac, c.bc, c.cc, c.dc, c.cmax, c.t, c.t_bs, c.y, c.y_bs, c.d, c.z, c.info, c.steady);
+        });
     }
     return check_launch(who);
 }
@@ -6552,9 +6608,9 @@ int gf_loglike_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int bloc
                      const double *y, int64_t y_bs,
                      double *d, double *z, double *S_state, double *F_state,
                      int32_t *info, void *stream) {
-    return fused_launch("gf_loglike_fused", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
-                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
-                        nullptr, nullptr, nullptr, S_state, F_state, info, stream);
+    return launch_sweep(sweep_call("gf_loglike_fused", B, N, n_first, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc,
+                                   cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, F_state,
+                                   info, stream));
 }
 
 int64_t gf_steady_size(void) { return ST_SIZE; }
@@ -6568,10 +6624,11 @@ int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int blo
                       const double *y, int64_t y_bs,
                       double *d, double *z, double *S_state, double *F_state,
                       int32_t *info, double *steady, int64_t arm_from, void *stream) {
-    if (!steady) return set_err("gf_loglike_steady: null pointer%s", "");
-    return fused_launch("gf_loglike_steady", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
-                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
-                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from);
+    if (!steady) return gf_internal_error(-1, "gf_loglike_steady: null pointer");
+    SweepCall c = sweep_call("gf_loglike_steady", B, N, n_first, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                             diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, F_state, info, stream);
+    c.steady = steady; c.arm_from = arm_from;
+    return launch_sweep(c);
 }
 
 int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
@@ -6583,10 +6640,11 @@ int gf_steady_sweep(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block
                     const double *y, int64_t y_bs,
                     double *d, double *z, double *S_state, double *F_state,
                     int32_t *info, double *steady, int64_t arm_from, void *stream) {
-    if (!steady) return set_err("gf_steady_sweep: null pointer%s", "");
-    return fused_launch("gf_steady_sweep", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
-                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
-                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false);
+    if (!steady) return gf_internal_error(-1, "gf_steady_sweep: null pointer");
+    SweepCall c = sweep_call("gf_steady_sweep", B, N, n_first, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                             diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, F_state, info, stream);
+    c.steady = steady; c.arm_from = arm_from; c.tail = false;
+    return launch_sweep(c);
 }
 
 int gf_steady_sweep_reduced(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
@@ -6598,11 +6656,11 @@ int gf_steady_sweep_reduced(int B, int64_t N, int64_t n_first, int Jr, int Jc, i
                             const double *y, int64_t y_bs,
                             double *d, double *z, double *S_state, double *F_state,
                             int32_t *info, double *steady, int64_t arm_from, double *acc, int init, void *stream) {
-    if (!steady || !acc) return set_err("gf_steady_sweep_reduced: null pointer%s", "");
-    return fused_launch("gf_steady_sweep_reduced", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
-                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, nullptr,
-                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, false, steady, arm_from, false,
-                        acc, init ? 1 : 0);
+    if (!steady || !acc) return gf_internal_error(-1, "gf_steady_sweep_reduced: null pointer");
+    SweepCall c = sweep_call("gf_steady_sweep_reduced", B, N, n_first, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc,
+                             cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, F_state, info, stream);
+    c.steady = steady; c.arm_from = arm_from; c.tail = false; c.acc = acc; c.acc_init = init ? 1 : 0;
+    return launch_sweep(c);
 }
 
 int gf_steady_sweep_rank1(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block,
@@ -6615,50 +6673,54 @@ int gf_steady_sweep_rank1(int B, int64_t N, int64_t n_first, int Jr, int Jc, int
                           double *d, double *z, double *S_state, double *F_state,
                           int32_t *info, double *steady, int64_t arm_from, double *acc, int init,
                           const double *dt, void *stream) {
-    const char *who = "gf_steady_sweep_rank1";
-    (void)ar; (void)cr; (void)F_state;  // (the arguments of gf_steady_sweep_reduced: no real terms, no forward-solve slot)
-    if (B < 1 || N < 1) return set_err("%s: empty problem (N=%lld)", who, N);
-    if (block < 1 || block > 64 || (block & (block - 1))) return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
-    if (n_first < 0 || (n_first % block) != 0) return set_err("%s: n_first=%lld must be a non-negative multiple of block=%lld", who, n_first, block);
+    // (the arguments of gf_steady_sweep_reduced: no real terms, no forward-solve slot -- ar, cr, F_state are not read)
+    const SweepCall c = sweep_call("gf_steady_sweep_rank1", B, N, n_first, Jr, Jc, block, gen_period, variant, ar, cr, ac,
+                                   bc, cc, dc, diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, F_state,
+                                   info, stream);
+    const char *who = c.who;
+    if (B < 1 || N < 1) return gf_internal_error(-1, "%s: empty problem (N=%lld)", who, (long long)N);
+    if (check_block(who, block) || check_n_first(who, n_first, block)) return -1;
     if (!t || !y || !d || !z || !S_state || !info || !diag_add || !cmax || !ac || !bc || !cc || !dc || !steady || !dt)
-        return set_err("%s: null pointer", who);
-    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
+        return gf_internal_error(-1, "%s: null pointer", who);
     if (check_sweep_options(who, gen_period, variant & ~(GF_SWEEP_ZERO_START | GF_SWEEP_LONG_SPAN), Jr, Jc)) return -1;
     if ((variant & GF_SWEEP_ZERO_START) || !sweep_tiled(variant & ~GF_SWEEP_LONG_SPAN, Jr, Jc) || Jc < 1 || arm_from < 0)
-        return set_err("%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%lld)", who, Jc);
-    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
-    hipLaunchKernelGGL(k_steady_rank1, dim3(B), dim3(64), 0, (hipStream_t)stream, N, n_first, Jc, gap, ac, bc, cc, dc,
-                       diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, info, steady, arm_from, dt,
-                       acc, init ? 1 : 0);
+        return gf_internal_error(-1, "%s: steady mode is for the streamed lane-tiled sweep only (Jr = 0, Jc <= 31; Jc=%d)", who, Jc);
+    hipLaunchKernelGGL(k_steady_rank1, dim3(c.B), dim3(64), 0, c.st, c.N, c.n_first, c.Jc, sweep_gap(block, variant),
+                       c.ac, c.bc, c.cc, c.dc, c.diag_add, c.cmax, c.t, c.t_bs, c.diag, c.diag_bs, c.y, c.y_bs, c.d, c.z,
+                       c.S_state, c.info, steady, arm_from, dt, acc, init ? 1 : 0);
     return check_launch(who);
 }
 
-#define GF_SF_CASE(R) case R: hipLaunchKernelGGL((k_steady_finish<R>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc, sw_lo, sw_hi); break;
+// what the finishing launches check first, and their window of switch rows
+static int check_finish(const char *who, int B, int64_t N, int Jr, int Jc, int block) {
+    if (B < 1 || N < 1) return gf_internal_error(-1, "%s: empty problem (B=%d, N=%lld)", who, B, (long long)N);
+    if (Jr != 0 || Jc < 1 || Jc > 31)
+        return gf_internal_error(-1, "%s: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%d, Jc=%d)", who, Jr, Jc);
+    return check_block(who, block);
+}
+static int check_window(const char *who, int64_t sw_lo, int64_t sw_hi) {
+    if (sw_lo < 0 || sw_hi < sw_lo)
+        return gf_internal_error(-1, "%s: the window of switch rows needs 0 <= sw_lo <= sw_hi (sw_lo=%lld, sw_hi=%lld)", who,
+                                 (long long)sw_lo, (long long)sw_hi);
+    return 0;
+}
 
 static int steady_finish_launch(const char *who, int B, int64_t N, int Jr, int Jc, int block, int variant,
                                 const double *ac, const double *bc, const double *cc, const double *dc,
                                 const double *cmax, const double *t, int64_t t_bs, const double *y, int64_t y_bs,
                                 const int32_t *info, double *steady, double *acc, int64_t sw_lo, int64_t sw_hi,
                                 void *stream) {
-    if (B < 1 || N < 1) return set_err("%s: empty problem (B=%lld, N=%lld)", who, B, N);
-    if (Jr != 0 || Jc < 1 || Jc > 31)
-        return set_err("%s: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%lld, Jc=%lld)", who, Jr, Jc);
-    if (block < 1 || block > 64 || (block & (block - 1)))
-        return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
+    if (check_finish(who, B, N, Jr, Jc, block)) return -1;
     if (!ac || !bc || !cc || !dc || !cmax || !t || !y || !info || !steady || !acc)
-        return set_err("%s: null pointer", who);
-    if (sw_lo < 0 || sw_hi < sw_lo)
-        return set_err("%s: the window of switch rows needs 0 <= sw_lo <= sw_hi (sw_lo=%lld, sw_hi=%lld)", who, sw_lo, sw_hi);
+        return gf_internal_error(-1, "%s: null pointer", who);
+    if (check_window(who, sw_lo, sw_hi)) return -1;
     if (sw_lo == sw_hi) return 0;       // an empty window: no launch
-    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
-    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
-    hipStream_t st = (hipStream_t)stream;
-    switch ((2 * Jc + 3) / 4 * 4) {
-        GF_SF_CASE(4) GF_SF_CASE(8) GF_SF_CASE(12) GF_SF_CASE(16) GF_SF_CASE(20) GF_SF_CASE(24)
-        GF_SF_CASE(28) GF_SF_CASE(32) GF_SF_CASE(36) GF_SF_CASE(40) GF_SF_CASE(44) GF_SF_CASE(48)
-        GF_SF_CASE(52) GF_SF_CASE(56) GF_SF_CASE(60) GF_SF_CASE(64)
-        default: return set_err("%s: internal dispatch error", who);
-    }
+    const double gap = sweep_gap(block, variant);   // the sweep's
+    if (!dispatch_rows((2 * Jc + 3) / 4 * 4, [&](auto r) {
+            hipLaunchKernelGGL((k_steady_finish<decltype(r)::value>), dim3(B), dim3(64), 0, (hipStream_t)stream, N, Jc, gap,
+                               ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc, sw_lo, sw_hi);
+        }))
+        return gf_internal_error(-1, "%s: internal dispatch error", who);
     return check_launch(who);
 }
 
@@ -6685,46 +6747,41 @@ int64_t gf_steady_chunk_size(int64_t N, int chunk_blocks) {
     return CH_P + (N + chunk_rows - 1) / chunk_rows * CH_SLOT;
 }
 
-#define GF_SC_CASE(R) case R: \
-    hipLaunchKernelGGL((k_steady_chunk<R, 3>), dim3(B), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld); \
-    hipLaunchKernelGGL((k_steady_chunk<R, 1>), dim3(B, nmax), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld); \
-    hipLaunchKernelGGL(k_steady_chunk_power, dim3(B), dim3(256), 0, st, N, info, steady, sw_lo, sw_hi, chunk_rows, squarings, chunk_ws, ws_ld); \
-    hipLaunchKernelGGL((k_steady_chunk<R, 2>), dim3(B, nmax), dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld); \
-    break;
-
 int gf_steady_finish_chunked(int B, int64_t N, int Jr, int Jc, int block, int variant,
                              const double *ac, const double *bc, const double *cc, const double *dc, const double *cmax,
                              const double *t, int64_t t_bs, const double *y, int64_t y_bs,
                              const int32_t *info, double *steady, double *acc,
                              int64_t sw_lo, int64_t sw_hi, int chunk_blocks, double *chunk_ws, void *stream) {
     const char *who = "gf_steady_finish_chunked";
-    if (B < 1 || N < 1) return set_err("%s: empty problem (B=%lld, N=%lld)", who, B, N);
-    if (Jr != 0 || Jc < 1 || Jc > 31)
-        return set_err("%s: steady mode is for the lane-tiled sweep only (Jr = 0, Jc <= 31; Jr=%lld, Jc=%lld)", who, Jr, Jc);
-    if (block < 1 || block > 64 || (block & (block - 1)))
-        return set_err("%s: block=%lld must be a power of two in 1..64", who, block);
+    if (check_finish(who, B, N, Jr, Jc, block)) return -1;
     if (!ac || !bc || !cc || !dc || !cmax || !t || !y || !info || !steady || !acc || !chunk_ws)
-        return set_err("%s: null pointer", who);
-    if (sw_lo < 0 || sw_hi < sw_lo)
-        return set_err("%s: the window of switch rows needs 0 <= sw_lo <= sw_hi (sw_lo=%lld, sw_hi=%lld)", who, sw_lo, sw_hi);
+        return gf_internal_error(-1, "%s: null pointer", who);
+    if (check_window(who, sw_lo, sw_hi)) return -1;
     if (chunk_blocks < 16 || (chunk_blocks & (chunk_blocks - 1)))
-        return set_err("%s: chunk_blocks=%lld must be a power of two >= 16 (chunks start on the groups' grid)", who, chunk_blocks);
+        return gf_internal_error(-1, "%s: chunk_blocks=%d must be a power of two >= 16 (chunks start on the groups' grid)", who, chunk_blocks);
     if (sw_lo == sw_hi) return 0;       // an empty window: no launch
-    const bool long_span = (variant & GF_SWEEP_LONG_SPAN) != 0;
-    const double gap = (block > 1) ? (long_span ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;   // the sweep's
+    const double gap = sweep_gap(block, variant);   // the sweep's
     const int64_t chunk_rows = 64 * (int64_t)chunk_blocks, ws_ld = gf_steady_chunk_size(N, chunk_blocks);
     const int64_t nmax64 = (N + chunk_rows - 1) / chunk_rows;
-    if (nmax64 > 65535) return set_err("%s: %lld chunks per problem are more than a launch takes", who, nmax64);
+    if (nmax64 > 65535)
+        return gf_internal_error(-1, "%s: %lld chunks per problem are more than a launch takes", who, (long long)nmax64);
     const int nmax = (int)nmax64;
     int squarings = 0;
     while ((1 << squarings) < chunk_blocks) ++squarings;
     hipStream_t st = (hipStream_t)stream;
-    switch ((2 * Jc + 3) / 4 * 4) {
-        GF_SC_CASE(4) GF_SC_CASE(8) GF_SC_CASE(12) GF_SC_CASE(16) GF_SC_CASE(20) GF_SC_CASE(24)
-        GF_SC_CASE(28) GF_SC_CASE(32) GF_SC_CASE(36) GF_SC_CASE(40) GF_SC_CASE(44) GF_SC_CASE(48)
-        GF_SC_CASE(52) GF_SC_CASE(56) GF_SC_CASE(60) GF_SC_CASE(64)
-        default: return set_err("%s: internal dispatch error", who);
-    }
+    if (!dispatch_rows((2 * Jc + 3) / 4 * 4, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            auto pass = [&](auto kernel, dim3 grid) {
+                hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info,
+                                   steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld);
+            };
+            pass(k_steady_chunk<R, 3>, dim3(B));
+            pass(k_steady_chunk<R, 1>, dim3(B, nmax));
+            hipLaunchKernelGGL(k_steady_chunk_power, dim3(B), dim3(256), 0, st, N, info, steady, sw_lo, sw_hi, chunk_rows,
+                               squarings, chunk_ws, ws_ld);
+            pass(k_steady_chunk<R, 2>, dim3(B, nmax));
+        }))
+        return gf_internal_error(-1, "%s: internal dispatch error", who);
     hipLaunchKernelGGL(k_steady_chunk_sum, dim3((B + 63) / 64), dim3(64), 0, st, B, N, info, steady, sw_lo, sw_hi,
                        chunk_rows, chunk_ws, ws_ld, acc);
     return check_launch(who);
@@ -6739,9 +6796,10 @@ int gf_sample_fused(int B, int64_t N, int64_t n_first, int Jr, int Jc, int block
                     const double *eps, int64_t eps_bs,
                     double *d, double *out, double *S_state, double *F_state,
                     int32_t *info, void *stream) {
-    return fused_launch("gf_sample_fused", B, N, n_first, N, 1, 0, 1, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
-                        diag_add, cmax, t, t_bs, diag, diag_bs, eps, eps_bs, d, out, nullptr,
-                        nullptr, nullptr, nullptr, S_state, F_state, info, stream, true);
+    SweepCall c = sweep_call("gf_sample_fused", B, N, n_first, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                             diag_add, cmax, t, t_bs, diag, diag_bs, eps, eps_bs, d, out, S_state, F_state, info, stream);
+    c.sample = true;
+    return launch_sweep(c);
 }
 
 int gf_chunk_sweep(int B, int64_t N, int64_t chunk_len, int nch, int chunk_first, int chunk_count,
@@ -6754,48 +6812,37 @@ int gf_chunk_sweep(int B, int64_t N, int64_t chunk_len, int nch, int chunk_first
                    double *d, double *z, double *r_out, double *Ut_out, double *Wt_out,
                    double *de_out, double *S_state, double *F_state,
                    int32_t *info, void *stream) {
-    return fused_launch("gf_chunk_sweep", B, N, 0, chunk_len, nch, chunk_first, chunk_count, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
-                        diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, r_out,
-                        Ut_out, Wt_out, de_out, S_state, F_state, info, stream);
+    SweepCall c = sweep_call("gf_chunk_sweep", B, N, 0, Jr, Jc, block, gen_period, variant, ar, cr, ac, bc, cc, dc,
+                             diag_add, cmax, t, t_bs, diag, diag_bs, y, y_bs, d, z, S_state, F_state, info, stream);
+    c.chunk_len = chunk_len; c.nch = nch; c.chunk_first = chunk_first; c.chunk_count = chunk_count;
+    c.r_out = r_out; c.Ut_out = Ut_out; c.Wt_out = Wt_out; c.de_out = de_out;
+    return launch_sweep(c);
 }
-
-#define GF_PHI_ARGS dim3(B * chunk_count), dim3(64), 0, st, N, chunk_len, nch, chunk_first, chunk_count, W, c, de, dbar, zbar, rbar, Ut, Phi_out, G_out, m_out
-#define GF_PHI_CASE(R) case R: if (tiled) hipLaunchKernelGGL((k_phi7<R>), GF_PHI_ARGS); else hipLaunchKernelGGL((k_phi<R>), GF_PHI_ARGS); break;
 
 int gf_chunk_transition(int B, int64_t N, int64_t chunk_len, int nch, int chunk_first, int chunk_count,
                         int Jr, int Jc, int variant, const double *c, const double *de, const double *dbar,
                         const double *zbar, const double *rbar, const double *Ut,
                         double *Phi_out, double *G_out, double *m_out, void *stream) {
+    const char *who = "gf_chunk_transition";
     const int W = Jr + 2 * Jc;
-    if (B < 1 || N < 1) return set_err("gf_chunk_transition: empty problem (N=%s%lld)", "", N);
-    if (W < 1 || W > 63) return set_err("gf_chunk_transition: width %s%lld unsupported (1..63)", "", W);
-    if (nch < 1 || chunk_len < 1 || (nch > 1 && (chunk_len % 64) != 0) || (int64_t)nch * chunk_len < N
-        || (int64_t)(nch - 1) * chunk_len >= N)
-        return set_err("gf_chunk_transition: bad chunking (chunk_len=%s%lld, nch=%lld)", "", chunk_len, nch);
-    if (chunk_first < 0 || chunk_count < 0 || chunk_first + chunk_count > nch)
-        return set_err("gf_chunk_transition: bad chunk range (first=%s%lld, count=%lld)", "", chunk_first, chunk_count);
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_chunk_transition: empty problem (N=%lld)", (long long)N);
+    if (W < 1 || W > 63) return gf_internal_error(-1, "gf_chunk_transition: width %d unsupported (1..63)", W);
+    if (check_chunking(who, N, chunk_len, nch, 64) || check_chunk_range(who, chunk_first, chunk_count, nch)) return -1;
     if (!c || !de || !dbar || !zbar || !rbar || !Ut || !Phi_out || !G_out || !m_out)
-        return set_err("gf_chunk_transition: null pointer%s", "");
-    if (check_sweep_options("gf_chunk_transition", 1, variant, Jr, Jc)) return -1;
+        return gf_internal_error(-1, "gf_chunk_transition: null pointer");
+    if (check_sweep_options(who, 1, variant, Jr, Jc)) return -1;
     if (chunk_count == 0) return 0;
     const bool tiled = sweep_tiled(variant, Jr, Jc);
-    hipStream_t st = (hipStream_t)stream;
-    const int rows = (W + 3) / 4 * 4;
-    switch (rows) {
-        GF_PHI_CASE(4) GF_PHI_CASE(8) GF_PHI_CASE(12) GF_PHI_CASE(16) GF_PHI_CASE(20) GF_PHI_CASE(24)
-        GF_PHI_CASE(28) GF_PHI_CASE(32) GF_PHI_CASE(36) GF_PHI_CASE(40) GF_PHI_CASE(44) GF_PHI_CASE(48)
-        GF_PHI_CASE(52) GF_PHI_CASE(56) GF_PHI_CASE(60) GF_PHI_CASE(64)
-        default: return set_err("gf_chunk_transition: internal dispatch error%s", "");
-    }
-    return check_launch("gf_chunk_transition");
+    if (!dispatch_rows((W + 3) / 4 * 4, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            hipLaunchKernelGGL((tiled ? k_phi7<R> : k_phi<R>), dim3(B * chunk_count), dim3(64), 0, (hipStream_t)stream, N,
+                               chunk_len, nch, chunk_first, chunk_count, W, c, de, dbar, zbar, rbar, Ut, Phi_out, G_out,
+                               m_out);
+        }))
+        return gf_internal_error(-1, "gf_chunk_transition: internal dispatch error");
+    return check_launch(who);
 }
 
-// the > 64 KB dynamic-LDS opt-in is a per-device function attribute: remember it per device -- the
-// device the STREAM belongs to (not the calling thread's current device) -- and apply it with that
-// device current.  Returns false if the attribute could not be set.
-static bool lds_opt_in(int which, hipStream_t st, const void *const *funcs, int nfuncs, size_t bytes) {
-    return gf_internal_lds_opt_in(which, st, funcs, nfuncs, bytes);
-}
 
 static int cb_ns(int W) { return W > 48 ? 64 : (W > 32 ? 48 : 32); }
 static size_t cb_lds_bytes(int W) {      // 48 x 48 matrices: two workgroups per CU; 32 x 32: four
@@ -6805,18 +6852,18 @@ static size_t cb_lds_bytes(int W) {      // 48 x 48 matrices: two workgroups per
 
 int gf_chunk_combine(int B, int nch, int W, const double *Phi, const double *G, const double *m,
                      double *S_state, double *F_state, void *stream) {
-    if (B < 1 || nch < 1) return set_err("gf_chunk_combine: empty problem%s", "");
-    if (W < 1 || W > 64) return set_err("gf_chunk_combine: width %s%lld unsupported (1..64)", "", W);
-    if (!Phi || !G || !m || !S_state || !F_state) return set_err("gf_chunk_combine: null pointer%s", "");
+    if (B < 1 || nch < 1) return gf_internal_error(-1, "gf_chunk_combine: empty problem");
+    if (W < 1 || W > 64) return gf_internal_error(-1, "gf_chunk_combine: width %d unsupported (1..64)", W);
+    if (!Phi || !G || !m || !S_state || !F_state) return gf_internal_error(-1, "gf_chunk_combine: null pointer");
     const size_t lds = cb_lds_bytes(W);
     const void *fn[3] = {(const void *)k_combine<64>, (const void *)k_combine<48>, (const void *)k_combine<32>};
-    if (!lds_opt_in(0, (hipStream_t)stream, fn, 3, cb_lds_bytes(64))) return set_err("gf_chunk_combine: cannot opt in to %s%lld bytes of LDS", "", (long long)lds);
     hipStream_t st = (hipStream_t)stream;
-    switch (cb_ns(W)) {
-    case 64: hipLaunchKernelGGL(k_combine<64>, dim3(B), dim3(256), lds, st, nch, W, Phi, G, m, S_state, F_state); break;
-    case 48: hipLaunchKernelGGL(k_combine<48>, dim3(B), dim3(256), lds, st, nch, W, Phi, G, m, S_state, F_state); break;
-    default: hipLaunchKernelGGL(k_combine<32>, dim3(B), dim3(256), lds, st, nch, W, Phi, G, m, S_state, F_state); break;
-    }
+    // (the > 64 KB dynamic-LDS opt-in is per device, the one the STREAM belongs to: gf_internal_lds_opt_in)
+    if (!gf_internal_lds_opt_in(0, st, fn, 3, cb_lds_bytes(64)))
+        return gf_internal_error(-1, "gf_chunk_combine: cannot opt in to %lld bytes of LDS", (long long)lds);
+    dispatch_among<64, 48, 32>(cb_ns(W), [&](auto ns) {
+        hipLaunchKernelGGL(k_combine<decltype(ns)::value>, dim3(B), dim3(256), lds, st, nch, W, Phi, G, m, S_state, F_state);
+    });
     return check_launch("gf_chunk_combine");
 }
 
@@ -6834,16 +6881,16 @@ int64_t gf_chunk_combine_tree_work(int B, int P, int nch) {
 
 int gf_chunk_combine_tree(int B, int P, int nch, int W, double *Phi, double *G, double *m, double *S, double *F,
                           double *Xst, double *Yst, double *work, void *stream) {
-    if (B < 1 || P < 2 || (P & (P - 1))) return set_err("gf_chunk_combine_tree: P=%s%lld must be a power of two >= 2", "", P);
-    if (nch <= P / 2 || nch > P) return set_err("gf_chunk_combine_tree: nch=%s%lld must lie in (P / 2, P]", "", nch);
-    if (W < 1 || W > 64) return set_err("gf_chunk_combine_tree: width %s%lld unsupported (1..64)", "", W);
-    if (!Phi || !G || !m || !S || !F || !Xst || !Yst || !work) return set_err("gf_chunk_combine_tree: null pointer%s", "");
+    if (B < 1 || P < 2 || (P & (P - 1))) return gf_internal_error(-1, "gf_chunk_combine_tree: P=%d must be a power of two >= 2", P);
+    if (nch <= P / 2 || nch > P) return gf_internal_error(-1, "gf_chunk_combine_tree: nch=%d must lie in (P / 2, P]", nch);
+    if (W < 1 || W > 64) return gf_internal_error(-1, "gf_chunk_combine_tree: width %d unsupported (1..64)", W);
+    if (!Phi || !G || !m || !S || !F || !Xst || !Yst || !work) return gf_internal_error(-1, "gf_chunk_combine_tree: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = cb_lds_bytes(W);
     const void *fn[6] = {(const void *)k_tree_compose<64>, (const void *)k_tree_apply<64>,
                          (const void *)k_tree_compose<48>, (const void *)k_tree_apply<48>,
                          (const void *)k_tree_compose<32>, (const void *)k_tree_apply<32>};
-    if (!lds_opt_in(1, st, fn, 6, cb_lds_bytes(64))) return set_err("gf_chunk_combine_tree: cannot opt in to %s%lld bytes of LDS", "", (long long)lds);
+    if (!gf_internal_lds_opt_in(1, st, fn, 6, cb_lds_bytes(64))) return gf_internal_error(-1, "gf_chunk_combine_tree: cannot opt in to %lld bytes of LDS", (long long)lds);
     TreeArgs A;
     A.P = P; A.n = W; A.nch = nch; A.Phi = Phi; A.G = G; A.S = S; A.F = F; A.m = m; A.Xst = Xst; A.Yst = Yst;
     {
@@ -6858,19 +6905,17 @@ int gf_chunk_combine_tree(int B, int P, int nch, int W, double *Phi, double *G, 
     // applies (it uses LEFT children only): left out, one level's latency less
     for (int d = 1; d < P / 2; d *= 2) {
         A.d = d; A.pairs = real_pairs(d);
-        const dim3 grid(B * A.pairs);
-        if (ns == 64) hipLaunchKernelGGL(k_tree_compose<64>, grid, dim3(256), lds, st, A);
-        else if (ns == 48) hipLaunchKernelGGL(k_tree_compose<48>, grid, dim3(256), lds, st, A);
-        else hipLaunchKernelGGL(k_tree_compose<32>, grid, dim3(256), lds, st, A);
+        dispatch_among<64, 48, 32>(ns, [&](auto s) {
+            hipLaunchKernelGGL(k_tree_compose<decltype(s)::value>, dim3(B * A.pairs), dim3(256), lds, st, A);
+        });
     }
     A.d = P / 2; A.pairs = 1;
     hipLaunchKernelGGL(k_tree_top, dim3(B), dim3(256), 0, st, A);                    // root state = zero, first level
     for (int d = P / 4; d >= 1; d /= 2) {   // down-sweep
         A.d = d; A.pairs = real_pairs(d);
-        const dim3 grid(B * A.pairs);
-        if (ns == 64) hipLaunchKernelGGL(k_tree_apply<64>, grid, dim3(256), lds, st, A);
-        else if (ns == 48) hipLaunchKernelGGL(k_tree_apply<48>, grid, dim3(256), lds, st, A);
-        else hipLaunchKernelGGL(k_tree_apply<32>, grid, dim3(256), lds, st, A);
+        dispatch_among<64, 48, 32>(ns, [&](auto s) {
+            hipLaunchKernelGGL(k_tree_apply<decltype(s)::value>, dim3(B * A.pairs), dim3(256), lds, st, A);
+        });
     }
     return check_launch("gf_chunk_combine_tree");
 }
@@ -6879,19 +6924,16 @@ int gf_chunk_transition_wide(int B, int64_t N, int64_t chunk_len, int nch, int c
                              int Jc, const double *c, const double *de, const double *dbar, const double *rbar,
                              const double *Ut, double *h_out, double *Phi_out, void *stream) {
     const int W = 2 * Jc;
-    if (chunk_first < 0 || chunk_count < 0 || chunk_first + chunk_count > nch)
-        return set_err("gf_chunk_transition_wide: bad chunk range (first=%s%lld, count=%lld)", "", chunk_first, chunk_count);
+    if (check_chunk_range("gf_chunk_transition_wide", chunk_first, chunk_count, nch)) return -1;
     if (chunk_count == 0) return 0;
-    if (B < 1 || N < 1) return set_err("gf_chunk_transition_wide: empty problem (N=%s%lld)", "", N);
-    if (W <= 63 || !gf_fused_supported(0, Jc)) return set_err("gf_chunk_transition_wide: width %s%lld unsupported (64..176)", "", W);
-    if (nch < 1 || chunk_len < 1 || (nch > 1 && (chunk_len % 64) != 0) || (int64_t)nch * chunk_len < N
-        || (int64_t)(nch - 1) * chunk_len >= N)
-        return set_err("gf_chunk_transition_wide: bad chunking (chunk_len=%s%lld, nch=%lld)", "", chunk_len, nch);
-    if (!c || !de || !dbar || !rbar || !Ut || !h_out || !Phi_out) return set_err("gf_chunk_transition_wide: null pointer%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_chunk_transition_wide: empty problem (N=%lld)", (long long)N);
+    if (W <= 63 || !gf_fused_supported(0, Jc)) return gf_internal_error(-1, "gf_chunk_transition_wide: width %d unsupported (64..176)", W);
+    if (check_chunking("gf_chunk_transition_wide", N, chunk_len, nch, 64)) return -1;
+    if (!c || !de || !dbar || !rbar || !Ut || !h_out || !Phi_out) return gf_internal_error(-1, "gf_chunk_transition_wide: null pointer");
     const WideShape ws = wide_shape(W);
     const int CP = 32 * ws.nw, tr8 = ws.tr / 2;     // rows per lane with 8 row groups
     const int64_t grid = (int64_t)B * chunk_count * ((W + 15) / 16);
-    if (grid > 0x7fffffffLL) return set_err("gf_chunk_transition_wide: problem too large%s", "");
+    if (grid > 0x7fffffffLL) return gf_internal_error(-1, "gf_chunk_transition_wide: problem too large");
     hipStream_t st = (hipStream_t)stream;
     // one kilobyte per row vector while the row, its pivot pair and its reset-span pair fit (CP <= 124), else two
     const int ni = (CP * 8 + 32 <= 1024) ? 1 : 2;
@@ -6899,8 +6941,7 @@ int gf_chunk_transition_wide(int B, int64_t N, int64_t chunk_len, int nch, int c
     GF_PW(8, 4, 1) GF_PW(10, 4, 1) GF_PW(12, 4, 1)
     GF_PW(12, 4, 2) GF_PW(14, 4, 2) GF_PW(16, 4, 2) GF_PW(18, 4, 2) GF_PW(20, 4, 2) GF_PW(22, 4, 2)
 #undef GF_PW
-    return set_err("gf_chunk_transition_wide: internal dispatch error%s", "");
-    return check_launch("gf_chunk_transition_wide");
+    return gf_internal_error(-1, "gf_chunk_transition_wide: internal dispatch error");
 }
 
 // leading dimension of the rows gf_chunk_sweep stores (Ut_out, Wt_out, r_out): 64 for W <= 63, the padded
@@ -6913,32 +6954,30 @@ int gf_fused_row_stride(int Jr, int Jc) {
 
 int gf_scaled_propagator(int B, int64_t N, int W, int ld, const double *c, const double *de,
                          double *P_out, void *stream) {
-    if (B < 1 || N < 1) return set_err("gf_scaled_propagator: empty problem (N=%s%lld)", "", N);
-    if (W < 1 || ld < W) return set_err("gf_scaled_propagator: bad width / ld (W=%s%lld, ld=%lld)", "", W, ld);
-    if (!c || !de || !P_out) return set_err("gf_scaled_propagator: null pointer%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_scaled_propagator: empty problem (N=%lld)", (long long)N);
+    if (W < 1 || ld < W) return gf_internal_error(-1, "gf_scaled_propagator: bad width / ld (W=%d, ld=%d)", W, ld);
+    if (!c || !de || !P_out) return gf_internal_error(-1, "gf_scaled_propagator: null pointer");
     const int64_t blocks = (N * ld + 255) / 256;
-    if (blocks > 0x7fffffffLL) return set_err("gf_scaled_propagator: problem too large%s", "");
+    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_scaled_propagator: problem too large");
     hipLaunchKernelGGL(k_scaled_propagator, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream,
                        N, W, ld, c, de, P_out);
     return check_launch("gf_scaled_propagator");
 }
 
-#define GF_LINR_CASE(Rw) case Rw: if (mode == GF_MATMUL_LOWER && !store) hipLaunchKernelGGL((k_linR7<Rw, true>), dim3(B * nch, (R + 63) / 64), dim3(64), 0, st, A); else hipLaunchKernelGGL((k_linR7<Rw, false>), dim3(B * nch, (R + 63) / 64), dim3(64), 0, st, A); break;
-
 int gf_chunk_linear(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int R,
                     int scale, int store, const double *c,
                     const double *Ut, const double *Wt, const double *d, const double *de,
                     const double *Y, double *Z, double *F_state, void *stream) {
-    if (mode < 0 || mode > 2) return set_err("gf_chunk_linear: bad mode %s%lld", "", mode);
-    if (B < 1 || N < 1 || R < 1) return set_err("gf_chunk_linear: empty problem (N=%s%lld, R=%lld)", "", N, R);
-    if (W < 1 || W > 63) return set_err("gf_chunk_linear: width %s%lld unsupported (1..63)", "", W);
-    if (nch < 1 || chunk_len < 1 || (int64_t)nch * chunk_len < N || (int64_t)(nch - 1) * chunk_len >= N)
-        return set_err("gf_chunk_linear: bad chunking (chunk_len=%s%lld, nch=%lld)", "", chunk_len, nch);
-    if (!c || !Ut || !Wt || !d || !de || !Y || !Z || !F_state) return set_err("gf_chunk_linear: null pointer%s", "");
+    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_chunk_linear: bad mode %d", mode);
+    if (B < 1 || N < 1 || R < 1) return gf_internal_error(-1, "gf_chunk_linear: empty problem (N=%lld, R=%d)", (long long)N, R);
+    if (W < 1 || W > 63) return gf_internal_error(-1, "gf_chunk_linear: width %d unsupported (1..63)", W);
+    if (check_chunking("gf_chunk_linear", N, chunk_len, nch, 1)) return -1;
+    if (!c || !Ut || !Wt || !d || !de || !Y || !Z || !F_state) return gf_internal_error(-1, "gf_chunk_linear: null pointer");
     LinArgs A;
     A.N = N; A.chunk_len = chunk_len; A.nch = nch; A.W = W; A.mode = mode; A.scale = scale; A.store = store;
     A.c = c; A.Ut = Ut; A.Wt = Wt; A.d = d; A.de = de; A.Y = Y; A.Z = Z; A.F_state = F_state; A.R = R;
     hipStream_t st = (hipStream_t)stream;
+    bool ok = true;
     if (R == 1) {
         hipLaunchKernelGGL(k_lin1, dim3(B * nch), dim3(64), 0, st, A);
     } else if (mode == GF_MATMUL_LOWER && R >= 16) {
@@ -6946,34 +6985,29 @@ int gf_chunk_linear(int mode, int B, int64_t N, int64_t chunk_len, int nch, int 
         // two waves per workgroup share the block's rows (32 right-hand sides each); one when R <= 32
         const int nwv = (R > 32) ? 2 : 1;
         const dim3 grid(B * nch, (R + 32 * nwv - 1) / (32 * nwv));
-#define GF_MM_LAUNCH(MTv, ND, NWVv) hipLaunchKernelGGL((k_mmR_mfma<MTv, ND, NWVv>), grid, dim3(64 * NWVv), 0, st, A)
-#define GF_MM_CASE(MTv) case MTv: if (store) { if (nwv == 2) GF_MM_LAUNCH(MTv, false, 2); else GF_MM_LAUNCH(MTv, false, 1); } \
-                                  else { if (nwv == 2) GF_MM_LAUNCH(MTv, true, 2); else GF_MM_LAUNCH(MTv, true, 1); } break;
-        switch ((W + 15) / 16) {
-            GF_MM_CASE(1) GF_MM_CASE(2) GF_MM_CASE(3) GF_MM_CASE(4)
-            default: return set_err("gf_chunk_linear: internal dispatch error%s", "");
-        }
-#undef GF_MM_LAUNCH
-#undef GF_MM_CASE
+        ok = dispatch_among<1, 2, 3, 4>((W + 15) / 16, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            if (nwv == 2) hipLaunchKernelGGL((store ? k_mmR_mfma<MT, false, 2> : k_mmR_mfma<MT, true, 2>), grid, dim3(128), 0, st, A);
+            else          hipLaunchKernelGGL((store ? k_mmR_mfma<MT, false, 1> : k_mmR_mfma<MT, true, 1>), grid, dim3(64), 0, st, A);
+        });
     } else {
-        const int rows = (W + 3) / 4 * 4;
-        switch (rows) {
-            GF_LINR_CASE(4) GF_LINR_CASE(8) GF_LINR_CASE(12) GF_LINR_CASE(16) GF_LINR_CASE(20) GF_LINR_CASE(24)
-            GF_LINR_CASE(28) GF_LINR_CASE(32) GF_LINR_CASE(36) GF_LINR_CASE(40) GF_LINR_CASE(44) GF_LINR_CASE(48)
-            GF_LINR_CASE(52) GF_LINR_CASE(56) GF_LINR_CASE(60) GF_LINR_CASE(64)
-            default: return set_err("gf_chunk_linear: internal dispatch error%s", "");
-        }
+        ok = dispatch_rows((W + 3) / 4 * 4, [&](auto r) {
+            constexpr int Rw = decltype(r)::value;
+            hipLaunchKernelGGL((mode == GF_MATMUL_LOWER && !store ? k_linR7<Rw, true> : k_linR7<Rw, false>),
+                               dim3(B * nch, (R + 63) / 64), dim3(64), 0, st, A);
+        });
     }
+    if (!ok) return gf_internal_error(-1, "gf_chunk_linear: internal dispatch error");
     return check_launch("gf_chunk_linear");
 }
 
 int gf_chunk_linear_combine(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int R,
                             const double *c, const double *de, const double *Phi,
                             double *D_work, double *F_state, void *stream) {
-    if (mode < 0 || mode > 2) return set_err("gf_chunk_linear_combine: bad mode %s%lld", "", mode);
-    if (B < 1 || nch < 1 || R < 1) return set_err("gf_chunk_linear_combine: empty problem%s", "");
+    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_chunk_linear_combine: bad mode %d", mode);
+    if (B < 1 || nch < 1 || R < 1) return gf_internal_error(-1, "gf_chunk_linear_combine: empty problem");
     if (!F_state || (mode == GF_MATMUL_LOWER ? (!D_work || !c || !de) : !Phi))
-        return set_err("gf_chunk_linear_combine: null pointer%s", "");
+        return gf_internal_error(-1, "gf_chunk_linear_combine: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (mode == GF_MATMUL_LOWER) {
         hipLaunchKernelGGL(k_chunk_decay, dim3(B * nch), dim3(64), 0, st, N, chunk_len, nch, W, c, de, D_work);
@@ -6987,9 +7021,9 @@ int gf_chunk_linear_combine(int mode, int B, int64_t N, int64_t chunk_len, int n
 
 int gf_chunk_segment_transitions(int B, int nch, int seg_len, const double *Phi, double *Psi_out,
                                  double *PhiT_out, double *PsiT_out, void *stream) {
-    if (B < 1 || nch < 1 || seg_len < 1) return set_err("gf_chunk_segment_transitions: empty problem%s", "");
+    if (B < 1 || nch < 1 || seg_len < 1) return gf_internal_error(-1, "gf_chunk_segment_transitions: empty problem");
     if (!Phi || !Psi_out || ((PhiT_out != nullptr) != (PsiT_out != nullptr)))
-        return set_err("gf_chunk_segment_transitions: null pointer (PhiT_out and PsiT_out go together)%s", "");
+        return gf_internal_error(-1, "gf_chunk_segment_transitions: null pointer (PhiT_out and PsiT_out go together)");
     const int nseg = (nch + seg_len - 1) / seg_len;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_segment_transition, dim3(B * nseg), dim3(256), 0, st, nch, seg_len, Phi, Psi_out);
@@ -7004,11 +7038,11 @@ int gf_chunk_linear_combine_seg(int mode, int B, int nch, int seg_len, int R, co
                                 const double *Psi, const double *PhiT, const double *PsiT,
                                 double *F_state, double *V_work, void *stream) {
     if (mode != GF_SOLVE_LOWER && mode != GF_SOLVE_UPPER)
-        return set_err("gf_chunk_linear_combine_seg: bad mode %s%lld (the solves only)", "", mode);
-    if ((PhiT != nullptr) != (PsiT != nullptr)) return set_err("gf_chunk_linear_combine_seg: PhiT and PsiT go together%s", "");
+        return gf_internal_error(-1, "gf_chunk_linear_combine_seg: bad mode %d (the solves only)", mode);
+    if ((PhiT != nullptr) != (PsiT != nullptr)) return gf_internal_error(-1, "gf_chunk_linear_combine_seg: PhiT and PsiT go together");
     if (mode == GF_SOLVE_UPPER && PhiT) { Phi = PhiT; Psi = PsiT; mode |= LC_TRANSPOSED; }
-    if (B < 1 || nch < 1 || R < 1 || seg_len < 1) return set_err("gf_chunk_linear_combine_seg: empty problem%s", "");
-    if (!Phi || !Psi || !F_state || !V_work) return set_err("gf_chunk_linear_combine_seg: null pointer%s", "");
+    if (B < 1 || nch < 1 || R < 1 || seg_len < 1) return gf_internal_error(-1, "gf_chunk_linear_combine_seg: empty problem");
+    if (!Phi || !Psi || !F_state || !V_work) return gf_internal_error(-1, "gf_chunk_linear_combine_seg: null pointer");
     const int nseg = (nch + seg_len - 1) / seg_len;
     hipStream_t st = (hipStream_t)stream;
     // the segment scans: per right-hand side, or 64 right-hand sides at a time on the matrix pipe
@@ -7026,9 +7060,9 @@ int gf_chunk_linear_combine_seg(int mode, int B, int nch, int seg_len, int R, co
 }
 
 int gf_dense_solve_logdet(int batch, int n, int nrhs, const double *A, double *B, double *logdet_out, void *stream) {
-    if (batch < 1 || n < 1 || nrhs < 1) return set_err("gf_dense_solve: empty problem (n=%s%lld, nrhs=%lld)", "", n, nrhs);
-    if (n > 192) return set_err("gf_dense_solve: n=%s%lld unsupported (max %lld)", "", n, 192);
-    if (!A || !B) return set_err("gf_dense_solve: null pointer%s", "");
+    if (batch < 1 || n < 1 || nrhs < 1) return gf_internal_error(-1, "gf_dense_solve: empty problem (n=%d, nrhs=%d)", n, nrhs);
+    if (n > 192) return gf_internal_error(-1, "gf_dense_solve: n=%d unsupported (max %d)", n, 192);
+    if (!A || !B) return gf_internal_error(-1, "gf_dense_solve: null pointer");
     hipStream_t st = (hipStream_t)stream;
     // few systems: 16 right-hand sides per workgroup (more, shorter-stepping workgroups); else 64
     const int slices4 = (nrhs + DS_WAVES * 4 - 1) / (DS_WAVES * 4);
@@ -7054,8 +7088,8 @@ int64_t gf_reduce_work(int64_t N) { return RED_NACC * (int64_t)red_groups(N); }
 
 int gf_reduce_tile(int B, int64_t N, const double *d, const double *z,
                    double *work, double *acc, int init, void *stream) {
-    if (B < 1 || N < 1) return set_err("gf_reduce_tile: empty problem (B=%s%lld, N=%lld)", "", B, N);
-    if (!d || !work || !acc) return set_err("gf_reduce_tile: null pointer%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_reduce_tile: empty problem (B=%d, N=%lld)", B, (long long)N);
+    if (!d || !work || !acc) return gf_internal_error(-1, "gf_reduce_tile: null pointer");
     const int G = red_groups(N);
     hipLaunchKernelGGL(k_reduce1<false>, dim3(G, B), dim3(RED_BLOCK), 0, (hipStream_t)stream, N, d, z, work,
                        (const double *)nullptr, (int64_t)0);
@@ -7067,8 +7101,8 @@ int gf_reduce_tile(int B, int64_t N, const double *d, const double *z,
 int gf_reduce_tile_steady(int B, int64_t N, int64_t n_first, const double *d, const double *z,
                           const double *steady, double *work, double *acc, int init, void *stream) {
     if (B < 1 || N < 1 || n_first < 0)
-        return set_err("gf_reduce_tile_steady: empty problem or negative n_first (N=%s%lld, n_first=%lld)", "", N, n_first);
-    if (!d || !steady || !work || !acc) return set_err("gf_reduce_tile_steady: null pointer%s", "");
+        return gf_internal_error(-1, "gf_reduce_tile_steady: empty problem or negative n_first (N=%lld, n_first=%lld)", (long long)N, (long long)n_first);
+    if (!d || !steady || !work || !acc) return gf_internal_error(-1, "gf_reduce_tile_steady: null pointer");
     const int G = red_groups(N);
     hipLaunchKernelGGL(k_reduce1<true>, dim3(G, B), dim3(RED_BLOCK), 0, (hipStream_t)stream, N, d, z, work, steady, n_first);
     hipLaunchKernelGGL(k_reduce2<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, G, work, acc, init, steady, N, n_first);
@@ -7077,8 +7111,8 @@ int gf_reduce_tile_steady(int B, int64_t N, int64_t n_first, const double *d, co
 
 int gf_loglike_finish(int B, int64_t N, const double *acc, const int32_t *info,
                       double *out, double *logdet, void *stream) {
-    if (B < 1 || N < 1) return set_err("gf_loglike_finish: empty problem (B=%s%lld, N=%lld)", "", B, N);
-    if (!acc || (!out && !logdet)) return set_err("gf_loglike_finish: null pointer%s", "");
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_loglike_finish: empty problem (B=%d, N=%lld)", B, (long long)N);
+    if (!acc || (!out && !logdet)) return gf_internal_error(-1, "gf_loglike_finish: null pointer");
     hipLaunchKernelGGL(k_finish, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, N, acc, info, out, logdet);
     return check_launch("gf_loglike_finish");
 }
@@ -7120,14 +7154,12 @@ static void launch_solve_rhs(const SolveArgs &A, int slots, hipStream_t st) {
 int gf_solve_chunk(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int ld,
                    const double *U, const double *Wm, const double *P, const double *scale,
                    const double *Y, double *Z, double *F_state, int store, void *stream) {
-    if (mode < 0 || mode > 2) return set_err("gf_solve_chunk: bad mode %s%lld", "", mode);
-    if (B < 1 || N < 1) return set_err("gf_solve_chunk: empty problem (N=%s%lld)", "", N);
-    if (W < 1 || W > GF_MAX_WIDTH) return set_err("gf_solve_chunk: width %s%lld unsupported (max %lld)", "", W, GF_MAX_WIDTH);
-    if (ld < W || (ld & 15)) return set_err("gf_solve_chunk: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
-    if (nch < 1 || chunk_len < 1 || (int64_t)nch * chunk_len < N || (int64_t)(nch - 1) * chunk_len >= N)
-        return set_err("gf_solve_chunk: bad chunking (chunk_len=%s%lld, nch=%lld)", "", chunk_len, nch);
-    if (!U || !Wm || !P || !Y || !Z || !F_state) return set_err("gf_solve_chunk: null pointer%s", "");
-    if ((int64_t)B * nch > 0x7fffffffLL) return set_err("gf_solve_chunk: problem too large%s", "");
+    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_solve_chunk: bad mode %d", mode);
+    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_solve_chunk: empty problem (N=%lld)", (long long)N);
+    if (check_width_ld("gf_solve_chunk", W, ld)) return -1;
+    if (check_chunking("gf_solve_chunk", N, chunk_len, nch, 1)) return -1;
+    if (!U || !Wm || !P || !Y || !Z || !F_state) return gf_internal_error(-1, "gf_solve_chunk: null pointer");
+    if ((int64_t)B * nch > 0x7fffffffLL) return gf_internal_error(-1, "gf_solve_chunk: problem too large");
     SolveArgs A;
     A.N = N; A.W = W; A.ld = ld; A.R = 1; A.mode = mode;
     A.U = U; A.Wm = Wm; A.P = P; A.scale = scale; A.Y = Y; A.Z = Z;
@@ -7142,14 +7174,12 @@ int gf_solve_chunk(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W
 int gf_solve_chunk_rhs(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int ld, int R,
                        const double *U, const double *Wm, const double *P, const double *scale,
                        const double *Y, double *Z, double *F_state, int store, void *stream) {
-    if (mode < 0 || mode > 2) return set_err("gf_solve_chunk_rhs: bad mode %s%lld", "", mode);
-    if (B < 1 || N < 1 || R < 1) return set_err("gf_solve_chunk_rhs: empty problem (N=%s%lld, R=%lld)", "", N, R);
-    if (W < 1 || W > GF_MAX_WIDTH) return set_err("gf_solve_chunk_rhs: width %s%lld unsupported (max %lld)", "", W, GF_MAX_WIDTH);
-    if (ld < W || (ld & 15)) return set_err("gf_solve_chunk_rhs: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
-    if (nch < 1 || chunk_len < 1 || (int64_t)nch * chunk_len < N || (int64_t)(nch - 1) * chunk_len >= N)
-        return set_err("gf_solve_chunk_rhs: bad chunking (chunk_len=%s%lld, nch=%lld)", "", chunk_len, nch);
-    if (!U || !Wm || !P || !Y || !Z || !F_state) return set_err("gf_solve_chunk_rhs: null pointer%s", "");
-    if ((int64_t)B * nch > 65535) return set_err("gf_solve_chunk_rhs: too many chunks (B * nch = %s%lld > 65535)", "", (int64_t)B * nch);
+    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_solve_chunk_rhs: bad mode %d", mode);
+    if (B < 1 || N < 1 || R < 1) return gf_internal_error(-1, "gf_solve_chunk_rhs: empty problem (N=%lld, R=%d)", (long long)N, R);
+    if (check_width_ld("gf_solve_chunk_rhs", W, ld)) return -1;
+    if (check_chunking("gf_solve_chunk_rhs", N, chunk_len, nch, 1)) return -1;
+    if (!U || !Wm || !P || !Y || !Z || !F_state) return gf_internal_error(-1, "gf_solve_chunk_rhs: null pointer");
+    if ((int64_t)B * nch > 65535) return gf_internal_error(-1, "gf_solve_chunk_rhs: too many chunks (B * nch = %lld > 65535)", (long long)B * nch);
     SolveArgs A;
     A.N = N; A.W = W; A.ld = ld; A.R = R; A.mode = mode;
     A.U = U; A.Wm = Wm; A.P = P; A.scale = scale; A.Y = Y; A.Z = Z;
@@ -7163,8 +7193,8 @@ int gf_solve_chunk_rhs(int mode, int B, int64_t N, int64_t chunk_len, int nch, i
 // GF_MATMUL_LOWER branch for any number of state rows.
 int gf_chunk_diag_scan(int B, int nch, int rows, int R, const double *D, double *F_state, void *stream) {
     if (B < 1 || nch < 1 || rows < 1 || R < 1 || R > 64)
-        return set_err("gf_chunk_diag_scan: bad shape (rows=%s%lld, R=%lld)", "", rows, R);
-    if (!D || !F_state) return set_err("gf_chunk_diag_scan: null pointer%s", "");
+        return gf_internal_error(-1, "gf_chunk_diag_scan: bad shape (rows=%d, R=%d)", rows, R);
+    if (!D || !F_state) return gf_internal_error(-1, "gf_chunk_diag_scan: null pointer");
     hipLaunchKernelGGL(k_lincombine_mm, dim3(B, rows, (R + 15) / 16), dim3(64 * LCM_WAVES), 0, (hipStream_t)stream,
                        nch, R, rows, D, F_state);
     return check_launch("gf_chunk_diag_scan");
@@ -7173,12 +7203,11 @@ int gf_chunk_diag_scan(int B, int nch, int rows, int R, const double *D, double 
 int gf_solve(int mode, int B, int64_t N, int W, int ld, int R,
              const double *U, const double *Wm, const double *P, const double *scale,
              const double *Y, double *Z, void *stream) {
-    if (mode < 0 || mode > 2) return set_err("gf_solve: bad mode %s%lld", "", mode);
-    if (B < 1 || N < 1 || R < 1) return set_err("gf_solve: empty problem (N=%s%lld, R=%lld)", "", N, R);
-    if (W < 1 || W > GF_MAX_WIDTH) return set_err("gf_solve: width %s%lld unsupported (max %lld)", "", W, GF_MAX_WIDTH);
-    if (ld < W || (ld & 15)) return set_err("gf_solve: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
-    if (!U || !Wm || !P || !Y || !Z) return set_err("gf_solve: null pointer%s", "");
-    if (mode == GF_MATMUL_LOWER && Y == Z) return set_err("gf_solve: GF_MATMUL_LOWER cannot run in place%s", "");
+    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_solve: bad mode %d", mode);
+    if (B < 1 || N < 1 || R < 1) return gf_internal_error(-1, "gf_solve: empty problem (N=%lld, R=%d)", (long long)N, R);
+    if (check_width_ld("gf_solve", W, ld)) return -1;
+    if (!U || !Wm || !P || !Y || !Z) return gf_internal_error(-1, "gf_solve: null pointer");
+    if (mode == GF_MATMUL_LOWER && Y == Z) return gf_internal_error(-1, "gf_solve: GF_MATMUL_LOWER cannot run in place");
     SolveArgs A;
     A.N = N; A.W = W; A.ld = ld; A.R = R; A.mode = mode;
     A.U = U; A.Wm = Wm; A.P = P; A.scale = scale; A.Y = Y; A.Z = Z;
@@ -7198,10 +7227,10 @@ int gf_cross_covariance(int B, int64_t N, int R, int Jr, int Jc,
                         const double *bc, const double *cc, const double *dc,
                         const double *t, int64_t t_bs, const double *ts, int64_t ts_bs,
                         double *out, void *stream) {
-    if (B < 1 || N < 1 || R < 1 || R > 4096) return set_err("gf_cross_covariance: bad shape (N=%s%lld, R=%lld)", "", N, R);
-    if (Jr < 0 || Jc < 0 || Jr + Jc < 1 || Jr + 2 * Jc > GF_MAX_WIDTH) return set_err("gf_cross_covariance: bad term counts%s", "");
+    if (B < 1 || N < 1 || R < 1 || R > 4096) return gf_internal_error(-1, "gf_cross_covariance: bad shape (N=%lld, R=%d)", (long long)N, R);
+    if (Jr < 0 || Jc < 0 || Jr + Jc < 1 || Jr + 2 * Jc > GF_MAX_WIDTH) return gf_internal_error(-1, "gf_cross_covariance: bad term counts");
     if (!t || !ts || !out || (Jr && (!ar || !cr)) || (Jc && (!ac || !bc || !cc || !dc)))
-        return set_err("gf_cross_covariance: null pointer%s", "");
+        return gf_internal_error(-1, "gf_cross_covariance: null pointer");
     // queries per pass (accumulators per lane) so that the table of (term, query) factors fits 48 KB of LDS up to
     // J = 92 and, with the kernel's 88 static bytes, the 64 KB a launch may ask for without the large-LDS attribute
     // beyond: 8 (36 J + 16) bytes at RT = 16 pass it from J = 227 on (real-term kernels up to J = 256 are within
@@ -7210,7 +7239,7 @@ int gf_cross_covariance(int B, int64_t N, int R, int Jr, int Jc,
     const int RT = (J <= 44) ? 64 : (J <= 92) ? 32 : (J <= 226) ? 16 : 8;
     const size_t lds = sizeof(double) * ((size_t)4 * J + (size_t)2 * RT * J + RT);
     const int64_t blocks = (N + 255) / 256;
-    if (blocks > 0x7fffffffLL) return set_err("gf_cross_covariance: problem too large%s", "");
+    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_cross_covariance: problem too large");
     const dim3 grid((unsigned)blocks, B);
     hipStream_t st = (hipStream_t)stream;
 #define GF_CX(RTv) hipLaunchKernelGGL((k_cross<RTv>), grid, dim3(256), lds, st, N, R, Jr, Jc, ar, cr, ac, bc, cc, dc, t, t_bs, ts, ts_bs, out)
@@ -7225,15 +7254,15 @@ int64_t gf_interp_work(int64_t N) {
 
 int gf_interp_plan(int64_t N, const double *t, const int64_t *cadences, double dt,
                    int64_t *offsets, int64_t *work, void *stream) {
-    if (N < 1) return set_err("gf_interp_plan: empty series (N=%s%lld)", "", N);
-    if (!t || !offsets || !work) return set_err("gf_interp_plan: null pointer%s", "");
-    if (!(dt > 0.0)) return set_err("gf_interp_plan: the cadence must be positive%s", "");
+    if (N < 1) return gf_internal_error(-1, "gf_interp_plan: empty series (N=%lld)", (long long)N);
+    if (!t || !offsets || !work) return gf_internal_error(-1, "gf_interp_plan: null pointer");
+    if (!(dt > 0.0)) return gf_internal_error(-1, "gf_interp_plan: the cadence must be positive");
     hipStream_t st = (hipStream_t)stream;
     const int64_t nb = gf_interp_work(N);
     double t0;
     if (hipMemcpyAsync(&t0, t, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-        return set_err("gf_interp_plan: cannot read the first time%s", "");
+        return gf_internal_error(-1, "gf_interp_plan: cannot read the first time");
     hipLaunchKernelGGL(k_interp_count, dim3((unsigned)nb), dim3(256), 0, st, N, t, cadences, t0, dt, offsets, work);
     hipLaunchKernelGGL(k_interp_scan_top, dim3(1), dim3(256), 0, st, nb, N, work, offsets);
     hipLaunchKernelGGL(k_interp_offsets, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, work, offsets);
@@ -7242,13 +7271,13 @@ int gf_interp_plan(int64_t N, const double *t, const int64_t *cadences, double d
 
 int gf_interp_fill(int64_t N, const double *t, const double *f, const int64_t *cadences, double dt,
                    const int64_t *offsets, double *t_out, double *f_out, void *stream) {
-    if (N < 1) return set_err("gf_interp_fill: empty series (N=%s%lld)", "", N);
-    if (!t || !f || !offsets || !t_out || !f_out) return set_err("gf_interp_fill: null pointer%s", "");
+    if (N < 1) return gf_internal_error(-1, "gf_interp_fill: empty series (N=%lld)", (long long)N);
+    if (!t || !f || !offsets || !t_out || !f_out) return gf_internal_error(-1, "gf_interp_fill: null pointer");
     hipStream_t st = (hipStream_t)stream;
     double t0;
     if (hipMemcpyAsync(&t0, t, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-        return set_err("gf_interp_fill: cannot read the first time%s", "");
+        return gf_internal_error(-1, "gf_interp_fill: cannot read the first time");
     hipLaunchKernelGGL(k_interp_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, t, f, cadences,
                        t0, dt, offsets, t_out, f_out);
     hipLaunchKernelGGL(k_interp_missing, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, t, f, cadences,
@@ -7258,9 +7287,9 @@ int gf_interp_fill(int64_t N, const double *t, const double *f, const int64_t *c
 
 int gf_psd_power(int R, int64_t M, int64_t first, double norm, const double *spec,
                  double *power, void *stream) {
-    if (R < 1 || M < 1 || first < 0 || first >= M) return set_err("gf_psd_power: bad shape (M=%s%lld, first=%lld)", "", M, first);
-    if (!spec || !power) return set_err("gf_psd_power: null pointer%s", "");
-    if (R > 65535) return set_err("gf_psd_power: more than 65535 series%s", "");
+    if (R < 1 || M < 1 || first < 0 || first >= M) return gf_internal_error(-1, "gf_psd_power: bad shape (M=%lld, first=%lld)", (long long)M, (long long)first);
+    if (!spec || !power) return gf_internal_error(-1, "gf_psd_power: null pointer");
+    if (R > 65535) return gf_internal_error(-1, "gf_psd_power: more than 65535 series");
     const int64_t Mout = M - first;
     int64_t blocks = (Mout + 255) / 256;
     if (blocks > 16384) blocks = 16384;
@@ -7271,9 +7300,9 @@ int gf_psd_power(int R, int64_t M, int64_t first, double norm, const double *spe
 
 int gf_psd_bin(int R, int64_t M, int nb, const double *x, const double *power,
                const int64_t *start, double constant, double *stat, double *err, void *stream) {
-    if (R < 1 || M < 1 || nb < 1) return set_err("gf_psd_bin: bad shape (M=%s%lld, bins=%lld)", "", M, (int64_t)nb);
-    if (!x || !power || !start || !stat || !err) return set_err("gf_psd_bin: null pointer%s", "");
-    if (R > 65535) return set_err("gf_psd_bin: more than 65535 series%s", "");
+    if (R < 1 || M < 1 || nb < 1) return gf_internal_error(-1, "gf_psd_bin: bad shape (M=%lld, bins=%d)", (long long)M, nb);
+    if (!x || !power || !start || !stat || !err) return gf_internal_error(-1, "gf_psd_bin: null pointer");
+    if (R > 65535) return gf_internal_error(-1, "gf_psd_bin: more than 65535 series");
     hipLaunchKernelGGL(k_psd_bin, dim3(nb, R), dim3(256), 0, (hipStream_t)stream, M, nb, x, power, start,
                        constant, stat, err);
     return check_launch("gf_psd_bin");
@@ -7307,11 +7336,10 @@ int gf_general_matmul(int B, int64_t M, int64_t N, int W, int ld,
                       const double *t2, int64_t t2_bs, const double *U2, const double *V2,
                       const double *P2, const double *alpha, const int64_t *qidx,
                       double *work, double *mu, void *stream) {
-    if (B < 1 || N < 1 || M < 1) return set_err("gf_general_matmul: empty problem (M=%s%lld, N=%lld)", "", M, N);
-    if (W < 1 || W > GF_MAX_WIDTH) return set_err("gf_general_matmul: width %s%lld unsupported (max %lld)", "", W, GF_MAX_WIDTH);
-    if (ld < W || (ld & 15)) return set_err("gf_general_matmul: ld=%s%lld must be a multiple of 16 and >= W=%lld", "", ld, W);
+    if (B < 1 || N < 1 || M < 1) return gf_internal_error(-1, "gf_general_matmul: empty problem (M=%lld, N=%lld)", (long long)M, (long long)N);
+    if (check_width_ld("gf_general_matmul", W, ld)) return -1;
     if (!c || !t1 || !U1 || !V1 || !t2 || !U2 || !V2 || !P2 || !alpha || !qidx || !work || !mu)
-        return set_err("gf_general_matmul: null pointer%s", "");
+        return gf_internal_error(-1, "gf_general_matmul: null pointer");
     GmmArgs A;
     A.M = M; A.N = N; A.W = W; A.ld = ld; A.c = c;
     A.t1 = t1; A.t1_bs = t1_bs; A.U1 = U1; A.V1 = V1;
@@ -7322,25 +7350,23 @@ int gf_general_matmul(int B, int64_t M, int64_t N, int W, int ld,
     int nch;
     int64_t chunk_len;
     gmm_chunking(B, N, &nch, &chunk_len);
-    if (nch > 1) {                      // long series: chunk-parallel (decayed prefix sums)
-        GmmChunk C;
+    dispatch_among<1, 2, 4>(CT, [&](auto ct) {
+        constexpr int CTv = decltype(ct)::value;
+        if (nch == 1) {
+            hipLaunchKernelGGL(k_gmm<CTv>, dim3(B, 2), dim3(64), 0, st, A);
+            return;
+        }
+        GmmChunk C;                     // long series: chunk-parallel (decayed prefix sums)
         C.chunk_len = chunk_len; C.nch = nch;
         const size_t per = (size_t)B * 2 * nch * CT * 64;
         C.Floc = work + (size_t)B * 2 * M;
         C.Dloc = C.Floc + per;
         C.Fstart = C.Dloc + per;
         const dim3 grid(B, 2, nch);
-        if (CT == 1)      hipLaunchKernelGGL((k_gmm_chunk<1, 0>), grid, dim3(64), 0, st, A, C);
-        else if (CT == 2) hipLaunchKernelGGL((k_gmm_chunk<2, 0>), grid, dim3(64), 0, st, A, C);
-        else              hipLaunchKernelGGL((k_gmm_chunk<4, 0>), grid, dim3(64), 0, st, A, C);
+        hipLaunchKernelGGL((k_gmm_chunk<CTv, 0>), grid, dim3(64), 0, st, A, C);
         hipLaunchKernelGGL(k_gmm_scan, dim3(B, 2), dim3(256), 0, st, CT * 64, C);
-        if (CT == 1)      hipLaunchKernelGGL((k_gmm_chunk<1, 1>), grid, dim3(64), 0, st, A, C);
-        else if (CT == 2) hipLaunchKernelGGL((k_gmm_chunk<2, 1>), grid, dim3(64), 0, st, A, C);
-        else              hipLaunchKernelGGL((k_gmm_chunk<4, 1>), grid, dim3(64), 0, st, A, C);
-    }
-    else if (W <= 64)  hipLaunchKernelGGL(k_gmm<1>, dim3(B, 2), dim3(64), 0, st, A);
-    else if (W <= 128) hipLaunchKernelGGL(k_gmm<2>, dim3(B, 2), dim3(64), 0, st, A);
-    else               hipLaunchKernelGGL(k_gmm<4>, dim3(B, 2), dim3(64), 0, st, A);
+        hipLaunchKernelGGL((k_gmm_chunk<CTv, 1>), grid, dim3(64), 0, st, A, C);
+    });
     hipLaunchKernelGGL(k_add2, dim3((unsigned)((M + 255) / 256), B), dim3(256), 0, st, M, work, mu);
     return check_launch("gf_general_matmul");
 }
