@@ -17,7 +17,8 @@ CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(CSRC, "libgadfly_hip.so")
 if os.environ.get("GADFLY_SO"):                 # another build of the same library (A/B measurements)
     SO_PATH = os.path.abspath(os.environ["GADFLY_SO"])
-SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_dense.hip"),
+SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_series.hip"),
+           os.path.join(CSRC, "gadfly_dense.hip"),
            os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip"),
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
@@ -174,7 +175,8 @@ class GadflyHipError(RuntimeError):
 
 
 HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC"]
-_DEPS = [HEADER] + [os.path.join(CSRC, h) for h in ("fastmath.h", "gf_internal.h", "gf_wave.h", "gf_rows.h")]
+_DEPS = [HEADER] + [os.path.join(CSRC, h) for h in ("fastmath.h", "gf_internal.h", "gf_wave.h", "gf_sweep.h",
+                                                         "gf_rows.h")]
 
 
 def hipcc_command(out=SO_PATH):

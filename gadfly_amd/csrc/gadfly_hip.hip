@@ -1,18 +1,31 @@
-// gadfly_hip.hip -- hand-written HIP kernels for gfx950 (MI355X, CDNA4) + the C-ABI of
-// include/gadfly_hip.h.  float64 throughout; wave = 64 lanes.
+// gadfly_hip.hip -- hand-written HIP kernels for gfx950 (MI355X, CDNA4) + most of the C-ABI of
+// include/gadfly_hip.h, and the library's error state.  float64 throughout; wave = 64 lanes.
 //
 // What is replaced: the celerite2 C++ driver routines behind gadfly's GaussianProcess
-// (/root/reference/gadfly/gp.py:202, :232, :327, :350, :370, :391).
+// (the reference's gadfly/gp.py:202,:232, :327, :350, :370, :391).
 // The arithmetic follows SURVEY.md Appendix A.4-A.8.
 //
 // Kernel inventory
-//   k_build        A.4 generator rows U, V (+ a, + propagator rows P)         HBM/VALU (sincos, exp)
-//   k_factor       A.5 LDL^T recurrence, state S (W x W) in VGPRs, rows split over NW waves,
-//                  optional fused forward solve (A.6) for the log-likelihood path
-//   k_reduce_*     sum log d, sum z^2/d (deterministic fixed-shape tree)
-//   k_solve_vec    A.6/A.7 sweeps, one right-hand side, state F lane-resident
-//   k_solve_rhs    A.6/A.7 sweeps, one lane per right-hand side, generator rows wave-uniform
-//   k_gmm_*        A.8 conditional mean at new times
+//   k_build, k_factor          A.4 generator rows U, V (+ a, + propagator rows P); A.5 LDL^T recurrence, state S (W x W)
+//                              in VGPRs, rows split over NW waves, optional fused forward solve (A.6)
+//   k_build2, k_factor2        the same in block-scaled coordinates (no per-row decay), one wave, W <= 64
+//   k_factor3, k_factor7       the FUSED sweep (build + factor + forward solve, rows never written; RowGen): one column
+//                              per lane, and the 2 x 32 lane tiling; SAMPLE instances draw
+//   k_steady_*                 the rows around the steady switch: tail, finish, chunked finish, rank-one rows
+//   k_phi7, k_phi, k_phiw      closed-loop transition sweeps of the time-parallel evaluation
+//   k_factorw                  the fused sweep for wide kernels (several waves)
+//   k_combine, k_tree_*        the chunk maps' combine, sequential and as a tree scan (cb_*: 64 x 64 LDS block algebra)
+//   k_lin*, k_mmR_mfma, k_lincombine*, k_segment_transition, k_chunk_decay   the stored scaled factor's
+//                              chunk-parallel linear sweeps and their combines
+//   k_dense_solve              batched Gauss-Jordan solve of the wide chunk maps (called from gadfly_dense.hip)
+//   k_reduce1, k_reduce2, k_finish   sum log d, sum z^2/d (deterministic fixed-shape tree), the log-likelihood
+//   k_solve_vec, k_solve_rhs   A.6/A.7 sweeps on stored rows: one right-hand side lane-resident, or one lane each
+//   k_gmm*, k_add2, k_cross    A.8 conditional mean at new times; cross-covariance block
+//   k_factor2w                 the block-scaled recurrence beyond one wave (64 < W <= 256)
+// Elsewhere: the wave-level primitives (gf_wave.h), the sweeps' shared row helpers and SC_SPAN (gf_sweep.h), the entry
+// points' argument checks and instance dispatch (gf_internal.h), and the power-spectrum and gap-filling kernels
+// (gadfly_series.hip).  gf_internal_error / gf_internal_check_launch / gf_internal_lds_opt_in are defined here for
+// every unit of the library.
 //
 // No CUDA compatibility layer, no Triton, no CPU fallback.
 
@@ -34,6 +47,7 @@
 #define FM_INLINE __device__ __forceinline__
 #include "fastmath.h"
 #include "gf_wave.h"
+#include "gf_sweep.h"
 
 // fm_exp with its coefficients formed where they are used.  Written as literals, hipcc hoists the fourteen FP64
 // coefficients out of any loop that contains a call -- also when the call sits on a reset row, one row in 16 to
@@ -74,14 +88,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int check_launch(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-        return -2;
-    }
-    return 0;
-}
 }  // namespace
 
 // what every translation unit of the library reports through, this one included (gf_internal.h)
@@ -92,69 +98,16 @@ int gf_internal_error(int code, const char *fmt, ...) {
     va_end(ap);
     return code;
 }
-int gf_internal_check_launch(const char *what) { return check_launch(what); }
+int gf_internal_check_launch(const char *what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
 
 namespace {
-
-// ------------------------------------------------------------------------------------
-// wave-level primitives (64 lanes, DPP; no LDS traffic)
-// ------------------------------------------------------------------------------------
-// A wave-uniform index made opaque to the optimiser (it stays in SGPRs, at no cost): `p[opaque(i)]`
-// with a loop-invariant per-lane pointer p is then addressed as p + i inside the branch that uses
-// it, instead of becoming one more per-lane 64-bit pointer that loop strength reduction advances
-// with a vector add on EVERY iteration, taken or not.
-__device__ __forceinline__ size_t opaque_uniform(size_t i) {
-    asm volatile("" : "+s"(i));
-    return i;
-}
-
-// Fixed-shape tree sum over the 64 lanes, result broadcast to every lane (deterministic).
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_get<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
-    v += dpp_get<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
-    v += dpp_get<0x141, 0xf>(v);   // row_half_mirror
-    v += dpp_get<0x140, 0xf>(v);   // row_mirror       -> every lane holds its 16-lane row sum
-    // the two broadcasts only matter for row 3 (rows 1, 3 and rows 2, 3 are what LLVM's own
-    // reductions enable with row_mask 0xa / 0xc); with all rows enabled and bound_ctrl every lane is
-    // written, so no zero-initialised destination (2 v_mov + s_nop per stage) is needed.  The other
-    // rows end up with sums nobody reads.
-    v += dpp_get<0x142, 0xf>(v);   // row_bcast15: rows 1, 3 += total of rows 0, 2
-    v += dpp_get<0x143, 0xf>(v);   // row_bcast31: row 3 += total of rows 0 + 1 -> lane 63 holds the sum
-    return read_lane(v, 63);
-}
-
-// Two independent sums interleaved (same latency chain as one).
-__device__ __forceinline__ void wave_sum2(double &a, double &b) {
-    a += dpp_get<0xB1, 0xf>(a);   b += dpp_get<0xB1, 0xf>(b);
-    a += dpp_get<0x4E, 0xf>(a);   b += dpp_get<0x4E, 0xf>(b);
-    a += dpp_get<0x141, 0xf>(a);  b += dpp_get<0x141, 0xf>(b);
-    a += dpp_get<0x140, 0xf>(a);  b += dpp_get<0x140, 0xf>(b);
-    a += dpp_get<0x142, 0xf>(a);  b += dpp_get<0x142, 0xf>(b);
-    a += dpp_get<0x143, 0xf>(a);  b += dpp_get<0x143, 0xf>(b);
-    a = read_lane(a, 63);
-    b = read_lane(b, 63);
-}
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory
-// queue (s_waitcnt vmcnt(0) before s_barrier), which turns a software prefetch issued before the
-// barrier into a wait for HBM at the barrier; kernels whose waves exchange data through LDS alone use
-// this instead and keep their global loads in flight.
-__device__ __forceinline__ void wg_lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// Order LDS traffic of ONE wave: lane-form writes before uniform (broadcast) reads.
-__device__ __forceinline__ void wave_lds_fence() {
-    // LDS operations of one wave execute in issue order, so wavefront scope (a pure
-    // compiler fence, no s_waitcnt) is enough and leaves global prefetches in flight.
-    // The fences name the LDS address space only, so global loads stay provably unclobbered
-    // (which is what lets hipcc turn wave-uniform row loads into s_load).
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // ------------------------------------------------------------------------------------
 // K0: generator rows + propagator rows
@@ -439,15 +392,6 @@ __global__ void __launch_bounds__(64 * NW) k_factor(const FactorArgs A) {
 // k_build2 writes u~, v~ (and E at reset rows); k_factor2 reads the row operands u~_i as
 // wave-uniform scalar loads (SGPR operands of v_fma_f64), so only w~ needs an LDS broadcast.
 // ------------------------------------------------------------------------------------
-// reset(n) = (n % block == 0) or cmax (t_n - t_{n-1}) > gap, with (block - 1) * gap = SC_SPAN: |log rho| <= SC_SPAN.
-// The streamed log-likelihood (gf_loglike_fused with GF_SWEEP_LONG_SPAN, one-wave sweeps only) may take
-// SC_SPAN_LONG: T~ then stays within e^+-2 SC_SPAN_LONG = e^+-256 of S, u~ / v~ / w~ / F~ within e^+-128 of the
-// unscaled rows, far inside FP64's e^+-708 for amplitudes and pivots within 1e+-100 (the host falls
-// back to SC_SPAN outside that range).  Every other route -- the time-parallel sweeps, the stored factor, the wide
-// kernels -- keeps SC_SPAN: their transition and solve kernels rebuild the reset rows from it.
-constexpr double SC_SPAN = 28.0;
-constexpr double SC_SPAN_LONG = 128.0;
-
 struct Build2Args {
     int64_t N, n_first;
     int Jr, Jc, ld, units, block;   // block: power of two, rows between forced resets
@@ -551,71 +495,6 @@ __global__ void __launch_bounds__(256) k_build2(const Build2Args A) {
             A.Vt[row + W + q] = 0.0;
         }
     }
-}
-
-// Sweeps over the ROWS register-resident rows of T with wave-uniform row operands read from
-// LDS (xa[i], xw[i]), software-pipelined: batches of 4 rows (2 + 2 ds_read_b128), SW_AHEAD
-// batches in flight ahead of the FMAs, so the LDS latency is paid once per sweep and not once
-// per read (hipcc otherwise parks every read right in front of its use).
-constexpr int SW_BR = 4, SW_AHEAD = 1;
-#ifndef GF_CHAIN_PRIO
-#define GF_CHAIN_PRIO 1
-#endif
-
-// issue the reads of the first SW_AHEAD batches (done early, under the reduction of the
-// previous row: the operands do not depend on it)
-template <int ROWS>
-__device__ __forceinline__ void sweep_preload(double (&ab)[SW_AHEAD + 1][SW_BR],
-                                              double (&wb)[SW_AHEAD + 1][SW_BR],
-                                              const double *xa, const double *xw) {
-    constexpr int NB = ROWS / SW_BR;
-#pragma unroll
-    for (int k = 0; k < SW_AHEAD && k < NB; ++k) {
-#pragma unroll
-        for (int r = 0; r < SW_BR; ++r) { ab[k][r] = xa[k * SW_BR + r]; wb[k][r] = xw[k * SW_BR + r]; }
-    }
-}
-
-//   RESET = false:  T_i += xw_i * q ;  acc += xa_i * T_i            (update + mat-vec)
-//   RESET = true :  T_i  = (T_i + xw_i * q) * (xa_i * el)          (fold pending, decay)
-template <int ROWS, bool RESET>
-__device__ __forceinline__ double sweep_run(double (&T)[ROWS], double (&ab)[SW_AHEAD + 1][SW_BR],
-                                            double (&wb)[SW_AHEAD + 1][SW_BR], const double *xa,
-                                            const double *xw, const double q, const double el) {
-    constexpr int BR = SW_BR, NB = ROWS / BR, AHEAD = SW_AHEAD;
-    static_assert(ROWS % BR == 0, "ROWS must be a multiple of 4");
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        if (k + AHEAD < NB) {
-#pragma unroll
-            for (int r = 0; r < BR; ++r) {
-                ab[(k + AHEAD) % (AHEAD + 1)][r] = xa[(k + AHEAD) * BR + r];
-                wb[(k + AHEAD) % (AHEAD + 1)][r] = xw[(k + AHEAD) * BR + r];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const int c = k % (AHEAD + 1);
-        if constexpr (RESET) {
-#pragma unroll
-            for (int r = 0; r < BR; ++r)
-                T[k * BR + r] = fma(wb[c][r], q, T[k * BR + r]) * (ab[c][r] * el);
-        } else {
-            T[k * BR + 0] = fma(wb[c][0], q, T[k * BR + 0]);
-            T[k * BR + 1] = fma(wb[c][1], q, T[k * BR + 1]);
-            T[k * BR + 2] = fma(wb[c][2], q, T[k * BR + 2]);
-            T[k * BR + 3] = fma(wb[c][3], q, T[k * BR + 3]);
-            acc0 = fma(ab[c][0], T[k * BR + 0], acc0);
-            acc1 = fma(ab[c][1], T[k * BR + 1], acc1);
-            acc2 = fma(ab[c][2], T[k * BR + 2], acc2);
-            acc3 = fma(ab[c][3], T[k * BR + 3], acc3);
-            // pin the partial sums to this batch: LLVM otherwise sinks all the mat-vec FMAs
-            // to the end of the sweep and keeps every row operand alive (register blow-up)
-            asm volatile("" : "+v"(acc0), "+v"(acc1), "+v"(acc2), "+v"(acc3));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return (acc0 + acc2) + (acc1 + acc3);
 }
 
 // Per row n (scaled coordinates; r = v~ - tmp, so w~ = r/d and d w~ = r):
@@ -1138,25 +1017,6 @@ k_factor3(const int64_t N, const int64_t n_first, const int64_t chunk_len, const
 // state layout in memory and results as k_factor3; needs Jr = 0 (every gadfly kernel with
 // Q > 1/2) and Jc <= 31 (block 31 carries the pad column 62 and the forward solve in column 63).
 // ------------------------------------------------------------------------------------
-// The row vectors (u~, v~, r, q) live one column per lane as in k_factor3 -- lane (g, c) owns column
-// 2c + g -- while the state is tiled two columns x half the rows per lane.  Two exchanges between
-// the half-waves connect the two layouts, each a pair of v_permlane32_swap (which swaps the upper
-// half of its first operand with the lower half of its second):
-//   own_column_sum(a, b): a, b = this half-wave's partial sums of columns 2c, 2c + 1; returns the
-//     full sum of the lane's OWN column (lower half: a_L + a_U, upper half: b_L + b_U);
-//   both_halves(x, lo, up): lo = x of lane c, up = x of lane c + 32, in both lanes.
-__device__ __forceinline__ double own_column_sum(const double a, const double b) {
-    const auto l = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
-    const auto h = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
-    return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-__device__ __forceinline__ void both_halves(const double x, double &lo, double &up) {
-    const auto l = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(x), false, false);
-    const auto h = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(x), false, false);
-    lo = __hiloint2double(h[0], l[0]);
-    up = __hiloint2double(h[1], l[1]);
-}
-
 // One LDS-DMA instruction (global_load_lds_dwordx4): lane l copies 16 bytes from ITS OWN global address to
 // LDS byte `lds_byte` + 16 l -- no VGPR destination, so a deep prefetch costs LDS instead of registers.
 // hipcc does not count it: completion is waited for with vm_wait (vector-memory operations retire in
@@ -1169,56 +1029,6 @@ __device__ __forceinline__ void glds16(const void *gsrc, const unsigned lds_byte
 }
 template <int CNT>
 __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(CNT) : "memory"); }
-
-constexpr int S7_AHEAD = 1;         // batches (one row pair = 8 FMAs + 2 reads) of LDS look-ahead
-
-template <int ROWS>
-__device__ __forceinline__ void sweep7_preload(double2 (&ub)[S7_AHEAD + 1], double2 (&wb)[S7_AHEAD + 1],
-                                               const double2 *pu, const double2 *pw) {
-#pragma unroll
-    for (int k = 0; k < S7_AHEAD && k < ROWS / 4; ++k) { ub[k] = pu[2 * k]; wb[k] = pw[2 * k]; }
-}
-
-// T[2k + s][e] is row 4k + 2g + s, column 2c + e.  pu / pw point at this half-wave's first row pair.
-//   RESET = false:  T += w q^T ;  acc += u^T T         (update + mat-vec, acc[e][s])
-//   RESET = true :  T  = (T + w q^T) * (e_row el_col)  (fold pending, decay; pu = the row decays)
-template <int ROWS, bool RESET>
-__device__ __forceinline__ void sweep7_run(double (&T)[ROWS / 2][2], double2 (&ub)[S7_AHEAD + 1],
-                                           double2 (&wb)[S7_AHEAD + 1], const double2 *pu,
-                                           const double2 *pw, const double q0, const double q1,
-                                           const double el0, const double el1, double &o0, double &o1) {
-    constexpr int NK = ROWS / 4, AHEAD = S7_AHEAD;
-    static_assert(ROWS % 4 == 0, "ROWS must be a multiple of 4");
-    double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        if (k + AHEAD < NK) {
-            ub[(k + AHEAD) % (AHEAD + 1)] = pu[2 * (k + AHEAD)];
-            wb[(k + AHEAD) % (AHEAD + 1)] = pw[2 * (k + AHEAD)];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const double2 u = ub[k % (AHEAD + 1)], w = wb[k % (AHEAD + 1)];
-        if constexpr (RESET) {
-            T[2 * k][0] = fma(w.x, q0, T[2 * k][0]) * (u.x * el0);
-            T[2 * k][1] = fma(w.x, q1, T[2 * k][1]) * (u.x * el1);
-            T[2 * k + 1][0] = fma(w.y, q0, T[2 * k + 1][0]) * (u.y * el0);
-            T[2 * k + 1][1] = fma(w.y, q1, T[2 * k + 1][1]) * (u.y * el1);
-        } else {
-            T[2 * k][0] = fma(w.x, q0, T[2 * k][0]);
-            T[2 * k][1] = fma(w.x, q1, T[2 * k][1]);
-            T[2 * k + 1][0] = fma(w.y, q0, T[2 * k + 1][0]);
-            T[2 * k + 1][1] = fma(w.y, q1, T[2 * k + 1][1]);
-            a00 = fma(u.x, T[2 * k][0], a00);
-            a01 = fma(u.x, T[2 * k][1], a01);
-            a10 = fma(u.y, T[2 * k + 1][0], a10);
-            a11 = fma(u.y, T[2 * k + 1][1], a11);
-            asm volatile("" : "+v"(a00), "+v"(a01), "+v"(a10), "+v"(a11));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    o0 = a00 + a10;
-    o1 = a01 + a11;
-}
 
 // ROWSTORE = false: no row is stored (r_out, Ut_out, Wt_out, de_out all null: the streamed log-likelihood
 // and the plain final pass) -- their tests, pointer arithmetic and exec-mask switches leave the row loop
@@ -5720,247 +5530,6 @@ __global__ void k_add2(int64_t M, const double *work, double *mu) {
 }
 
 // ------------------------------------------------------------------------------------
-// Power spectra of light curves / prior draws and their binning: the step
-// after `sample` in the reference's own hot-path test (gadfly/tests/test_core.py:29-34).  The
-// transform itself is hipFFT's (a plain library FFT); these two kernels are what the reference
-// does around it in numpy / scipy.binned_statistic.
-// ------------------------------------------------------------------------------------
-// power[r][k] = |X[r][first + k]|^2 * norm      (PowerSpectrum._fft, psd.py:566-587)
-// X interleaved complex [R][M]; re*re + im*im without contraction, as numpy forms it.
-__global__ void __launch_bounds__(256)
-k_psd_power(const int64_t M, const int64_t Mout, const int64_t first, const double norm,
-            const double2 *__restrict__ spec, double *__restrict__ power) {
-#pragma clang fp contract(off)      // plain operators under this pragma: HIP's __dmul_rn / __dadd_rn wrappers still contract
-    const size_t r = blockIdx.y;
-    const double2 *X = spec + r * (size_t)M + first;
-    double *P = power + r * (size_t)Mout;
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < Mout; k += (int64_t)gridDim.x * 256) {
-        const double2 v = X[k];
-        P[k] = (v.x * v.x + v.y * v.y) * norm;
-    }
-}
-
-// sum over the 256 threads of a workgroup, result in every thread (fixed shape: deterministic)
-__device__ __forceinline__ double wg_sum256(double v, double *red) {
-    v = wave_sum(v);
-    __syncthreads();                                // red may still be read from the last call
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// One workgroup per (bin, series): the bin's points are the contiguous range [start[b], start[b+1])
-// of the ascending frequency axis x.  bin_power_spectrum's two statistics (psd.py:186-227):
-//   stat = trapz(y, x) / (x_last - x_first)                          (one point: y itself)
-//   err  = std(y) / sqrt(n) * mean(x) / (x_last - x_first) / constant (one point: y itself)
-// and NaN for an empty bin (scipy.stats.binned_statistic's value for a failing statistic).
-__global__ void __launch_bounds__(256)
-k_psd_bin(const int64_t M, const int nb, const double *__restrict__ x,
-          const double *__restrict__ power, const int64_t *__restrict__ start,
-          const double constant, double *__restrict__ stat, double *__restrict__ err) {
-    __shared__ double red[4];
-    const int b = blockIdx.x;
-    const size_t r = blockIdx.y;
-    const int64_t s = start[b], e = start[b + 1], n = e - s;
-    const double *y = power + r * (size_t)M;
-    double *st = stat + r * (size_t)nb + b, *er = err + r * (size_t)nb + b;
-    if (n <= 0) {
-        if (threadIdx.x == 0) { *st = __builtin_nan(""); *er = __builtin_nan(""); }
-        return;
-    }
-    const double span = x[e - 1] - x[s];
-    if (n == 1 || !(span > 0.0)) {
-        if (threadIdx.x == 0) { *st = y[s]; *er = y[s]; }
-        return;
-    }
-    double tz = 0.0, sy = 0.0, sx = 0.0;
-    for (int64_t i = s + threadIdx.x; i < e; i += 256) {
-        const double yi = y[i], xi = x[i];
-        sy += yi;
-        sx += xi;
-        if (i + 1 < e) tz += (x[i + 1] - xi) * (yi + y[i + 1]) * 0.5;
-    }
-    tz = wg_sum256(tz, red);
-    sy = wg_sum256(sy, red);
-    sx = wg_sum256(sx, red);
-    const double mean = sy / (double)n;
-    double ss = 0.0;
-    for (int64_t i = s + threadIdx.x; i < e; i += 256) {
-        const double dv = y[i] - mean;
-        ss = fma(dv, dv, ss);
-    }
-    ss = wg_sum256(ss, red);
-    if (threadIdx.x == 0) {
-        *st = tz / span;
-        *er = sqrt(ss / (double)n) / sqrt((double)n) * (sx / (double)n) / span / constant;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// Light-curve ingestion: fill the missing cadences of an otherwise evenly
-// sampled series by linear interpolation -- interpolate_missing_data (gadfly/interp.py:6-60), what
-// the reference runs before every FFT power spectrum (psd.py:495, :531).  Times ascending.
-//   cadence index c_i = rint((t_i - t_0) / dt)  (or the given cadence numbers, minus the first);
-//   after point i the indices c_i + 1 .. c_{i+1} - 1 are missing: grid time x = t_0 + index * dt,
-//   flux np.interp(x, t, f) = slope * (x - t_j) + f_j on the interval that holds x,
-// each product and sum rounded on its own, as numpy forms them (bit-identical results).
-// Steps: counts (1 + gap) per point, an exclusive scan, then the merge by time (below).
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t cadence_index(const double *t, const int64_t *cad, int64_t i,
-                                                 double t0, double dt) {
-#pragma clang fp contract(off)
-    return cad ? (cad[i] - cad[0]) : (int64_t)rint((t[i] - t0) / dt);
-}
-
-constexpr int SCAN_PER_WG = 2048;       // elements per 256-thread workgroup (8 per thread)
-
-// counts[i] = 1 + number of cadences missing after point i; block_sums[wg] = sum over the workgroup's
-// SCAN_PER_WG elements; offsets[i] = exclusive scan of counts WITHIN the workgroup
-__global__ void __launch_bounds__(256)
-k_interp_count(const int64_t N, const double *__restrict__ t, const int64_t *__restrict__ cad,
-               const double t0, const double dt, int64_t *__restrict__ offsets,
-               int64_t *__restrict__ block_sums) {
-    __shared__ int64_t part[256];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_PER_WG + (int64_t)threadIdx.x * 8;
-    int64_t loc[8], run = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int64_t i = base + k;
-        int64_t cnt = 0;
-        if (i < N) {
-            cnt = 1;
-            if (i + 1 < N) {
-                const int64_t gap = cadence_index(t, cad, i + 1, t0, dt) - cadence_index(t, cad, i, t0, dt) - 1;
-                if (gap > 0) cnt += gap;
-            }
-        }
-        loc[k] = run;
-        run += cnt;
-    }
-    part[threadIdx.x] = run;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {           // Hillis-Steele inclusive scan of the 256 partials
-        const int64_t v = (threadIdx.x >= (unsigned)off) ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const int64_t before = part[threadIdx.x] - run;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-        if (base + k < N) offsets[base + k] = before + loc[k];
-    if (threadIdx.x == 255) block_sums[blockIdx.x] = part[255];
-}
-
-// exclusive scan of the block sums in place (one workgroup, any count); total -> offsets[N]
-__global__ void __launch_bounds__(256)
-k_interp_scan_top(const int64_t nblocks, const int64_t N, int64_t *__restrict__ block_sums,
-                  int64_t *__restrict__ offsets) {
-    __shared__ int64_t part[256];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < nblocks; b0 += 256) {
-        const int64_t i = b0 + threadIdx.x;
-        const int64_t v = (i < nblocks) ? block_sums[i] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const int64_t u = (threadIdx.x >= (unsigned)off) ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < nblocks) block_sums[i] = carry + part[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += part[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) offsets[N] = carry;
-}
-
-__global__ void __launch_bounds__(256)
-k_interp_offsets(const int64_t N, const int64_t *__restrict__ block_sums, int64_t *__restrict__ offsets) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < N) offsets[i] += block_sums[i / SCAN_PER_WG];
-}
-
-// The filled series is the reference's merge BY TIME of the input points and the missing cadences'
-// grid times t_0 + m dt (interp.py:56-59).  With cadence numbers given, dt is a median and the grid
-// drifts against the (e.g. barycentric) time stamps, so a missing cadence's grid time need not lie
-// between its neighbours' time stamps: positions come from ranks, not from the gap a cadence sits in.
-//   input point i   -> i + #{missing m : x_m <  t_i}
-//   missing cadence -> (its rank among the missing) + #{i : t_i <= x_m}      (ties: input points first)
-__device__ __forceinline__ double grid_time(const double t0, const int64_t m, const double dt) {
-#pragma clang fp contract(off)
-    return t0 + (double)m * dt;
-}
-
-// G[i] = offsets[i] - i = number of missing cadences before point i's gap
-__global__ void __launch_bounds__(256)
-k_interp_points(const int64_t N, const double *__restrict__ t, const double *__restrict__ f,
-                const int64_t *__restrict__ cad, const double t0, const double dt,
-                const int64_t *__restrict__ offsets, double *__restrict__ t_out, double *__restrict__ f_out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const double ti = t[i];
-    // M = smallest cadence index whose grid time is >= t_i (monotone in m: settle it exactly)
-    int64_t M = (int64_t)floor((ti - t0) / dt) - 1;
-    while (grid_time(t0, M, dt) >= ti) --M;
-    while (grid_time(t0, M, dt) < ti) ++M;
-    // j = last input point with cadence index < M; missing below M = G[j] + those of j's gap below M
-    int64_t lo = 0, hi = N;                         // first point with index >= M
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (cadence_index(t, cad, mid, t0, dt) < M) lo = mid + 1; else hi = mid;
-    }
-    int64_t before = 0;
-    if (lo > 0) {
-        const int64_t j = lo - 1;
-        const int64_t gap = offsets[j + 1] - offsets[j] - 1;
-        int64_t part = M - cadence_index(t, cad, j, t0, dt) - 1;
-        part = part < 0 ? 0 : (part > gap ? gap : part);
-        before = (offsets[j] - j) + part;
-    }
-    t_out[i + before] = ti;
-    f_out[i + before] = f[i];
-}
-
-__global__ void __launch_bounds__(256)
-k_interp_missing(const int64_t N, const double *__restrict__ t, const double *__restrict__ f,
-                 const int64_t *__restrict__ cad, const double t0, const double dt,
-                 const int64_t *__restrict__ offsets, double *__restrict__ t_out, double *__restrict__ f_out) {
-#pragma clang fp contract(off)      // numpy rounds the product and the sum separately (no FMA)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const int64_t G = offsets[i] - i, gap = offsets[i + 1] - offsets[i] - 1;
-    if (gap <= 0) return;
-    const int64_t ci = cadence_index(t, cad, i, t0, dt);
-    int64_t p = i + 1;                              // #{points with t <= x}: grows with k, starts near i
-    for (int64_t k = 1; k <= gap; ++k) {
-        const double x = grid_time(t0, ci + k, dt);
-        if (p > 0 && t[p - 1] > x) {                // the grid has drifted back past point p-1: search below
-            int64_t lo = 0, hi = p - 1;
-            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (t[mid] <= x) lo = mid + 1; else hi = mid; }
-            p = lo;
-        }
-        while (p < N && t[p] <= x) ++p;
-        // np.interp: clamped outside the series, the sample itself on a knot, else the chord
-        double v;
-        if (p == 0) v = f[0];
-        else if (p == N) v = f[N - 1];
-        else {
-            const int64_t j = p - 1;
-            const double slope = (f[j + 1] - f[j]) / (t[j + 1] - t[j]);
-            v = slope * (x - t[j]) + f[j];
-        }
-        const int64_t o = (G + k - 1) + p;
-        t_out[o] = x;
-        f_out[o] = v;
-    }
-}
-
-// ------------------------------------------------------------------------------------
 // k_factor2w: the block-scaled recurrence of k_factor2 for widths beyond one wave (64 < W <= 256),
 // in k_factor's multi-wave mapping.  Scaled coordinates turn the per-row decay
 // S <- P (S + ...) P (two multiplies per element and row) into a rescaling at reset rows only:
@@ -6230,75 +5799,13 @@ int dispatch_factorw(const FactorWArgs &A, const FactorWPtrs &P, int W, int grid
     return -1;
 }
 
-// Kernels that exist per value of an int template argument: dispatch_among calls f with
-// std::integral_constant<int, V> for the V that equals v, and says whether there was one.
-template <int... V, class F>
-constexpr bool dispatch_among(int v, F &&f) {
-    return ((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
-}
-// the one-wave kernels' row count: the width rounded up to a multiple of 4 (the ladder is written here alone)
-template <class F>
-constexpr bool dispatch_rows(int rows, F &&f) {
-    return dispatch_among<4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64>(rows, f);
-}
-// A wrong instance for a width is a fault on the device, not a failed assertion: every multiple of 4 in 4 .. 64
-// selects the instance of that many rows, and no other count (0, 2 and 68 among them) selects any.
-constexpr bool dispatch_rows_exact() {
-    for (int rows = -4; rows <= 72; ++rows) {
-        int got = -1;
-        dispatch_rows(rows, [&](auto r) { got = decltype(r)::value; });
-        if (got != ((rows >= 4 && rows <= 64 && rows % 4 == 0) ? rows : -1)) return false;
-    }
-    return true;
-}
-static_assert(dispatch_rows_exact(), "dispatch_rows: rows must select the instance R == rows, in 4, 8, .., 64 only");
-
-// Argument checks the entry points share: 0, or -1 with "<who>: ..." recorded.
-int check_block(const char *who, int block) {
-    if (block < 1 || block > 64 || (block & (block - 1)))
-        return gf_internal_error(-1, "%s: block=%d must be a power of two in 1..64", who, block);
-    return 0;
-}
-int check_n_first(const char *who, int64_t n_first, int block) {        // (behind check_block)
-    if (n_first < 0 || (n_first % block) != 0)
-        return gf_internal_error(-1, "%s: n_first=%lld must be a non-negative multiple of block=%d", who,
-                                 (long long)n_first, block);
-    return 0;
-}
-// nch chunks of chunk_len rows cover the N rows, none of them empty; more than one chunk: chunk_len is a multiple
-// of `quantum` (the sweeps: their scaling block; the transitions: 64; 1: any length)
-int check_chunking(const char *who, int64_t N, int64_t chunk_len, int nch, int quantum) {
-    if (nch < 1 || chunk_len < 1 || (nch > 1 && (chunk_len % quantum) != 0) || (int64_t)nch * chunk_len < N
-        || (int64_t)(nch - 1) * chunk_len >= N)
-        return gf_internal_error(-1, "%s: bad chunking (chunk_len=%lld, nch=%d)", who, (long long)chunk_len, nch);
-    return 0;
-}
-int check_chunk_range(const char *who, int chunk_first, int chunk_count, int nch) {
-    if (chunk_first < 0 || chunk_count < 0 || chunk_first + chunk_count > nch)
-        return gf_internal_error(-1, "%s: bad chunk range (first=%d, count=%d)", who, chunk_first, chunk_count);
-    return 0;
-}
-int check_ld(const char *who, int W, int ld) {
-    if (ld < W || (ld & 15))
-        return gf_internal_error(-1, "%s: ld=%d must be a multiple of 16 and >= W=%d", who, ld, W);
-    return 0;
-}
-int check_width_ld(const char *who, int W, int ld) {
-    if (W < 1 || W > GF_MAX_WIDTH)
-        return gf_internal_error(-1, "%s: width %d unsupported (max %d)", who, W, GF_MAX_WIDTH);
-    return check_ld(who, W, ld);
-}
-// the reset gap of a sweep with this scaling block (`variant`: its GF_SWEEP_LONG_SPAN bit)
-double sweep_gap(int block, int variant) {
-    return (block > 1) ? ((variant & GF_SWEEP_LONG_SPAN) ? SC_SPAN_LONG : SC_SPAN) / (double)(block - 1) : 0.0;
-}
 
 }  // namespace
 
 // ======================================================================================
 // C-ABI
 // ======================================================================================
-// (shared with gadfly_dense.hip: `which` = 0, 1 here, 2 there)
+// (shared with gadfly_dense.hip: `which` = 0, 1 here, 2 and 3 there)
 bool gf_internal_lds_opt_in(int which, hipStream_t st, const void *const *funcs, int nfuncs, size_t bytes) {
     static std::atomic<bool> done[4][64];
     if (which < 0 || which >= 4) return false;
@@ -7246,66 +6753,6 @@ int gf_cross_covariance(int B, int64_t N, int R, int Jr, int Jc,
     if (RT == 64) GF_CX(64); else if (RT == 32) GF_CX(32); else if (RT == 16) GF_CX(16); else GF_CX(8);
 #undef GF_CX
     return check_launch("gf_cross_covariance");
-}
-
-int64_t gf_interp_work(int64_t N) {
-    return (N < 1) ? 0 : (N + SCAN_PER_WG - 1) / SCAN_PER_WG;
-}
-
-int gf_interp_plan(int64_t N, const double *t, const int64_t *cadences, double dt,
-                   int64_t *offsets, int64_t *work, void *stream) {
-    if (N < 1) return gf_internal_error(-1, "gf_interp_plan: empty series (N=%lld)", (long long)N);
-    if (!t || !offsets || !work) return gf_internal_error(-1, "gf_interp_plan: null pointer");
-    if (!(dt > 0.0)) return gf_internal_error(-1, "gf_interp_plan: the cadence must be positive");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t nb = gf_interp_work(N);
-    double t0;
-    if (hipMemcpyAsync(&t0, t, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return gf_internal_error(-1, "gf_interp_plan: cannot read the first time");
-    hipLaunchKernelGGL(k_interp_count, dim3((unsigned)nb), dim3(256), 0, st, N, t, cadences, t0, dt, offsets, work);
-    hipLaunchKernelGGL(k_interp_scan_top, dim3(1), dim3(256), 0, st, nb, N, work, offsets);
-    hipLaunchKernelGGL(k_interp_offsets, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, work, offsets);
-    return check_launch("gf_interp_plan");
-}
-
-int gf_interp_fill(int64_t N, const double *t, const double *f, const int64_t *cadences, double dt,
-                   const int64_t *offsets, double *t_out, double *f_out, void *stream) {
-    if (N < 1) return gf_internal_error(-1, "gf_interp_fill: empty series (N=%lld)", (long long)N);
-    if (!t || !f || !offsets || !t_out || !f_out) return gf_internal_error(-1, "gf_interp_fill: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    double t0;
-    if (hipMemcpyAsync(&t0, t, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return gf_internal_error(-1, "gf_interp_fill: cannot read the first time");
-    hipLaunchKernelGGL(k_interp_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, t, f, cadences,
-                       t0, dt, offsets, t_out, f_out);
-    hipLaunchKernelGGL(k_interp_missing, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, t, f, cadences,
-                       t0, dt, offsets, t_out, f_out);
-    return check_launch("gf_interp_fill");
-}
-
-int gf_psd_power(int R, int64_t M, int64_t first, double norm, const double *spec,
-                 double *power, void *stream) {
-    if (R < 1 || M < 1 || first < 0 || first >= M) return gf_internal_error(-1, "gf_psd_power: bad shape (M=%lld, first=%lld)", (long long)M, (long long)first);
-    if (!spec || !power) return gf_internal_error(-1, "gf_psd_power: null pointer");
-    if (R > 65535) return gf_internal_error(-1, "gf_psd_power: more than 65535 series");
-    const int64_t Mout = M - first;
-    int64_t blocks = (Mout + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_psd_power, dim3((unsigned)blocks, R), dim3(256), 0, (hipStream_t)stream, M, Mout,
-                       first, norm, (const double2 *)spec, power);
-    return check_launch("gf_psd_power");
-}
-
-int gf_psd_bin(int R, int64_t M, int nb, const double *x, const double *power,
-               const int64_t *start, double constant, double *stat, double *err, void *stream) {
-    if (R < 1 || M < 1 || nb < 1) return gf_internal_error(-1, "gf_psd_bin: bad shape (M=%lld, bins=%d)", (long long)M, nb);
-    if (!x || !power || !start || !stat || !err) return gf_internal_error(-1, "gf_psd_bin: null pointer");
-    if (R > 65535) return gf_internal_error(-1, "gf_psd_bin: more than 65535 series");
-    hipLaunchKernelGGL(k_psd_bin, dim3(nb, R), dim3(256), 0, (hipStream_t)stream, M, nb, x, power, start,
-                       constant, stat, err);
-    return check_launch("gf_psd_bin");
 }
 
 // chunking of the conditional-mean sweeps: ~2048 waves over (problem, direction, chunk), chunks of

@@ -57,7 +57,7 @@ __host__ __device__ inline int64_t sp_work(int64_t M, int J) {
     return (int64_t)SP_COEF * J + sp_tiles(M) * (SP_SCAL + 3 * (int64_t)J);
 }
 
-// fixed-shape tree sum over the 64 lanes, broadcast (the tree of gadfly_hip.hip's wave_sum)
+// fixed-shape tree sum over the 64 lanes, broadcast (the tree of gf_wave.h's wave_sum)
 __device__ __forceinline__ double sp_wave_sum(double v) {
     v += dpp_get<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
     v += dpp_get<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]

@@ -92,4 +92,65 @@ __device__ __forceinline__ void gj_update(double (&R)[N], const double f, const 
     }, std::make_integer_sequence<int, (NC - L0 + GJ_BATCH - 1) / GJ_BATCH>{});
 }
 
+
+// ------------------------------------------------------------------------------------
+// wave-level primitives (64 lanes, DPP; no LDS traffic)
+// ------------------------------------------------------------------------------------
+// A wave-uniform index made opaque to the optimiser (it stays in SGPRs, at no cost): `p[opaque(i)]`
+// with a loop-invariant per-lane pointer p is then addressed as p + i inside the branch that uses
+// it, instead of becoming one more per-lane 64-bit pointer that loop strength reduction advances
+// with a vector add on EVERY iteration, taken or not.
+__device__ __forceinline__ size_t opaque_uniform(size_t i) {
+    asm volatile("" : "+s"(i));
+    return i;
+}
+
+// Fixed-shape tree sum over the 64 lanes, result broadcast to every lane (deterministic).
+__device__ __forceinline__ double wave_sum(double v) {
+    v += dpp_get<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
+    v += dpp_get<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
+    v += dpp_get<0x141, 0xf>(v);   // row_half_mirror
+    v += dpp_get<0x140, 0xf>(v);   // row_mirror       -> every lane holds its 16-lane row sum
+    // the two broadcasts only matter for row 3 (rows 1, 3 and rows 2, 3 are what LLVM's own
+    // reductions enable with row_mask 0xa / 0xc); with all rows enabled and bound_ctrl every lane is
+    // written, so no zero-initialised destination (2 v_mov + s_nop per stage) is needed.  The other
+    // rows end up with sums nobody reads.
+    v += dpp_get<0x142, 0xf>(v);   // row_bcast15: rows 1, 3 += total of rows 0, 2
+    v += dpp_get<0x143, 0xf>(v);   // row_bcast31: row 3 += total of rows 0 + 1 -> lane 63 holds the sum
+    return read_lane(v, 63);
+}
+
+// Two independent sums interleaved (same latency chain as one).
+__device__ __forceinline__ void wave_sum2(double &a, double &b) {
+    a += dpp_get<0xB1, 0xf>(a);   b += dpp_get<0xB1, 0xf>(b);
+    a += dpp_get<0x4E, 0xf>(a);   b += dpp_get<0x4E, 0xf>(b);
+    a += dpp_get<0x141, 0xf>(a);  b += dpp_get<0x141, 0xf>(b);
+    a += dpp_get<0x140, 0xf>(a);  b += dpp_get<0x140, 0xf>(b);
+    a += dpp_get<0x142, 0xf>(a);  b += dpp_get<0x142, 0xf>(b);
+    a += dpp_get<0x143, 0xf>(a);  b += dpp_get<0x143, 0xf>(b);
+    a = read_lane(a, 63);
+    b = read_lane(b, 63);
+}
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory
+// queue (s_waitcnt vmcnt(0) before s_barrier), which turns a software prefetch issued before the
+// barrier into a wait for HBM at the barrier; kernels whose waves exchange data through LDS alone use
+// this instead and keep their global loads in flight.
+__device__ __forceinline__ void wg_lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// Order LDS traffic of ONE wave: lane-form writes before uniform (broadcast) reads.
+__device__ __forceinline__ void wave_lds_fence() {
+    // LDS operations of one wave execute in issue order, so wavefront scope (a pure
+    // compiler fence, no s_waitcnt) is enough and leaves global prefetches in flight.
+    // The fences name the LDS address space only, so global loads stay provably unclobbered
+    // (which is what lets hipcc turn wave-uniform row loads into s_load).
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
 }  // namespace

@@ -165,9 +165,10 @@ def steady_tail(lines, rows, kernel="k_steady_tail"):
               f"{g['mfma'] / 16:.2f} MFMA, {dyn['lds'] + g['lds'] / 16:.0f} LDS")
 
 
-def functions(lines):
+def functions(lines, twice=None):
     """name -> instruction lines of every function of a listing, with the per-function label numbers taken out (a
-    function added in front renumbers the labels of all that follow)."""
+    function added in front renumbers the labels of all that follow).  `twice`, if given, collects the names that
+    occur more than once (listings of several translation units, concatenated)."""
     out, name, body = {}, None, []
     for ln in lines:
         if name is None:
@@ -175,6 +176,8 @@ def functions(lines):
             if m:
                 name, body = m.group(1), []
         elif ln.startswith(".Lfunc_end"):
+            if twice is not None and name in out:
+                twice.append(name)
             out[name], name = body, None
         else:
             s = ln.split(";")[0].strip()
@@ -185,10 +188,15 @@ def functions(lines):
 
 def compare(lines, other):
     """Which kernels' instructions differ between two listings (registers included: the operands are compared)."""
-    a, b = functions(lines), functions(other)
+    twice_a, twice_b = [], []
+    a, b = functions(lines, twice_a), functions(other, twice_b)
     changed = sorted(k for k in a.keys() & b.keys() if a[k] != b[k])
     print(f"{len(a)} functions in this listing, {len(b)} in the other; {len(a.keys() & b.keys())} in both, "
           f"{len(changed)} of them differ")
+    for k in sorted(twice_a):
+        print(f"  twice in this listing: {k}")
+    for k in sorted(twice_b):
+        print(f"  twice in the other: {k}")
     for k in changed:
         print(f"  differs: {k}")
     for k in sorted(a.keys() - b.keys()):
