@@ -23,7 +23,8 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_seri
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
            os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip"),
-           os.path.join(CSRC, "gadfly_lsfft.hip"), os.path.join(CSRC, "gadfly_gradtp.hip")]
+           os.path.join(CSRC, "gadfly_lsfft.hip"), os.path.join(CSRC, "gadfly_gradtp.hip"),
+           os.path.join(CSRC, "gadfly_detrend.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -35,6 +36,7 @@ GF_GRAD_MAX_WIDTH = 63          # gf_loglike_grad: one wave per problem
 GF_GRAD_WORKSPACE_BYTES = 16 << 30   # default cap on gf_loglike_grad's workspace per call (batches run in groups)
 GF_SOLVE_MAX_WIDTH = 63         # gf_solve_batch: one wave per problem (kernel and component alike)
 GF_SOLVE_WORKSPACE_BYTES = 16 << 30  # default cap on gf_solve_batch's workspace per call
+GF_DETREND_MAX_ORDER = 8        # gf_poly_normalise: Legendre polynomials P_0 .. P_8
 
 _lib = None
 
@@ -167,6 +169,12 @@ SIGNATURES = {
     "gf_spectral_fisher_slab": (_int, []),
     "gf_spectral_fisher_work": (_i64, [_int, _i64, _int]),
     "gf_spectral_fisher": (_int, [_int, _i64, _int, _int] + [_vp] * 6 + [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_vp]),
+    "gf_seg_median": (_int, [_int, _vp, _vp, _vp, _int, _vp, _vp]),
+    "gf_sigma_clip": (_int, [_int, _vp, _vp, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp]),
+    "gf_seg_compact": (_int, [_int] + [_vp] * 7 + [_vp]),
+    "gf_seg_diff": (_int, [_int, _vp, _vp, _vp, _vp]),
+    "gf_poly_normalise": (_int, [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "gf_seg_ppm": (_int, [_int] + [_vp] * 4 + [_vp]),
 }
 
 

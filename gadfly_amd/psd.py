@@ -464,16 +464,16 @@ class PowerSpectrum:
         light curve: ``method='fft'`` for an evenly sampled one, ``method='lomb-scargle'`` (the
         time axis ``jd * day`` in 1/uHz, see :meth:`from_lomb_scargle`; ``ls_method="nufft"`` picks its
         non-uniform FFT route) for a gapped one.
-        Detrending / gap interpolation (psd.py:474-535) needs lightkurve and stays with the
-        reference.
+        Detrending / gap interpolation (psd.py:474-535) works on lightkurve objects there; on plain arrays it is
+        :meth:`from_quarters`.
         """
         if method.lower() not in ("fft", "lomb-scargle"):
             raise ValueError(f'PowerSpectrum.from_lightcurve was given method="{method}", but it '
                              "must be one of: ['fft', 'lomb-scargle'].")
         if detrend:
             raise NotImplementedError(
-                "only detrend=False runs on the device; detrending needs lightkurve "
-                "(reference psd.py:474-535)")
+                "only detrend=False runs on the device for light-curve objects (reference psd.py:474-535 needs "
+                "lightkurve); PowerSpectrum.from_quarters detrends raw (times, flux) arrays")
         time = light_curve.time
         jd = np.asarray(getattr(time, "jd", time), dtype=np.float64)
         meta = getattr(light_curve, "meta", None) or {}
@@ -484,6 +484,34 @@ class PowerSpectrum:
         d = np.median(np.diff(jd)) * 86400.0 / _units.SECONDS_PER_INVERSE_UHZ
         return cls.from_flux(light_curve.flux, d, include_zero_freq=include_zero_freq,
                              name=meta.get("name", name))
+
+    @classmethod
+    def from_quarters(cls, quarters, method="fft", include_zero_freq=False, name=None, ls_method="direct",
+                      **prepare_kwargs):
+        """Power spectrum of one star's raw observing quarters, a list of ``(times [d], flux)`` pairs: the
+        ``detrend=True`` branch of the reference (psd.py:482-564) on plain arrays.  The quarters are clipped,
+        detrended and stitched by :func:`gadfly_amd.prepare_quarters` (``prepare_kwargs``: its options but ``fill``)
+        -- gap-filled for ``method='fft'``, left gapped for ``method='lomb-scargle'`` (time axis ``jd * day`` in
+        1/uHz as in :meth:`from_light_curve`; ``ls_method`` picks :meth:`from_lomb_scargle`'s route).
+        ``detrended_lc`` is ``(times [d], flux_ppm)``."""
+        from .detrend import prepare_quarters
+        if method.lower() not in ("fft", "lomb-scargle"):
+            raise ValueError(f'PowerSpectrum.from_quarters was given method="{method}", but it '
+                             "must be one of: ['fft', 'lomb-scargle'].")
+        if "fill" in prepare_kwargs or "return_device" in prepare_kwargs:
+            raise TypeError("from_quarters sets fill from the method and returns host arrays")
+        fft = method.lower() == "fft"
+        jd, flux, cadence = prepare_quarters(quarters, fill=fft, **prepare_kwargs)
+        device = prepare_kwargs.get("device")
+        if fft:
+            d = cadence * 86400.0 / _units.SECONDS_PER_INVERSE_UHZ
+            ps = cls.from_flux(flux, d, include_zero_freq=include_zero_freq, name=name, device=device)
+        else:
+            t = jd * 86400.0 / _units.SECONDS_PER_INVERSE_UHZ
+            ps = cls.from_lomb_scargle(t, flux, include_zero_freq=include_zero_freq, name=name, device=device,
+                                       method=ls_method)
+        ps.detrended_lc = (jd, flux)
+        return ps
 
 
 def bin_power_spectrum(power_spectrum, bins=None, log=True, constant=1, device=None):

@@ -1025,6 +1025,45 @@ int gf_spectral_fisher(int B, int64_t M, int J, int objective,
                        const double *power, int64_t power_bs, const double *weight, int64_t weight_bs,
                        double *work, double *fisher, int64_t *used, int32_t *info, void *stream);
 
+/*
+ * Raw observing quarters to detrended series: the steps of the detrend=True branch of
+ * PowerSpectrum.from_light_curve (gadfly/psd.py:482-535) that are not the gap fill, on S segments (star x quarter) at
+ * once.  Segment s owns the elements off[s] .. off[s + 1] - 1 of the concatenated arrays (off [S + 1] int64,
+ * ascending; an empty segment is allowed).  One workgroup per segment, no floating-point atomics, every sum in a
+ * fixed order: a segment's result bits depend on its own data alone.  All return -1 for S < 1 or a null pointer.
+ *   gf_seg_median: med [S] <- numpy.median of each segment's finite values, to the bit (an even count gives
+ *     (a + b) / 2 of the two middle elements; -0 counts as +0; NaN for no element).  keep [off[S]] (uint8) or NULL:
+ *     only elements with keep != 0 count.  drop_last = 1 leaves each segment's last slot out (x then holds the
+ *     n - 1 differences that the diff entry point below wrote into the segment's n slots), 0 takes all.
+ *   gf_sigma_clip: astropy's sigma_clip(cenfunc=median, stdfunc=std) as lightkurve's remove_outliers runs it, all
+ *     rounds in one launch.  keep <- rows with finite f (and finite t, unless t is NULL); then per round med and the
+ *     population standard deviation sd (two passes, ddof 0) of the kept rows, keep only
+ *     med - sigma_lower sd <= f <= med + sigma_upper sd, stop after the round that removed nothing or after
+ *     maxiters rounds (maxiters < 0: no cap; 0: only the finite rows are selected, the sigmas are not read).
+ *     kept [S] (int64) <- rows kept, rounds [S] (int32) <- rounds run.  -1 unless both sigmas are > 0.
+ *   gf_seg_compact: the kept rows of (t, f) in their order, packed: new_off [S + 1] <- offsets of the packed
+ *     segments, t_out, f_out [up to off[S]] <- the rows.
+ *   gf_seg_diff: d[off[s] + i] <- t[off[s] + i + 1] - t[off[s] + i] for i < n_s - 1 (the last slot is set to 0).
+ *   gf_poly_normalise: the least-squares polynomial of degree `order` (0 .. GF_DETREND_MAX_ORDER, else -1) of f over
+ *     t per segment, and normed <- f / fit.  Basis: Legendre polynomials of u = (t - mid) / half, mid and half from
+ *     the segment's first and last time (u = 0 where they coincide) -- the space numpy.polyfit(t - mean(t), f, order)
+ *     fits; Gram matrix and right-hand side in float64, Cholesky on chip.  info [S] (int32) <- 0, or the 1-based
+ *     index of the pivot that was not positive (an empty segment: 1); such a segment's normed is NaN, the others are
+ *     not touched.
+ *   gf_seg_ppm: out <- 1e6 (x / med[s] - 1) (out may be x).
+ */
+#define GF_DETREND_MAX_ORDER 8
+int gf_seg_median(int S, const int64_t *off, const double *x, const uint8_t *keep, int drop_last, double *med,
+                  void *stream);
+int gf_sigma_clip(int S, const int64_t *off, const double *t, const double *f, double sigma_lower,
+                  double sigma_upper, int maxiters, uint8_t *keep, int64_t *kept, int32_t *rounds, void *stream);
+int gf_seg_compact(int S, const int64_t *off, const uint8_t *keep, const double *t, const double *f,
+                   int64_t *new_off, double *t_out, double *f_out, void *stream);
+int gf_seg_diff(int S, const int64_t *off, const double *t, double *d, void *stream);
+int gf_poly_normalise(int S, const int64_t *off, const double *t, const double *f, int order, double *normed,
+                      int32_t *info, void *stream);
+int gf_seg_ppm(int S, const int64_t *off, const double *x, const double *med, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
