@@ -15,7 +15,7 @@ from .batch import (BatchedLogLikelihood, log_likelihood_batch, BatchedSampler, 
                     predict_batch, sample_conditional_batch)
 from . import terms  # noqa: F401
 from .psd import PowerSpectrum, bin_power_spectrum  # noqa: F401
-from .interp import interpolate_missing_data, stitch_quarters  # noqa: F401
+from .interp import interpolate_missing_data, interpolate_missing_data_batch, stitch_quarters  # noqa: F401
 from .detrend import prepare_quarters, prepare_quarters_batch  # noqa: F401
 from . import spectral  # noqa: F401
 from . import conddraw  # noqa: F401

@@ -175,6 +175,9 @@ SIGNATURES = {
     "gf_seg_diff": (_int, [_int, _vp, _vp, _vp, _vp]),
     "gf_poly_normalise": (_int, [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "gf_seg_ppm": (_int, [_int] + [_vp] * 4 + [_vp]),
+    "gf_interp_seg_work": (_i64, [_i64]),
+    "gf_interp_plan_seg": (_int, [_int, _i64] + [_vp] * 9 + [_vp]),
+    "gf_interp_fill_seg": (_int, [_int, _i64] + [_vp] * 9 + [_vp]),
 }
 
 

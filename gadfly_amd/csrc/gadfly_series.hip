@@ -5,6 +5,7 @@
 // transform itself is hipFFT's.
 //   k_psd_power, k_psd_bin     |X|^2 * norm of a spectrum, and its means and errors over frequency bins
 //   k_interp_*                 a plan (count, scan, offsets) and a fill (points, missing) of the cadences a series lacks
+//   k_interp_*_seg             the same plan and fill for many series at once, over one offset table
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -111,6 +112,28 @@ __device__ __forceinline__ int64_t cadence_index(const double *t, const int64_t 
 
 constexpr int SCAN_PER_WG = 2048;       // elements per 256-thread workgroup (8 per thread)
 
+// 1 + number of cadences missing after point i of a series of N points (its last point: 1)
+__device__ __forceinline__ int64_t interp_count(const int64_t N, const double *t, const int64_t *cad,
+                                                const double t0, const double dt, const int64_t i) {
+    if (i + 1 >= N) return 1;
+    const int64_t gap = cadence_index(t, cad, i + 1, t0, dt) - cadence_index(t, cad, i, t0, dt) - 1;
+    return gap > 0 ? 1 + gap : 1;
+}
+
+// The scan of one workgroup's SCAN_PER_WG counts: thread x holds 8 neighbours, loc[k] = sum of its counts before the
+// k-th and run = their sum; -> the sum over the threads before x (the workgroup's total: part[255])
+__device__ __forceinline__ int64_t interp_scan_wg(int64_t *part, const int64_t run) {
+    part[threadIdx.x] = run;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {           // Hillis-Steele inclusive scan of the 256 partials
+        const int64_t v = (threadIdx.x >= (unsigned)off) ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    return part[threadIdx.x] - run;
+}
+
 // counts[i] = 1 + number of cadences missing after point i; block_sums[wg] = sum over the workgroup's
 // SCAN_PER_WG elements; offsets[i] = exclusive scan of counts WITHIN the workgroup
 __global__ void __launch_bounds__(256)
@@ -123,26 +146,11 @@ k_interp_count(const int64_t N, const double *__restrict__ t, const int64_t *__r
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int64_t i = base + k;
-        int64_t cnt = 0;
-        if (i < N) {
-            cnt = 1;
-            if (i + 1 < N) {
-                const int64_t gap = cadence_index(t, cad, i + 1, t0, dt) - cadence_index(t, cad, i, t0, dt) - 1;
-                if (gap > 0) cnt += gap;
-            }
-        }
+        const int64_t cnt = (i < N) ? interp_count(N, t, cad, t0, dt, i) : 0;
         loc[k] = run;
         run += cnt;
     }
-    part[threadIdx.x] = run;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {           // Hillis-Steele inclusive scan of the 256 partials
-        const int64_t v = (threadIdx.x >= (unsigned)off) ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const int64_t before = part[threadIdx.x] - run;
+    const int64_t before = interp_scan_wg(part, run);
 #pragma unroll
     for (int k = 0; k < 8; ++k)
         if (base + k < N) offsets[base + k] = before + loc[k];
@@ -193,13 +201,15 @@ __device__ __forceinline__ double grid_time(const double t0, const int64_t m, co
     return t0 + (double)m * dt;
 }
 
-// G[i] = offsets[i] - i = number of missing cadences before point i's gap
-__global__ void __launch_bounds__(256)
-k_interp_points(const int64_t N, const double *__restrict__ t, const double *__restrict__ f,
-                const int64_t *__restrict__ cad, const double t0, const double dt,
-                const int64_t *__restrict__ offsets, double *__restrict__ t_out, double *__restrict__ f_out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
+// The two fill rules for point i of ONE series of N points (t, f, cad start at its first point; t0 = t[0]).
+// offs[j] - obase = j + (number of cadences missing before point j), j = 0 .. N: the series' own scan (obase = 0)
+// or its stretch of a scan over many series, obase = offs[0].  t_out, f_out start at the series' first output.
+// G[i] = offs[i] - obase - i = number of missing cadences before point i's gap
+__device__ __forceinline__ void interp_point(const int64_t N, const double *__restrict__ t,
+                                             const double *__restrict__ f, const int64_t *__restrict__ cad,
+                                             const double t0, const double dt, const int64_t *__restrict__ offs,
+                                             const int64_t obase, const int64_t i, double *__restrict__ t_out,
+                                             double *__restrict__ f_out) {
     const double ti = t[i];
     // M = smallest cadence index whose grid time is >= t_i (monotone in m: settle it exactly)
     int64_t M = (int64_t)floor((ti - t0) / dt) - 1;
@@ -214,24 +224,22 @@ k_interp_points(const int64_t N, const double *__restrict__ t, const double *__r
     int64_t before = 0;
     if (lo > 0) {
         const int64_t j = lo - 1;
-        const int64_t gap = offsets[j + 1] - offsets[j] - 1;
+        const int64_t gap = offs[j + 1] - offs[j] - 1;
         int64_t part = M - cadence_index(t, cad, j, t0, dt) - 1;
         part = part < 0 ? 0 : (part > gap ? gap : part);
-        before = (offsets[j] - j) + part;
+        before = (offs[j] - obase - j) + part;
     }
     t_out[i + before] = ti;
     f_out[i + before] = f[i];
 }
 
-__global__ void __launch_bounds__(256)
-k_interp_missing(const int64_t N, const double *__restrict__ t, const double *__restrict__ f,
-                 const int64_t *__restrict__ cad, const double t0, const double dt,
-                 const int64_t *__restrict__ offsets, double *__restrict__ t_out, double *__restrict__ f_out) {
+// the cadences missing after point i (one thread fills the whole gap)
+__device__ __forceinline__ void interp_missing(const int64_t N, const double *__restrict__ t,
+                                               const double *__restrict__ f, const int64_t *__restrict__ cad,
+                                               const double t0, const double dt, const int64_t G, const int64_t gap,
+                                               const int64_t i, double *__restrict__ t_out,
+                                               double *__restrict__ f_out) {
 #pragma clang fp contract(off)      // numpy rounds the product and the sum separately (no FMA)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const int64_t G = offsets[i] - i, gap = offsets[i + 1] - offsets[i] - 1;
-    if (gap <= 0) return;
     const int64_t ci = cadence_index(t, cad, i, t0, dt);
     int64_t p = i + 1;                              // #{points with t <= x}: grows with k, starts near i
     for (int64_t k = 1; k <= gap; ++k) {
@@ -255,6 +263,144 @@ k_interp_missing(const int64_t N, const double *__restrict__ t, const double *__
         t_out[o] = x;
         f_out[o] = v;
     }
+}
+
+__global__ void __launch_bounds__(256)
+k_interp_points(const int64_t N, const double *__restrict__ t, const double *__restrict__ f,
+                const int64_t *__restrict__ cad, const double t0, const double dt,
+                const int64_t *__restrict__ offsets, double *__restrict__ t_out, double *__restrict__ f_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    interp_point(N, t, f, cad, t0, dt, offsets, 0, i, t_out, f_out);
+}
+
+__global__ void __launch_bounds__(256)
+k_interp_missing(const int64_t N, const double *__restrict__ t, const double *__restrict__ f,
+                 const int64_t *__restrict__ cad, const double t0, const double dt,
+                 const int64_t *__restrict__ offsets, double *__restrict__ t_out, double *__restrict__ f_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int64_t G = offsets[i] - i, gap = offsets[i + 1] - offsets[i] - 1;
+    if (gap <= 0) return;
+    interp_missing(N, t, f, cad, t0, dt, G, gap, i, t_out, f_out);
+}
+
+// ------------------------------------------------------------------------------------
+// The same plan and fill over S series at once (gf_interp_plan_seg / gf_interp_fill_seg): segment s owns the
+// elements off[s] .. off[s + 1] - 1 of the concatenated arrays.  The structure stays flat -- one count per point, ONE
+// int64 scan over the whole concatenation, one thread per point and per gap -- so a single series of 2e6 points is as
+// parallel as 1000 of 2000; each point finds its segment by a binary search of off and then applies the per-point
+// rules above to its segment's own stretch (first time, first cadence number, searches, ranks: all local), so a
+// segment's bits depend on its own data alone.  A segment that is not selected, or whose dt is not a positive
+// finite number, counts 1 per point: it comes out as a copy.
+// ------------------------------------------------------------------------------------
+// the segment that owns element i (0 <= i < off[S]): the last s with off[s] <= i, which steps over empty segments
+__device__ __forceinline__ int segment_of(const int64_t *__restrict__ off, const int S, const int64_t i) {
+    int lo = 0, hi = S;                             // first s with off[s + 1] > i (off[S] > i)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid + 1] <= i) lo = mid + 1; else hi = mid;
+    }
+    return lo < S ? lo : S - 1;
+}
+
+// dt of a segment to fill, 0 for one to copy (which[s] == 0: dt[s] is not read)
+__device__ __forceinline__ double segment_cadence(const uint8_t *__restrict__ which, const double *__restrict__ dt,
+                                                  const int s) {
+    if (which && !which[s]) return 0.0;
+    const double d = dt[s];
+    return (d > 0.0 && d < __builtin_inf()) ? d : 0.0;
+}
+
+// k_interp_count over the concatenation: plan[i] = exclusive scan of the counts WITHIN the workgroup
+__global__ void __launch_bounds__(256)
+k_interp_count_seg(const int S, const int64_t total, const int64_t *__restrict__ off, const double *__restrict__ t,
+                   const int64_t *__restrict__ cad, const double *__restrict__ dt, const uint8_t *__restrict__ which,
+                   int64_t *__restrict__ plan, int64_t *__restrict__ block_sums) {
+    __shared__ int64_t part[256];
+    const int64_t base = (int64_t)blockIdx.x * SCAN_PER_WG + (int64_t)threadIdx.x * 8;
+    int64_t loc[8], run = 0;
+    if (base < total) {
+        int s = segment_of(off, S, base);
+        int64_t b = off[s], e = off[s + 1];
+        double d = segment_cadence(which, dt, s);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int64_t i = base + k;
+            int64_t cnt = 0;
+            if (i < total) {
+                if (i >= e) {                       // the thread's 8 neighbours cross into a later segment
+                    while (i >= e && s + 1 < S) { ++s; e = off[s + 1]; }
+                    b = off[s];
+                    d = segment_cadence(which, dt, s);
+                }
+                cnt = (d > 0.0) ? interp_count(e - b, t + b, cad ? cad + b : nullptr, t[b], d, i - b) : 1;
+            }
+            loc[k] = run;
+            run += cnt;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) loc[k] = 0;
+    }
+    const int64_t before = interp_scan_wg(part, run);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (base + k < total) plan[base + k] = before + loc[k];
+    if (threadIdx.x == 255) block_sums[blockIdx.x] = part[255];
+}
+
+// new_off[s] = plan[off[s]] (s = 0 .. S); info[s] = 1 where a segment to fill has no usable dt
+__global__ void __launch_bounds__(256)
+k_interp_seg_offsets(const int S, const int64_t *__restrict__ off, const double *__restrict__ dt,
+                     const uint8_t *__restrict__ which, const int64_t *__restrict__ plan,
+                     int64_t *__restrict__ new_off, int32_t *__restrict__ info) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s > S) return;
+    new_off[s] = plan[off[s]];
+    if (s < S) {
+        const bool fill = (!which || which[s]) && off[s + 1] > off[s];
+        info[s] = (fill && !(segment_cadence(which, dt, s) > 0.0)) ? 1 : 0;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_interp_points_seg(const int S, const int64_t total, const int64_t *__restrict__ off, const double *__restrict__ t,
+                    const double *__restrict__ f, const int64_t *__restrict__ cad, const double *__restrict__ dt,
+                    const uint8_t *__restrict__ which, const int64_t *__restrict__ plan,
+                    double *__restrict__ t_out, double *__restrict__ f_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int s = segment_of(off, S, i);
+    const int64_t b = off[s], n = off[s + 1] - b, o = plan[b];
+    const double d = segment_cadence(which, dt, s);
+    if (!(d > 0.0)) {
+        t_out[o + (i - b)] = t[i];
+        f_out[o + (i - b)] = f[i];
+        return;
+    }
+    interp_point(n, t + b, f + b, cad ? cad + b : nullptr, t[b], d, plan + b, o, i - b, t_out + o, f_out + o);
+}
+
+__global__ void __launch_bounds__(256)
+k_interp_missing_seg(const int S, const int64_t total, const int64_t *__restrict__ off, const double *__restrict__ t,
+                     const double *__restrict__ f, const int64_t *__restrict__ cad, const double *__restrict__ dt,
+                     const uint8_t *__restrict__ which, const int64_t *__restrict__ plan,
+                     double *__restrict__ t_out, double *__restrict__ f_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t gap = plan[i + 1] - plan[i] - 1;
+    if (gap <= 0) return;                           // also every point of a copied segment
+    const int s = segment_of(off, S, i);
+    const int64_t b = off[s], n = off[s + 1] - b, o = plan[b];
+    interp_missing(n, t + b, f + b, cad ? cad + b : nullptr, t[b], segment_cadence(which, dt, s),
+                   plan[i] - o - (i - b), gap, i - b, t_out + o, f_out + o);
+}
+
+int check_segments(const char *who, int S, int64_t total) {
+    if (S < 1) return gf_internal_error(-1, "%s: no segments (S=%d)", who, S);
+    if (total < 0) return gf_internal_error(-1, "%s: negative length (total=%lld)", who, (long long)total);
+    return 0;
 }
 
 }  // namespace
@@ -296,6 +442,47 @@ int gf_interp_fill(int64_t N, const double *t, const double *f, const int64_t *c
     hipLaunchKernelGGL(k_interp_missing, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, t, f, cadences,
                        t0, dt, offsets, t_out, f_out);
     return check_launch("gf_interp_fill");
+}
+
+int64_t gf_interp_seg_work(int64_t total) {
+    if (total < 0) return gf_internal_error(-1, "gf_interp_seg_work: negative length (total=%lld)", (long long)total);
+    return gf_interp_work(total);
+}
+
+int gf_interp_plan_seg(int S, int64_t total, const int64_t *off, const double *t, const int64_t *cadences,
+                       const double *dt, const uint8_t *which, int64_t *plan, int64_t *new_off, int32_t *info,
+                       int64_t *work, void *stream) {
+    if (int st = check_segments("gf_interp_plan_seg", S, total)) return st;
+    if (!off || !t || !dt || !plan || !new_off || !info || !work)
+        return gf_internal_error(-1, "gf_interp_plan_seg: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nb = gf_interp_seg_work(total);
+    if (nb > 0)
+        hipLaunchKernelGGL(k_interp_count_seg, dim3((unsigned)nb), dim3(256), 0, st, S, total, off, t, cadences, dt,
+                           which, plan, work);
+    hipLaunchKernelGGL(k_interp_scan_top, dim3(1), dim3(256), 0, st, nb, total, work, plan);
+    if (total > 0)
+        hipLaunchKernelGGL(k_interp_offsets, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, work,
+                           plan);
+    hipLaunchKernelGGL(k_interp_seg_offsets, dim3((unsigned)(S / 256 + 1)), dim3(256), 0, st, S, off, dt, which, plan,
+                       new_off, info);
+    return check_launch("gf_interp_plan_seg");
+}
+
+int gf_interp_fill_seg(int S, int64_t total, const int64_t *off, const double *t, const double *f,
+                       const int64_t *cadences, const double *dt, const uint8_t *which, const int64_t *plan,
+                       double *t_out, double *f_out, void *stream) {
+    if (int st = check_segments("gf_interp_fill_seg", S, total)) return st;
+    if (!off || !t || !f || !dt || !plan || !t_out || !f_out)
+        return gf_internal_error(-1, "gf_interp_fill_seg: null pointer");
+    if (total == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    hipLaunchKernelGGL(k_interp_points_seg, grid, dim3(256), 0, st, S, total, off, t, f, cadences, dt, which, plan,
+                       t_out, f_out);
+    hipLaunchKernelGGL(k_interp_missing_seg, grid, dim3(256), 0, st, S, total, off, t, f, cadences, dt, which, plan,
+                       t_out, f_out);
+    return check_launch("gf_interp_fill_seg");
 }
 
 int gf_psd_power(int R, int64_t M, int64_t first, double norm, const double *spec,

@@ -7,8 +7,8 @@ Per quarter: drop the rows whose time or flux is not finite and clip outliers ab
 divide by a least-squares polynomial in time and by the median, ``1e6 (f / median - 1)``; then the quarters in the
 order given, and one more fill over the gaps between them.  All quarters of all stars of a call go through the
 clip, the compaction, the medians and the fit together, as ONE segmented batch (``gf_sigma_clip``,
-``gf_seg_compact``, ``gf_seg_diff``, ``gf_seg_median``, ``gf_poly_normalise``, ``gf_seg_ppm``); the
-gap fill runs per segment through ``gf_interp_plan`` / ``gf_interp_fill``.
+``gf_seg_compact``, ``gf_seg_diff``, ``gf_seg_median``, ``gf_poly_normalise``, ``gf_seg_ppm``, and for the gap fill
+``gf_interp_plan_seg`` / ``gf_interp_fill_seg``).
 
 Parity with lightkurve is unpinned: neither lightkurve nor astropy is a dependency, so the clip is restated from
 the documented behaviour of ``remove_outliers(sigma=5)`` -- astropy's ``sigma_clip(sigma, maxiters=5,
@@ -17,6 +17,7 @@ cenfunc=median, stdfunc=std)`` -- and tested against ``tests/detrend_ref.py``.
 import numpy as np
 
 from . import _lib
+from .interp import _fill_segments
 
 __all__ = ["prepare_quarters", "prepare_quarters_batch"]
 
@@ -97,36 +98,14 @@ class _Device:
         _lib.check(self.lib.gf_seg_diff(S, _lib.ptr(off), _lib.ptr(t), _lib.ptr(d), self.st), "gf_seg_diff")
         return self.median(S, off, d, drop_last=1)
 
-    def fill(self, off_h, t, f, dt_h, which):
-        """`interpolate_missing_data` of the segments `which` (the others are copied): all plans, one read-back of
-        the totals, then the fills.  -> (new host offsets, t, f)"""
-        torch, lib = self.torch, self.lib
+    def fill(self, off_h, off, t, f, dt, which=None, name=lambda s: f"segment {s}"):
+        """`interpolate_missing_data` of the segments with `which[s] != 0` (host flags; None: all; the others are
+        copied) at the cadences `dt` [S], which stay on the device: one plan, ONE read-back of the new offsets, one
+        fill.  -> (new host offsets, new device offsets, t, f)"""
         S = len(off_h) - 1
-        n = np.diff(off_h)
-        plan = self.empty(int(off_h[-1]) + S, torch.int64)          # segment s: n_s + 1 words at off[s] + s
-        work = self.empty(max(1, int(lib.gf_interp_work(int(n.max())))), torch.int64)
-        tp, fp, pp = t.data_ptr(), f.data_ptr(), plan.data_ptr()
-        for s in which:
-            b = int(off_h[s])
-            _lib.check(lib.gf_interp_plan(int(n[s]), tp + 8 * b, None, float(dt_h[s]), pp + 8 * (b + s),
-                                          _lib.ptr(work), self.st), "gf_interp_plan")
-        new_n = n.copy()
-        if len(which):
-            last = torch.as_tensor(np.asarray([off_h[s + 1] + s for s in which], dtype=np.int64), device=self.dev)
-            new_n[np.asarray(which)] = plan[last].cpu().numpy()
-        new_off = _offsets(new_n)
-        t2, f2 = self.empty(new_off[-1]), self.empty(new_off[-1])
-        tp2, fp2 = t2.data_ptr(), f2.data_ptr()
-        filled = set(which)
-        for s in range(S):
-            b, o = int(off_h[s]), int(new_off[s])
-            if s in filled:
-                _lib.check(lib.gf_interp_fill(int(n[s]), tp + 8 * b, fp + 8 * b, None, float(dt_h[s]),
-                                              pp + 8 * (b + s), tp2 + 8 * o, fp2 + 8 * o, self.st), "gf_interp_fill")
-            else:
-                t2[o:o + int(n[s])] = t[b:b + int(n[s])]
-                f2[o:o + int(n[s])] = f[b:b + int(n[s])]
-        return new_off, t2, f2
+        if which is not None:
+            which = self.torch.as_tensor(np.asarray(which, dtype=np.uint8), device=self.dev)
+        return _fill_segments(self.lib, self.dev, self.st, S, int(off_h[-1]), off, t, f, None, dt, which, name)
 
 
 def prepare_quarters_batch(stars, detrend_poly_order=3, sigma=5.0, sigma_lower=None, sigma_upper=None, maxiters=5,
@@ -172,8 +151,8 @@ def prepare_quarters_batch(stars, detrend_poly_order=3, sigma=5.0, sigma_lower=N
                                  f"{need} are needed (detrend_poly_order={k})")
         t1, f1 = t1[:int(off1_h[-1])], f1[:int(off1_h[-1])]
         if fill:
-            off2_h, t2, f2 = d.fill(off1_h, t1, f1, dt1.cpu().numpy(), list(range(S)))
-            off2 = torch.as_tensor(off2_h, device=dev)
+            off2_h, off2, t2, f2 = d.fill(off1_h, off1, t1, f1, dt1,
+                                          name=lambda s: f"star {labels[s][0]}, quarter {labels[s][1]}")
         else:
             off2_h, off2, t2, f2 = off1_h, off1, t1, f1
         # polynomial and median out, ppm
@@ -189,11 +168,10 @@ def prepare_quarters_batch(stars, detrend_poly_order=3, sigma=5.0, sigma_lower=N
         first = _offsets(per_star)
         off3_h = off2_h[first]
         off3 = torch.as_tensor(off3_h, device=dev)
-        many = [b for b in range(B) if per_star[b] > 1] if fill else []
-        if many:
-            dt3 = d.cadence(B, off3, t2).cpu().numpy()
-            off3_h, t2, f2 = d.fill(off3_h, t2, f2, dt3, many)
-            off3 = torch.as_tensor(off3_h, device=dev)
+        many = [n > 1 for n in per_star]
+        if fill and any(many):
+            off3_h, off3, t2, f2 = d.fill(off3_h, off3, t2, f2, d.cadence(B, off3, t2), many,
+                                          name=lambda b: f"star {b}")
         cadence = d.cadence(B, off3, t2).cpu().numpy()
         if not in_ppm:
             bad = np.flatnonzero(info.cpu().numpy())

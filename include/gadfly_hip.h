@@ -1064,6 +1064,32 @@ int gf_poly_normalise(int S, const int64_t *off, const double *t, const double *
                       int32_t *info, void *stream);
 int gf_seg_ppm(int S, const int64_t *off, const double *x, const double *med, double *out, void *stream);
 
+/*
+ * The gap fill of S series in one call: interpolate_missing_data (gadfly/interp.py:6-60, what the reference runs
+ * before every FFT spectrum, psd.py:495, :531) over the segment layout above.  Segment s owns the elements
+ * off[s] .. off[s + 1] - 1 (off [S + 1] int64, ascending, off[S] = total; an empty segment is allowed) of t, f and
+ * cadences (int64, or NULL: the cadence index of a point is rint((t - t_0) / dt[s]) with t_0 = t[off[s]], read on
+ * the device).  dt [S] float64 ON THE DEVICE; which [S] uint8 or NULL for all: a segment with which[s] == 0 is
+ * copied and its dt[s] is not read.  Per point the rules of gf_interp_plan / gf_interp_fill with every index and
+ * search local to the segment: a segment's result is, bit for bit, what those give for it alone.  One count per
+ * point, one scan over the whole concatenation, one thread per point and per gap -- one long segment stays parallel.
+ * Nothing is copied to the host and nothing synchronises.  All return -1 for S < 1, total < 0 or a null pointer.
+ *   gf_interp_plan_seg: plan [total + 1] <- exclusive scan over the concatenation of 1 + (cadences missing after
+ *     the point) (1 for a segment's last point and for every point of a copied segment), plan[total] = length of the
+ *     filled concatenation; new_off [S + 1] <- plan[off[s]], the offsets of the filled segments; info [S] (int32)
+ *     <- 0, or 1 where a selected, non-empty segment's dt is not a positive finite number: that segment is copied.
+ *     work: gf_interp_seg_work(total) int64 words of scratch.
+ *   gf_interp_fill_seg: t_out, f_out [plan[total]] <- each segment's input points and missing cadences, merged in
+ *     time order, from new_off[s] on.
+ */
+int64_t gf_interp_seg_work(int64_t total);
+int gf_interp_plan_seg(int S, int64_t total, const int64_t *off, const double *t, const int64_t *cadences,
+                       const double *dt, const uint8_t *which, int64_t *plan, int64_t *new_off, int32_t *info,
+                       int64_t *work, void *stream);
+int gf_interp_fill_seg(int S, int64_t total, const int64_t *off, const double *t, const double *f,
+                       const int64_t *cadences, const double *dt, const uint8_t *which, const int64_t *plan,
+                       double *t_out, double *f_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

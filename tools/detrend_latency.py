@@ -74,11 +74,11 @@ def stages(stars, order, reps):
     out["compact"] = measure(lambda: lib.gf_seg_compact(S, p(off0), p(keep), p(t0), p(f0), p(off1), p(t1), p(f1), st),
                              reps)
     out["cadence"] = measure(lambda: d.cadence(S, off1, t1), reps)
-    off1_h, dt1 = off1.cpu().numpy(), d.cadence(S, off1, t1).cpu().numpy()
+    off1_h, dt1 = off1.cpu().numpy(), d.cadence(S, off1, t1)
     t1, f1 = t1[:int(off1_h[-1])], f1[:int(off1_h[-1])]
-    out["fill_quarters"] = measure(lambda: d.fill(off1_h, t1, f1, dt1, list(range(S))), reps)
-    off2_h, t2, f2 = d.fill(off1_h, t1, f1, dt1, list(range(S)))
-    off2, normed, info = torch.as_tensor(off2_h, device=d.dev), torch.empty_like(f2), d.empty(S, torch.int32)
+    out["fill_quarters"] = measure(lambda: d.fill(off1_h, off1, t1, f1, dt1), reps)
+    off2_h, off2, t2, f2 = d.fill(off1_h, off1, t1, f1, dt1)
+    normed, info = torch.empty_like(f2), d.empty(S, torch.int32)
     out["poly_normalise"] = measure(lambda: lib.gf_poly_normalise(S, p(off2), p(t2), p(f2), order, p(normed), p(info),
                                                                   st), reps)
     ppm = torch.empty_like(normed)
@@ -91,8 +91,7 @@ def stages(stars, order, reps):
     off3 = torch.as_tensor(off3_h, device=d.dev)
 
     def stitch():
-        dt3 = d.cadence(B, off3, t2).cpu().numpy()
-        return d.fill(off3_h, t2, ppm, dt3, list(range(B)))
+        return d.fill(off3_h, off3, t2, ppm, d.cadence(B, off3, t2))
     out["fill_stitched"] = measure(stitch, reps)
     keep_h = keep.cpu().numpy().astype(bool)
     return {k: list(v) for k, v in out.items()}, [keep_h[off_h[s]:off_h[s + 1]] for s in range(S)], \
