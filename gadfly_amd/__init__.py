@@ -17,6 +17,7 @@ from . import terms  # noqa: F401
 from .psd import PowerSpectrum, bin_power_spectrum  # noqa: F401
 from .interp import interpolate_missing_data, interpolate_missing_data_batch, stitch_quarters  # noqa: F401
 from .detrend import prepare_quarters, prepare_quarters_batch  # noqa: F401
+from .linmodel import fit_linear_batch, quarter_polynomial_basis  # noqa: F401
 from . import spectral  # noqa: F401
 from . import conddraw  # noqa: F401
 from .spectral import SpectralLikelihood  # noqa: F401

@@ -24,7 +24,7 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_seri
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
            os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip"),
            os.path.join(CSRC, "gadfly_lsfft.hip"), os.path.join(CSRC, "gadfly_gradtp.hip"),
-           os.path.join(CSRC, "gadfly_detrend.hip")]
+           os.path.join(CSRC, "gadfly_detrend.hip"), os.path.join(CSRC, "gadfly_linmodel.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -37,6 +37,7 @@ GF_GRAD_WORKSPACE_BYTES = 16 << 30   # default cap on gf_loglike_grad's workspac
 GF_SOLVE_MAX_WIDTH = 63         # gf_solve_batch: one wave per problem (kernel and component alike)
 GF_SOLVE_WORKSPACE_BYTES = 16 << 30  # default cap on gf_solve_batch's workspace per call
 GF_DETREND_MAX_ORDER = 8        # gf_poly_normalise: Legendre polynomials P_0 .. P_8
+GF_LINEAR_MAX_COLS = 255        # gf_linear_gram: columns of the design matrix
 
 _lib = None
 
@@ -178,6 +179,10 @@ SIGNATURES = {
     "gf_interp_seg_work": (_i64, [_i64]),
     "gf_interp_plan_seg": (_int, [_int, _i64] + [_vp] * 9 + [_vp]),
     "gf_interp_fill_seg": (_int, [_int, _i64] + [_vp] * 9 + [_vp]),
+    "gf_linear_gram_work": (_i64, [_i64, _int, _int]),
+    "gf_linear_gram": (_int, [_int, _i64, _int, _int, _int] + [_vp] * 7
+                       + [_vp, _i64, _vp, _i64, _vp, _i64, _vp] + [_vp, _i64, _i64, _vp, _i64]
+                       + [_vp] * 3 + [_vp]),
 }
 
 

@@ -693,6 +693,70 @@ class BatchedLogLikelihood:
         res, _ = self._solve_rhs(y, pack_or_kernels, want_alpha=False, want_mu=False)
         return res["ll"]
 
+    # -- linear mean models: generalised least squares from one forward sweep (DESIGN.md 3.17) -------------------
+
+    #: cap on the workspace of one :meth:`linear_gram_device` call in bytes: larger batches run in groups
+    linear_workspace_bytes = _lib.GF_SOLVE_WORKSPACE_BYTES
+
+    def _linear_gram(self, basis, pack_or_kernels):
+        from .linmodel import check_width, linear_gram, stack_basis
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0)
+        A, ncols = stack_basis(basis, self.B, eng.N, self.rows)
+        Jr, Jc, real, comp, diag_add = self._pack0 if pack_or_kernels is None else self._host_pack(pack_or_kernels)
+        A = eng.torch.as_tensor(A, dtype=eng.torch.float64, device=eng.device)
+        res = linear_gram(eng, Jr, Jc, real, comp, diag_add, A, self.rows, self.linear_workspace_bytes)
+        #: (workspace bytes of a group, number of groups, problems per group) and the HIP events of the last call
+        self.last_linear_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
+        self._linear_events = res["events"]
+        return res, ncols
+
+    def linear_gram_device(self, basis, pack_or_kernels=None):
+        """[A | y]^T Sigma^-1 [A | y] of the linear mean models y = A beta + eps, eps ~ N(0, K_b + diag), for B
+        kernels at once from ONE forward sweep (``gf_linear_gram``): ``basis`` (N, R) shared, (B, N, R), or a list of
+        B arrays (N_b, R_b) (required for a ragged batch; zero-padded to the widest), y the data of construction minus
+        their mean.  Returns ``(gram (B, R + 1, R + 1), logdet (B,), info (B,))`` as device tensors: y is the last
+        column, logdet = log det Sigma, info the 1-based row of a failed pivot (that problem's gram and logdet are
+        NaN).  W > 63 raises ``NotImplementedError``.  No host synchronisation."""
+        res, _ = self._linear_gram(basis, pack_or_kernels)
+        return res["gram"], res["logdet"], res["info"]
+
+    @property
+    def last_linear_device_ms(self):
+        """Device time of the last :meth:`linear_gram_device` / :meth:`fit_linear` call (waits for it)."""
+        return self._events_ms(self._linear_events)
+
+    def fit_linear(self, basis, pack_or_kernels=None):
+        """The generalised least squares fits of the B linear mean models (``basis`` as :meth:`linear_gram_device`):
+        a :class:`gadfly_amd.linmodel.LinearFit` of numpy fields -- ``beta``, ``cov``, ``stderr``, ``chi2``, the
+        profile log-likelihood ``ll``, the likelihood marginalised over beta ``ll_marginal``, ``ok``, ``ncols``,
+        ``info``.  A problem whose matrix is not positive definite or whose basis is rank-deficient gets ``ok =
+        False`` and NaN; the others are unaffected."""
+        from .linmodel import solve_normal_equations
+        res, ncols = self._linear_gram(basis, pack_or_kernels)
+        nrows = np.full(self.B, self.engine.N, dtype=np.int64) if self.rows is None else self.rows
+        return solve_normal_equations(res["gram"].cpu().numpy(), res["logdet"].cpu().numpy(), nrows, ncols,
+                                      res["info"].cpu().numpy())
+
+    def linear_trend_device(self, basis, beta):
+        """The fitted trends A beta of the B problems on the device: (B, N), or a list of B series for a ragged batch
+        or a list ``basis``; ``beta`` (B, R) as :meth:`fit_linear` gives it."""
+        from .linmodel import stack_basis
+        eng = self.engine
+        torch = eng.torch
+        as_list = isinstance(basis, (list, tuple)) or self.rows is not None
+        A, ncols = stack_basis(basis, self.B, eng.N, self.rows)
+        beta = torch.as_tensor(np.asarray(beta, dtype=np.float64), device=eng.device)
+        if tuple(beta.shape) != (self.B, A.shape[2]):
+            raise ValueError(f"beta of shape {tuple(beta.shape)} for {self.B} problems of {A.shape[2]} columns")
+        A = torch.as_tensor(A, dtype=torch.float64, device=eng.device)
+        trend = torch.matmul(A, beta[:, :, None])[:, :, 0]
+        if not as_list:
+            return trend
+        rows = [eng.N] * self.B if self.rows is None else [int(n) for n in self.rows]
+        return [trend[b, :n] for b, n in enumerate(rows)]
+
     def sample_conditional_device(self, pack_or_kernels=None, t=None, size=None, normals=None, seed=None,
                                   include_mean=True):
         """Draws from the conditional distribution of the B processes given their data, exact and with

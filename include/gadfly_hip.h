@@ -1090,6 +1090,34 @@ int gf_interp_fill_seg(int S, int64_t total, const int64_t *off, const double *t
                        const int64_t *cadences, const double *dt, const uint8_t *which, const int64_t *plan,
                        double *t_out, double *f_out, void *stream);
 
+/*
+ * Linear mean models under B kernels: y = A beta + eps, eps ~ N(0, Sigma_b), Sigma_b = K_b + diag.
+ * With Sigma = L D L^T and Z = L^-1 [A | y], one forward sweep gives everything a generalised least squares fit needs:
+ *   gram [B][R + 1][R + 1] = [A | y]^T Sigma^-1 [A | y] = Z^T D^-1 Z (contiguous, equal to its transpose bit for bit),
+ *   logdet [B] = sum_n log D_n,  info [B] (int32) = 0, or the 1-based row whose pivot fails.
+ * No upper solve, no checkpoints, nothing of size N is returned.
+ *   coefficients, diag_add, t, diag, y with their batch strides as gf_solve_batch
+ *   nobs [B] int64 or NULL: the sweep of problem b stops after nobs[b] rows (held to 0 .. N); later rows of t, diag,
+ *     y and A are never read
+ *   A [B][N][R], row-major: row stride lda >= R, batch stride a_bs (0 = one matrix shared by all problems)
+ *   work: work_bs >= gf_linear_gram_work(N, W, R) doubles per problem (z_n / sqrt(D_n) of every row and column)
+ * One workgroup per problem and block of 64 columns of [A | y]: one wave runs gf_solve_batch's forward row (D and
+ * info are gf_solve_batch's), a second one carries a column per lane; a second kernel sums the products over the rows
+ * in one fixed order.  A problem's outputs have the same bits whatever the batch around it, and the entries among the
+ * first r columns and y have the same bits whatever further columns A holds.  A problem whose pivot fails gets NaN in
+ * gram and logdet; the other problems are unaffected.  No atomics.
+ * Returns -1 for bad shapes (R < 1 or R > 255 among them), strides or null pointers, -3 for W > 63;
+ * gf_linear_gram_work returns 0 for them.
+ */
+int64_t gf_linear_gram_work(int64_t N, int W, int R);
+int gf_linear_gram(int B, int64_t N, int R, int Jr, int Jc,
+                   const double *ar, const double *cr, const double *ac, const double *bc,
+                   const double *cc, const double *dc, const double *diag_add,
+                   const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                   const double *y, int64_t y_bs, const int64_t *nobs,
+                   const double *A, int64_t lda, int64_t a_bs, double *work, int64_t work_bs,
+                   double *gram, double *logdet, int32_t *info, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
