@@ -2070,6 +2070,17 @@ __device__ __forceinline__ void half_wave_sums(double v, double &lo, double &up)
     up = read_lane(v, 63);
 }
 
+// v in the lanes of the mask, keep in the others: the mask is wave-uniform and stays in a scalar register pair (as a
+// comparison of the lane number it would be a vector compare per use)
+__device__ __forceinline__ double lane_select(const unsigned long long lanes, const double v, const double keep) {
+    int lo = __double2loint(keep), hi = __double2hiint(keep);
+    asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(lo) : "v"(__double2loint(v)), "s"(lanes));
+    asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(hi) : "v"(__double2hiint(v)), "s"(lanes));
+    return __hiloint2double(hi, lo);
+}
+
+constexpr int R1_UNROLL = 8;                        // plain rows per trip of the unrolled body
+
 __global__ void __launch_bounds__(64, 2)
 k_steady_rank1(const int64_t N, const int64_t n_first, const int Jc, const double gap,
                const double *__restrict__ ac_, const double *__restrict__ bc_,
@@ -2143,14 +2154,70 @@ k_steady_rank1(const int64_t N, const int64_t n_first, const int Jc, const doubl
         tp_nx = (n_first + i > 0) ? tg[i - 1] : t_nx - delta;
         y_nx = yg[i];
     }
+    // A block's d and z are staged in two registers, row j's in lane j, and leave by one lane-parallel store each where
+    // the block ends: at its last row, at the switch row, in front of the first row whose pivot is not positive.  The
+    // pivots are tested there and at the anchor, on the staged lanes at once: the recursion may run up to 63 rows past
+    // a failed pivot (nothing traps, nothing of those rows is stored), but no anchor is taken behind one.
+    double sd = 0.0, sz = 0.0, sr, si, beta, yv_blk = 0.0;
+    auto row_front = [&](const int j) __attribute__((always_inline)) {             // pivot and residual of block row j, and s = X + k m
+        const double yy = read_lane(yv_blk, j);
+        double sf;
+        half_wave_sums(fma(ck_a, Xr, -(ck_b * Xi)), sf, beta);          // Re((a + i b) X): <u0, f> below, <u0, Y> above
+        const double zn = yy - sf;
+        const unsigned long long row_lane = 1ull << j;
+        sd = lane_select(row_lane, d, sd);
+        sz = lane_select(row_lane, zn, sz);
+        const double m = h ? -beta : zn;
+        sr = fma(kr, m, Xr), si = fma(ki, m, Xi);   // below: s = f + k z, the tail's state
+    };
+    auto row_back = [&]() __attribute__((always_inline)) {
+        Xr = fma(lr, sr, -(li * si));
+        Xi = fma(lr, si, li * sr);
+        const double sb = sg * beta;
+        rr = fma(-sb, Yr, rr);
+        ri = fma(-sb, Yi, ri);
+        const double dn = fma(-sb, beta, d);
+        const double wr = fma(-beta, kr, Yr), wi = fma(-beta, ki, Yi);          // (k: the old gain)
+        Yr = fma(lr, wr, -(li * wi));
+        Yi = fma(lr, wi, li * wr);
+        inv = fast_rcp(dn);
+        sg = sg * d * inv;
+        d = dn;
+        kr = rr * inv;
+        ki = ri * inv;
+    };
+    auto plain_rows = [&](int j, const int j1) __attribute__((always_inline)) {    // rows without an anchor: no test, no store, no exit
+        for (; j + R1_UNROLL <= j1; j += R1_UNROLL) {
+#pragma unroll
+            for (int u = 0; u < R1_UNROLL; ++u) {
+                row_front(j + u);
+                row_back();
+            }
+        }
+#pragma unroll 1
+        for (; j < j1; ++j) {
+            row_front(j);
+            row_back();
+        }
+    };
+    // the first of the staged rows [0, rows) whose pivot is not positive, -1: none
+    auto first_failed = [&](const int rows) __attribute__((always_inline)) {
+        const unsigned long long staged = rows < 64 ? (1ull << rows) - 1 : ~0ull;
+        const unsigned long long bad = __ballot(!(sd > 0.0)) & staged;
+        return bad ? (int)__ffsll((long long)bad) - 1 : -1;
+    };
+    auto flush = [&](const int64_t nb, const int rows) __attribute__((always_inline)) {
+        if (lane < rows) { dg[nb + lane] = sd; zg[nb + lane] = sz; }
+    };
     const int g0lo = (int)(n_first & (ST_GRID - 1));
+    const int ja = (ST_GRID - g0lo) & (ST_GRID - 1);        // the anchor's row in every block of this tile
     __builtin_amdgcn_s_setprio(GF_CHAIN_PRIO);
-    for (int64_t nb = 0; nb < N && !fail; nb += 64) {
+    for (int64_t nb = 0; nb < N; nb += 64) {
         const int lim = (int)(N - nb < 64 ? N - nb : 64);
-        double yv = y_nx;
-        // the block's y has arrived HERE: left to the row loop, its first use puts a vector-memory wait into every row,
-        // and that counter holds the rows' own stores of d and z too
-        asm volatile("" : "+v"(yv));
+        yv_blk = y_nx;
+        // the block's y has arrived HERE: left to the rows, its first use puts a vector-memory wait into every row,
+        // and that counter holds the blocks' stores of d and z too
+        asm volatile("" : "+v"(yv_blk));
         {
             const double dt = t_nx - tp_nx;
             const bool bad = (dt > gthr) || !(fabs(dt - delta) < jthr);
@@ -2160,21 +2227,13 @@ k_steady_rank1(const int64_t N, const int64_t n_first, const int Jc, const doubl
             tp_nx = (n_first + i > 0) ? tg[i - 1] : t_nx - delta;
             y_nx = yg[i];
         }
-        for (int j = 0; j < lim; ++j) {
-            const double yy = read_lane(yv, j);
-            double sf, beta;
-            half_wave_sums(fma(ck_a, Xr, -(ck_b * Xi)), sf, beta);      // Re((a + i b) X): <u0, f> below, <u0, Y> above
-            const double zn = yy - sf;
-            if (!(d > 0.0)) {
-                const int64_t gf = n_first + nb + j + 1;
-                fail = (int32_t)(gf > 0x7fffffff ? 0x7fffffff : gf);
-                break;
-            }
-            if (lane == 0) { dg[nb + j] = d; zg[nb + j] = zn; }
-            const double m = h ? -beta : zn;
-            const double sr = fma(kr, m, Xr), si = fma(ki, m, Xi);      // below: s = f + k z, the tail's state
-            if (((g0lo + j) & (ST_GRID - 1)) == 0) {
-                const int64_t n = nb + j, gn = n_first + n;
+        int jf;                                     // the block's first failed row
+        if (ja < lim) {
+            plain_rows(0, ja);
+            row_front(ja);
+            jf = first_failed(ja + 1);              // (in front of the ring, ST_CNT, ST_FILL and the header)
+            if (jf < 0) {
+                const int64_t n = nb + ja, gn = n_first + n;
                 if (gn >= arm_from) {
                     // an anchor of the rule: k_factor7's test on the same ring
                     const double x = fl ? d : (h ? ki : kr);
@@ -2200,25 +2259,25 @@ k_steady_rank1(const int64_t N, const int64_t n_first, const int Jc, const doubl
                             hdr[ST_D] = d;
                             hdr[ST_DT] = (tg[n] - tg[n - ST_DLAG]) * (1.0 / ST_DLAG);     // (gn >= 1024)
                         }
+                        flush(nb, ja + 1);
                         R1_EXIT(n + 1);             // (row n + 1 is the tail's first; rows 0 .. n were stored)
                     }
                 }
+                row_back();
+                plain_rows(ja + 1, lim);
+                jf = first_failed(lim);
             }
-            Xr = fma(lr, sr, -(li * si));
-            Xi = fma(lr, si, li * sr);
-            const double sb = sg * beta;
-            rr = fma(-sb, Yr, rr);
-            ri = fma(-sb, Yi, ri);
-            const double dn = fma(-sb, beta, d);
-            const double wr = fma(-beta, kr, Yr), wi = fma(-beta, ki, Yi);      // (k: the old gain)
-            Yr = fma(lr, wr, -(li * wi));
-            Yi = fma(lr, wi, li * wr);
-            inv = fast_rcp(dn);
-            sg = sg * d * inv;
-            d = dn;
-            kr = rr * inv;
-            ki = ri * inv;
+        } else {                                    // the tile's last block ends in front of its anchor
+            plain_rows(0, lim);
+            jf = first_failed(lim);
         }
+        if (jf >= 0) {                              // the failed row and the rows behind it are not stored
+            flush(nb, jf);
+            const int64_t gf = n_first + nb + jf + 1;
+            fail = (int32_t)(gf > 0x7fffffff ? 0x7fffffff : gf);
+            break;
+        }
+        flush(nb, lim);
     }
     if (fail) {
         if (lane == 0) info[pr] = fail;
@@ -2232,7 +2291,7 @@ k_steady_rank1(const int64_t N, const int64_t n_first, const int Jc, const doubl
   }
 #undef R1_EXIT
 tile_sums:
-    // as k_factor7's steady instance: lane 0's stores of d and z ordered before the wave's loads of them
+    // as k_factor7's steady instance: the blocks' stores of d and z ordered before the wave's loads of them
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");

@@ -1017,6 +1017,7 @@ class StreamingBatch:
         self._steady_chunk_ws = None        # [B][gf_steady_chunk_size()] workspace of the chunked launch
         self._steady_mid_ws = None          # the same of the middle window's launch (the two can overlap)
         self._finish_side = None            # the early launches' stream
+        self._finish_mid_side = None        # the middle window's stream (steady_middle_stream)
         self._simds = None                  # SIMDs of the device (4 per compute unit), read once
         # behind the split the sweep's own wave adds its tile to acc (gf_steady_sweep_reduced); False: the separate
         # reduction on every tile, for comparisons (the same bits)
@@ -1355,6 +1356,16 @@ class StreamingBatch:
         if not k_e < k_m < ntiles - 1:
             mid_end, k_m = 0, -1
         windows = steady_windows(split, mid_end)
+        used = []                           # this evaluation's side streams, joined in front of gf_loglike_finish
+
+        def side_stream(middle):
+            """The early launch's stream, or the middle window's own."""
+            which = "_finish_mid_side" if middle else "_finish_side"
+            if getattr(self, which) is None:
+                setattr(self, which, torch.cuda.Stream(device=self.device))
+            if getattr(self, which) not in used:
+                used.append(getattr(self, which))
+            return getattr(self, which)
 
         def chunked(stream, window, cb, which):
             """One chunked finishing launch with the workspace of its own."""
@@ -1409,15 +1420,15 @@ class StreamingBatch:
             if k == k_e or k == k_m:
                 # every problem that has switched by now: its last write of acc on this stream -- tile k's reduction,
                 # or tile k's sweep where that adds its own rows -- is behind us, and the later tiles touch neither its
-                # header nor its acc.  The two launches share the side stream: the middle one runs
-                # behind the early one
-                if self._finish_side is None:
-                    self._finish_side = torch.cuda.Stream(device=self.device)
-                self._finish_side.wait_event(main.record_event())
+                # header nor its acc.  The middle launch has a stream of its own and stands behind
+                # tile k_m's sweep only: the two windows hold different problems, and they need slots, not an order
+                # (steady_middle_stream off: on the early launch's stream, behind it)
+                side = side_stream(k == k_m and self.steady_middle_stream)
+                side.wait_event(main.record_event())
                 if k == k_e:
-                    finish("gf_steady_finish_window", self._finish_side, *windows[0])
+                    finish("gf_steady_finish_window", side, *windows[0])
                 else:
-                    chunked(self._finish_side, windows[1], steady_chunk_blocks(N, 8), "_steady_mid_ws")
+                    chunked(side, windows[1], steady_chunk_blocks(N, 8), "_steady_mid_ws")
         if self.steady_used:
             # every switched problem's rows from its switch row to the end of the series: no row is stored, acc takes
             # their sums (event pairs of their own: factor_events stays one entry per tile)
@@ -1429,7 +1440,8 @@ class StreamingBatch:
                 else:
                     cb = steady_chunk_blocks(N, 8)
                 chunked(main, windows[-1], cb, "_steady_chunk_ws")
-                main.wait_stream(self._finish_side)
+                for side in used:
+                    main.wait_stream(side)
             else:
                 finish("gf_steady_finish", main)
             # for the next plan, without a sync here: the earliest switch row (0: nothing armed), the rows in front of
@@ -1457,6 +1469,8 @@ class StreamingBatch:
     #: smallest batch that takes a middle window: below it the last window would hold fewer than 8 problems, and the
     #: B/8 stragglers' chunks all find a SIMD at once behind the last tile anyway
     STEADY_MIDDLE_MIN_B = 512
+    #: the middle window's launch on a stream of its own; False: behind the early launch, on its stream
+    steady_middle_stream = True
 
     def _steady_plan(self, arm_from):
         """Row from whose tile on this evaluation runs the steady instance, None for the plain sweep throughout.

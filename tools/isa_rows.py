@@ -215,20 +215,32 @@ def rank1(lines):
     total = counts([op for b in bl for op in b["ins"]])
     print(f"k_steady_rank1: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, {total['scratch']} scratch "
           f"(spill) in all; {vgpr} VGPRs")
-    tree = [i for i, b in enumerate(bl) if b["ins"].count("v_mov_b32_dpp") == 10]    # five steps of one double
-    reg = tree[0]
-    i0, i1 = row_loop_outer(bl, reg)
-    print(f"row loop: blocks {bl[i0]['name']} .. {bl[i1]['name']} (`tree`: the half-wave sums)")
-    print(f"{'block':>14} {'VALU':>5} {'fma':>4} {'dpp':>4} {'SALU':>5} {'br':>3} {'store':>5} {'load':>5}  role")
+    # five DPP steps of one double per row: a block with 10 n of them holds n rows (an unrolled body)
+    tree = [i for i, b in enumerate(bl) if b["ins"].count("v_mov_b32_dpp") and b["ins"].count("v_mov_b32_dpp") % 10 == 0]
+    if len(tree) == 1:
+        i0, i1 = row_loop_outer(bl, tree[0])
+    else:                                       # the block loop: the smallest loop around every block that holds rows
+        idx = {b["name"]: i for i, b in enumerate(bl)}
+        loops = [(idx[t], j) for j, b in enumerate(bl) for t in b["targets"]
+                 if t in idx and idx[t] <= tree[0] and j >= tree[-1]]
+        i0, i1 = min(loops, key=lambda r: r[1] - r[0])
+    print(f"row loop: blocks {bl[i0]['name']} .. {bl[i1]['name']} (`tree`: the half-wave sums; `rows`: trees in the block)")
+    print(f"{'block':>14} {'VALU':>5} {'fma':>4} {'dpp':>4} {'SALU':>5} {'br':>3} {'store':>5} {'load':>5} {'rows':>4}  role")
     for k in range(i0, i1 + 1):
         b = bl[k]
         if not b["ins"]:
             continue
         c = counts(b["ins"])
         fma = sum(op.startswith(("v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64")) for op in b["ins"])
+        rows = b["ins"].count("v_mov_b32_dpp") // 10 if k in tree else 0
         print(f"{b['name']:>14} {c['valu']:5d} {fma:4d} {b['ins'].count('v_mov_b32_dpp'):4d} {c['salu']:5d} "
-              f"{c['branch']:3d} {sum(op.startswith('global_store') for op in b['ins']):5d} {c['gload']:5d}  "
-              f"{'tree' if k == reg else ''}")
+              f"{c['branch']:3d} {sum(op.startswith('global_store') for op in b['ins']):5d} {c['gload']:5d} "
+              f"{rows or '':>4}  {'tree' if k in tree else ''}")
+    for k in tree:
+        c, rows = counts(bl[k]["ins"]), bl[k]["ins"].count("v_mov_b32_dpp") // 10
+        if i0 <= k <= i1 and rows > 1:
+            print(f"  {bl[k]['name']}: {rows} rows; per row {c['valu'] / rows:.1f} VALU, {c['salu'] / rows:.1f} SALU, "
+                  f"{c['branch'] / rows:.2f} branches")
 
 
 def row_loop_outer(bl, reg):
