@@ -30,6 +30,10 @@ def __getattr__(name):
     if name == "LogLikelihood":
         from .grad import LogLikelihood
         return LogLikelihood
+    # torch.autograd.Function over BatchedLogLikelihood.linear_value_and_grad (gadfly_amd.grad); imported on first use
+    if name == "LinearModelLogLikelihood":
+        from .grad import LinearModelLogLikelihood
+        return LinearModelLogLikelihood
     # torch.autograd.Function over SpectralLikelihood.value_and_grad (gadfly_amd.spectral); imported on first use
     if name == "SpectralLogLikelihood":
         return spectral.SpectralLogLikelihood

@@ -24,7 +24,8 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_seri
            os.path.join(CSRC, "gadfly_var.hip"), os.path.join(CSRC, "gadfly_spectral.hip"),
            os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip"),
            os.path.join(CSRC, "gadfly_lsfft.hip"), os.path.join(CSRC, "gadfly_gradtp.hip"),
-           os.path.join(CSRC, "gadfly_detrend.hip"), os.path.join(CSRC, "gadfly_linmodel.hip")]
+           os.path.join(CSRC, "gadfly_detrend.hip"), os.path.join(CSRC, "gadfly_linmodel.hip"),
+           os.path.join(CSRC, "gadfly_quadform.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -183,6 +184,10 @@ SIGNATURES = {
     "gf_linear_gram": (_int, [_int, _i64, _int, _int, _int] + [_vp] * 7
                        + [_vp, _i64, _vp, _i64, _vp, _i64, _vp] + [_vp, _i64, _i64, _vp, _i64]
                        + [_vp] * 3 + [_vp]),
+    "gf_quadform_grad_block": (_int, []),
+    "gf_quadform_grad_work": (_i64, [_int, _int]),
+    "gf_quadform_grad": (_int, [_int, _i64, _int, _int, _int] + [_vp] * 6 + [_vp, _i64, _vp]
+                         + [_vp, _i64, _i64, _vp, _i64] + [_vp, _i64] + [_vp] * 3 + [_vp]),
 }
 
 

@@ -710,6 +710,7 @@ class BatchedLogLikelihood:
         #: (workspace bytes of a group, number of groups, problems per group) and the HIP events of the last call
         self.last_linear_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
         self._linear_events = res["events"]
+        res["A"], res["pack"] = A, (Jr, Jc, real, comp, diag_add)
         return res, ncols
 
     def linear_gram_device(self, basis, pack_or_kernels=None):
@@ -733,11 +734,63 @@ class BatchedLogLikelihood:
         profile log-likelihood ``ll``, the likelihood marginalised over beta ``ll_marginal``, ``ok``, ``ncols``,
         ``info``.  A problem whose matrix is not positive definite or whose basis is rank-deficient gets ``ok =
         False`` and NaN; the others are unaffected."""
+        return self._fit_linear(basis, pack_or_kernels)[0]
+
+    def _fit_linear(self, basis, pack_or_kernels):
+        """:meth:`fit_linear`, and what :meth:`_linear_gram` returned with it."""
         from .linmodel import solve_normal_equations
         res, ncols = self._linear_gram(basis, pack_or_kernels)
         nrows = np.full(self.B, self.engine.N, dtype=np.int64) if self.rows is None else self.rows
-        return solve_normal_equations(res["gram"].cpu().numpy(), res["logdet"].cpu().numpy(), nrows, ncols,
-                                      res["info"].cpu().numpy())
+        fit = solve_normal_equations(res["gram"].cpu().numpy(), res["logdet"].cpu().numpy(), nrows, ncols,
+                                     res["info"].cpu().numpy())
+        return fit, res
+
+    def linear_value_and_grad_coefficients(self, basis, pack_or_kernels=None, marginal=False):
+        """The log-likelihoods of the B linear mean models at their generalised least squares fits -- profiled over
+        beta, or with ``marginal`` integrated over it under a flat prior -- and their gradients with respect to the
+        celerite coefficients.  ``basis`` as :meth:`fit_linear`.  Returns ``(ll, grads)``: ll (B,)
+        numpy, :meth:`fit_linear`'s ``ll`` or ``ll_marginal`` to the bit; grads in the engine's stacked layout,
+        ``real`` (2, B, Jr), ``comp`` (4, B, Jc), ``diag_add`` (B,).  A problem whose fit failed (``ok`` False) gets
+        NaN, the others are unaffected.  The fit is kept in :attr:`last_linear_fit`, the device time per stage in
+        :attr:`last_linear_grad_ms`."""
+        from .linmodel import linear_gradients
+        self._grad_check_width()
+        fit, res = self._fit_linear(basis, pack_or_kernels)
+        g = linear_gradients(self.engine, *res["pack"], res["A"], fit, self.rows, bool(marginal),
+                             self.grad_workspace_bytes, self.predict_workspace_bytes)
+        stages = g.pop("stage_events")
+        #: (workspace bytes of a group, number of groups, problems per group) of the last call's gf_loglike_grad step
+        self.last_linear_grad_plan = g.pop("grad_plan")
+        ms = {"gram": self._events_ms(res["events"]), "grad": stages.pop("grad_ms")}
+        ms.update({k: self._events_ms(v) for k, v in stages.items()})
+        #: the fit of the last :meth:`linear_value_and_grad` call and its device time in ms, stage by stage
+        self.last_linear_fit, self.last_linear_grad_ms = fit, ms
+        return (fit.ll_marginal if marginal else fit.ll), g
+
+    def linear_value_and_grad(self, basis, S0, w0, Q, delta, wrt=("S0", "w0", "Q"), marginal=False,
+                              return_fit=False):
+        """:meth:`value_and_grad` under a linear mean fitted with the kernel: the profile (``marginal``: the
+        marginal) log-likelihoods of y = A beta + eps at (B, J) SHO hyperparameter arrays and their gradients.
+        Returns ``(ll, grads)`` -- with ``return_fit`` also the :class:`gadfly_amd.linmodel.LinearFit`; grads holds
+        the names of ``wrt`` among ``"S0"``, ``"w0"``, ``"Q"`` ((B, J) each) and ``"diag"`` ((B,)).  W > 63 raises
+        ``NotImplementedError``; every error is raised before anything is enqueued."""
+        from .grad import parameter_vjp
+        wrt = tuple(wrt)
+        unknown = set(wrt) - {"S0", "w0", "Q", "diag"}
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        shapes = {np.shape(np.atleast_2d(np.asarray(v))) for v in (S0, w0, Q)}
+        if len(shapes) != 1 or next(iter(shapes))[0] != self.B:
+            raise ValueError(f"S0, w0, Q of shapes {sorted(shapes)} do not hold the batch's {self.B} problems")
+        pk = sho_coefficient_pack(S0, w0, Q, delta)
+        ll, g = self.linear_value_and_grad_coefficients(basis, pk, marginal=marginal)
+        out = {}
+        if {"S0", "w0", "Q"} & set(wrt):
+            gS0, gw0, gQ = parameter_vjp(S0, w0, Q, delta, g["real"], g["comp"], g["diag_add"])
+            out.update({k: v for k, v in (("S0", gS0), ("w0", gw0), ("Q", gQ)) if k in wrt})
+        if "diag" in wrt:
+            out["diag"] = g["diag_add"]
+        return (ll, out, self.last_linear_fit) if return_fit else (ll, out)
 
     def linear_trend_device(self, basis, beta):
         """The fitted trends A beta of the B problems on the device: (B, N), or a list of B series for a ragged batch

@@ -17,7 +17,8 @@ from . import _lib
 from .rowcall import GroupedCall, check_pack_batch, group_plan
 
 __all__ = ["sho_coefficient_pack_torch", "check_width", "check_pack_batch", "workspace_plan", "default_chunk_len",
-           "coefficient_gradients", "parameter_vjp", "LogLikelihood", "DEFAULT_WORKSPACE_BYTES"]
+           "coefficient_gradients", "parameter_vjp", "LogLikelihood", "LinearModelLogLikelihood",
+           "DEFAULT_WORKSPACE_BYTES"]
 
 #: default cap on the gradient workspace of one call (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = _lib.GF_GRAD_WORKSPACE_BYTES
@@ -86,7 +87,7 @@ def default_chunk_len(B, N, W):
 
 
 def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES,
-                          chunk_len=None, time_parallel=False):
+                          chunk_len=None, time_parallel=False, y=None, rows=None):
     """Run ``gf_loglike_grad`` over an engine's data (t, y - mean, diag on the device) for stacked host
     coefficient arrays of its ORIGINAL term structure.  Returns a dict of numpy arrays: ``ll`` (B,),
     ``real`` (2, B, Jr) = d/d(a, c), ``comp`` (4, B, Jc) = d/d(a, b, c, d), ``diag_add`` (B,), ``mean`` (B,),
@@ -96,7 +97,11 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
     ``time_parallel``: the chunked route (``gf_loglike_grad_chunked``, for one long series or a few) in chunks of
     ``chunk_len`` rows (None: :func:`default_chunk_len`); the result also holds ``chunk_len`` and ``reruns``, the
     number of problems it flagged.  Those are run again through ``gf_loglike_grad``, so that log L, info and the NaN
-    gradients of a matrix that is not positive definite are the one-wave route's."""
+    gradients of a matrix that is not positive definite are the one-wave route's.
+
+    ``y``: a float64 device tensor (1 or B, N) that stands in for the engine's data (the residuals of a linear mean
+    model); ``rows``: (B,) real rows per problem -- every problem is then swept on its own, over its
+    real rows alone (one-wave route only), and has the bits of a call of its own.  Without them nothing changes."""
     W = Jr + 2 * Jc
     if (Jr, Jc) != engine._struct0:
         raise ValueError("coefficient pack does not match the batch structure")
@@ -111,9 +116,16 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
             raise ValueError(f"chunk_len = {chunk_len}")
         name, head = "gf_loglike_grad_chunked", (N, min(chunk_len, N))
     plan = workspace_plan(N, W, B, cap_bytes, head[1] if time_parallel else None)
+    if rows is not None:
+        if time_parallel:
+            raise ValueError("rows= belongs to the one-wave route")
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.shape != (B,) or np.any(rows < 1) or np.any(rows > N):
+            raise ValueError("dimension mismatch")
+        plan = (max(workspace_plan(int(n), W, 1, cap_bytes)[0] for n in np.unique(rows)), 1, B)
     f64 = dict(dtype=torch.float64, device=engine.device)
     with torch.cuda.device(engine.device):
-        rc = GroupedCall(engine, name, plan, (real, comp, diag_add))
+        rc = GroupedCall(engine, name, plan, (real, comp, diag_add), y=y)
         ll = torch.empty((B,), **f64)
         info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
         g_diag = torch.empty((B,), **f64)
@@ -125,7 +137,8 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
         def group(g):
             gr = torch.zeros((2, g.nb, lr), **f64)
             gc = torch.zeros((4, g.nb, lc), **f64)
-            g.launch(g.nb, *head, Jr, Jc, *g.coef[0], *g.data, *g.work, g.at(ll), gr.data_ptr(), gc.data_ptr(),
+            shape = head if rows is None else (int(rows[g.b0]),)
+            g.launch(g.nb, *shape, Jr, Jc, *g.coef[0], *g.data, *g.work, g.at(ll), gr.data_ptr(), gc.data_ptr(),
                      g.at(g_diag), g.at(g_mean), g.at(info), g.stream)
             g_real[:, g.b0:g.b0 + g.nb] = gr.cpu().numpy()
             g_comp[:, g.b0:g.b0 + g.nb] = gc.cpu().numpy()
@@ -139,7 +152,7 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
                 # one problem per group: the one-wave kernel, whose bits do not depend on the batch around a problem
                 per = workspace_plan(N, W, 1, cap_bytes)[0]
                 head = (N,)
-                one = GroupedCall(engine, "gf_loglike_grad", (per, 1, B), (real, comp, diag_add))
+                one = GroupedCall(engine, "gf_loglike_grad", (per, 1, B), (real, comp, diag_add), y=y)
                 events += one.run(group, only=flagged)
         return dict(ll=ll.cpu().numpy(), real=g_real[:, :, :Jr], comp=g_comp[:, :, :Jc],
                     diag_add=g_diag.cpu().numpy(), mean=g_mean.cpu().numpy(), info=info.cpu().numpy(),
@@ -225,3 +238,25 @@ class LogLikelihood(torch.autograd.Function):
         gS0, gw0, gQ = ctx.saved_tensors
         go = grad_output[:, None]
         return go * gS0, go * gw0, go * gQ, None, None, None
+
+
+class LinearModelLogLikelihood(torch.autograd.Function):
+    """``LinearModelLogLikelihood.apply(S0, w0, Q, evaluator, basis, delta[, marginal])``: the (B,) log-likelihoods of
+    the linear mean models y = A beta + eps of a :class:`gadfly_amd.BatchedLogLikelihood` at their generalised least
+    squares fits -- profiled over beta, or with ``marginal`` integrated over it -- at (B, J) tensors of SHO
+    hyperparameters, differentiable with respect to S0, w0 and Q
+    (:meth:`BatchedLogLikelihood.linear_value_and_grad`)."""
+
+    @staticmethod
+    def forward(ctx, S0, w0, Q, evaluator, basis, delta, marginal=False):
+        host = [x.detach().cpu().numpy() for x in (S0, w0, Q)]
+        ll, g = evaluator.linear_value_and_grad(basis, *host, delta, marginal=bool(marginal))
+        ctx.save_for_backward(*(torch.as_tensor(g[k], dtype=S0.dtype, device=S0.device)
+                                for k in ("S0", "w0", "Q")))
+        return torch.as_tensor(ll, dtype=S0.dtype, device=S0.device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gS0, gw0, gQ = ctx.saved_tensors
+        go = grad_output[:, None]
+        return go * gS0, go * gw0, go * gQ, None, None, None, None

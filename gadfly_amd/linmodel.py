@@ -13,7 +13,8 @@ from . import _lib
 from .rowcall import GroupedCall, check_pack_batch, group_plan
 
 __all__ = ["MAX_COLUMNS", "check_width", "workspace_plan", "stack_basis", "linear_gram", "solve_normal_equations",
-           "LinearFit", "quarter_polynomial_basis", "fit_linear_batch", "DEFAULT_WORKSPACE_BYTES"]
+           "LinearFit", "quarter_polynomial_basis", "fit_linear_batch", "DEFAULT_WORKSPACE_BYTES",
+           "quadform_gradients", "linear_gradients"]
 
 #: default cap on the workspace of one call (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = _lib.GF_SOLVE_WORKSPACE_BYTES
@@ -113,6 +114,7 @@ class LinearFit:
     """What :func:`solve_normal_equations` returns, numpy fields over the B problems:
 
     ``beta`` (B, R) and ``stderr`` (B, R), ``cov`` (B, R, R) -- entries beyond a problem's ``ncols`` are zero --,
+    ``factor`` (B, R, R) upper triangular with factor factor^T = cov to rounding (the scaled inverse Cholesky factor),
     ``chi2`` = y^T Sigma^-1 y - g^T beta, ``ll`` the profile log-likelihood, ``ll_marginal`` the log-likelihood
     marginalised over beta under a flat prior, ``logdet`` = log det Sigma, ``logdet_normal`` = log det A^T Sigma^-1 A,
     ``ok`` (False: NaN in every field of that problem), ``ncols``, ``nrows``, ``info``."""
@@ -161,7 +163,7 @@ def solve_normal_equations(gram, logdet, nrows, ncols, info=None):
     info = np.zeros(B, dtype=np.int32) if info is None else np.asarray(info, dtype=np.int32).reshape(-1)
     R = C - 1
     nan = np.nan
-    beta, cov = np.full((B, R), nan), np.full((B, R, R), nan)
+    beta, cov, fac = np.full((B, R), nan), np.full((B, R, R), nan), np.full((B, R, R), nan)
     chi2, ldn = np.full(B, nan), np.full(B, nan)
     ok = np.zeros(B, dtype=bool)
     for r in np.unique(ncols):
@@ -184,8 +186,9 @@ def solve_normal_equations(gram, logdet, nrows, ncols, info=None):
         bt = np.matmul(inv, g[:, :, None])[:, :, 0]
         good &= np.all(np.isfinite(inv.reshape(len(idx), -1)), axis=1) & np.all(np.isfinite(bt), axis=1)
         k = idx[good]
-        beta[k], cov[k] = 0.0, 0.0
+        beta[k], cov[k], fac[k] = 0.0, 0.0, 0.0
         beta[k, :r] = bt[good]
+        fac[k, :r, :r] = s[good][:, :, None] * np.transpose(Li[good], (0, 2, 1))
         cov[k, :r, :r] = inv[good]
         chi2[k] = yy[good] - np.sum(g[good] * bt[good], axis=1)
         ldn[k] = 2.0 * np.sum(np.log(piv[good]), axis=1) - 2.0 * np.sum(np.log(s[good]), axis=1)
@@ -194,7 +197,7 @@ def solve_normal_equations(gram, logdet, nrows, ncols, info=None):
     ll = -0.5 * (chi2 + logdet + nrows * log2pi)
     ll_marginal = ll - 0.5 * ldn + 0.5 * ncols * log2pi
     stderr = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
-    return LinearFit(beta=beta, cov=cov, stderr=stderr, chi2=chi2, ll=ll, ll_marginal=ll_marginal,
+    return LinearFit(beta=beta, cov=cov, factor=fac, stderr=stderr, chi2=chi2, ll=ll, ll_marginal=ll_marginal,
                      logdet=np.where(ok, logdet, nan), logdet_normal=ldn, ok=ok, ncols=ncols, nrows=nrows, info=info)
 
 
@@ -230,3 +233,140 @@ def fit_linear_batch(kernels, t, y, basis, yerr=None, diag=None, mean=0.0, devic
     """One-shot :meth:`gadfly_amd.BatchedLogLikelihood.fit_linear`: the GLS fits of B kernels' linear mean models."""
     from .batch import BatchedLogLikelihood
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean, device=device).fit_linear(basis)
+
+
+# ---- gradients of the profile and the marginal likelihood (DESIGN.md 3.17.1) ----------------------------------------
+
+def quadform_gradients(engine, Jr, Jc, real, comp, x, w=None, nobs=None):
+    """Enqueue ``gf_quadform_grad`` over an engine's time axes: sum_r w_r x_r^T (d Sigma / d theta) x_r for every
+    celerite coefficient of B problems.  ``x``: float64 device tensor (B, R, N), or (1, R, N) shared; ``w``: None
+    (ones), or a float64 device tensor (R,) or (B, R); ``nobs``: (B,) real rows per problem, or None.  Returns a dict of
+    device tensors in gf_loglike_grad's layout -- ``real`` (2, B, max(Jr, 1)), ``comp`` (4, B, max(Jc, 1)),
+    ``diag_add`` (B,) -- and ``events``.  No host synchronisation."""
+    import torch
+    W = Jr + 2 * Jc
+    check_width(W)
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, np.zeros(B))
+    if x.ndim != 3 or x.shape[0] not in (1, B) or x.shape[2] != N or x.dtype != torch.float64:
+        raise ValueError(f"vectors of shape {tuple(x.shape)} for a batch of {B} problems of {N} rows")
+    R = int(x.shape[1])
+    if not 1 <= R <= MAX_COLUMNS + 1:
+        raise ValueError(f"gf_quadform_grad takes 1 .. {MAX_COLUMNS + 1} vectors per problem, not {R}")
+    if w is not None and (tuple(w.shape) not in ((R,), (B, R)) or w.dtype != torch.float64):
+        raise ValueError(f"weights of shape {tuple(w.shape)} for {R} vectors in {B} problems")
+    if nobs is not None:
+        nobs = np.ascontiguousarray(nobs, dtype=np.int64)
+        if nobs.shape != (B,) or np.any(nobs < 1) or np.any(nobs > N):
+            raise ValueError("dimension mismatch")
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    lib, p = engine.lib, _lib.ptr
+    per = int(lib.gf_quadform_grad_work(W, R))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        x = x.to(dev).contiguous()
+        w = None if w is None else w.to(dev).contiguous()
+        nobs = None if nobs is None else torch.as_tensor(nobs, dtype=torch.int64, device=dev)
+        cr_ = torch.as_tensor(np.ascontiguousarray(real, dtype=np.float64), **f64)
+        cc_ = torch.as_tensor(np.ascontiguousarray(comp, dtype=np.float64), **f64)
+        work = torch.empty((B * per,), **f64)
+        g_real = torch.zeros((2, B, max(Jr, 1)), **f64)
+        g_comp = torch.zeros((4, B, max(Jc, 1)), **f64)
+        g_diag = torch.empty((B,), **f64)
+        t = engine.t
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        st = lib.gf_quadform_grad(
+            B, N, R, Jr, Jc, p(cr_[0]), p(cr_[1]), p(cc_[0]), p(cc_[1]), p(cc_[2]), p(cc_[3]),
+            p(t), engine._bs(t), p(nobs), p(x), 0 if x.shape[0] == 1 else R * N, N,
+            p(w), 0 if w is None or w.ndim == 1 else R, p(work), per, p(g_real), p(g_comp), p(g_diag), stream)
+        _lib.check(st, "gf_quadform_grad")
+        e1.record()
+    return dict(real=g_real, comp=g_comp, diag_add=g_diag, events=[(e0, e1)])
+
+
+def _solve_columns(engine, Jr, Jc, real, comp, diag_add, AT, rows, cap_bytes):
+    """X = Sigma^-1 A, the columns as rows: (B, R, N) on the device from ``AT`` (1 or B, R, N).  ``rows``: real rows per
+    problem of a ragged batch -- each problem is then solved on its own over its real rows (the rest stays zero)."""
+    import torch
+    from .predict import rhs_workspace_plan, solve_batch_rhs
+    if rows is None:
+        res = solve_batch_rhs(engine, Jr, Jc, real, comp, diag_add, AT, cap_bytes, want_alpha=True, want_mu=False)
+        return res["alpha"], res["events"]
+    B, N, R, W = engine.B, engine.N, int(AT.shape[1]), Jr + 2 * Jc
+    per = max(rhs_workspace_plan(int(n), W, 1, R, cap_bytes, 0)[0] for n in np.unique(rows))
+    f64 = dict(dtype=torch.float64, device=engine.device)
+    with torch.cuda.device(engine.device):
+        ybs = 0 if AT.shape[0] == 1 else R * N
+        rc = GroupedCall(engine, "gf_solve_batch_rhs", (per, 1, B), (real, comp, diag_add))
+        X = torch.zeros((B, R, N), **f64)
+        ll = torch.empty((B, R), **f64)
+        info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
+        events = rc.run(lambda g: g.launch(
+            g.nb, int(rows[g.b0]), R, Jr, Jc, *g.coef[0], *g.data[:4], g.at(AT, ybs), ybs, N, 0, *g.work,
+            g.at(X, R * N), None, R * N, N, g.at(ll, R), g.at(info), g.stream))
+    return X, events
+
+
+def linear_gradients(engine, Jr, Jc, real, comp, diag_add, A, fit, rows=None, marginal=False,
+                     grad_cap_bytes=_lib.GF_GRAD_WORKSPACE_BYTES, solve_cap_bytes=DEFAULT_WORKSPACE_BYTES):
+    """The coefficient adjoints of the profile (or, ``marginal``, the marginal) log-likelihood of B linear mean models
+    at their fits.  ``A``: the design matrices on the device, (1 or B, N, R) as
+    :func:`linear_gram` took them; ``fit``: the :class:`LinearFit` of the same coefficients; ``rows``: real rows per
+    problem of a ragged batch.
+
+    beta-hat maximises the likelihood, so the profile gradient is gf_loglike_grad's at the fixed residual
+    r = y - A beta-hat; the marginal one adds +1/2 sum_k c_k^T (d Sigma / d theta) c_k with C = Sigma^-1 A F,
+    F F^T = (A^T Sigma^-1 A)^-1 (``gf_solve_batch_rhs``, one batched product, ``gf_quadform_grad``).  Returns a dict of
+    numpy arrays -- ``real`` (2, B, Jr), ``comp`` (4, B, Jc), ``diag_add`` (B,), NaN for the problems with
+    ``fit.ok`` False, whose neighbours are unaffected --, ``stage_events``, name -> pairs of HIP events (``grad_ms``:
+    the summed device time of the gf_loglike_grad launches), and ``grad_plan``, (workspace bytes of a group, groups,
+    problems per group) of those launches."""
+    import torch
+    from .grad import coefficient_gradients
+    B, N = engine.B, engine.N
+    R = int(A.shape[2])
+    ok = np.asarray(fit.ok, dtype=bool)
+    dev = engine.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    stages = {}
+    with torch.cuda.device(dev):
+        beta = torch.as_tensor(np.where(ok[:, None], fit.beta, 0.0), **f64)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        # column by column, elementwise: one order of operations per element whatever B, N and R (a library product
+        # may sum in another order for another shape), and a padded column (zeros, beta = 0) changes no bit
+        resid = engine.y.expand(B, N).clone()
+        for i in range(R):
+            resid.addcmul_(A[:, :, i], beta[:, i:i + 1], value=-1.0)
+        e1.record()
+        stages["residual"] = [(e0, e1)]
+    g = coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, grad_cap_bytes, y=resid, rows=rows)
+    stages["grad_ms"] = g["device_ms"]
+    g_real, g_comp, g_diag = g["real"].copy(), g["comp"].copy(), g["diag_add"].copy()
+    if marginal:
+        with torch.cuda.device(dev):
+            AT = A.transpose(1, 2).contiguous()
+            X, stages["solve"] = _solve_columns(engine, Jr, Jc, real, comp, diag_add, AT, rows, solve_cap_bytes)
+            F = torch.as_tensor(np.where(ok[:, None, None], fit.factor, 0.0), **f64)
+            C = torch.empty((B, R, N), **f64)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for b0 in range(0, B, 32768):                   # C_b = F_b^T X_b (gf_bgemm: at most 65535 per launch)
+                nb = min(32768, B - b0)
+                _lib.check(engine.lib.gf_bgemm(nb, 1, 0, R, N, R, F[b0].data_ptr(), R, R * R, X[b0].data_ptr(), N,
+                                               R * N, None, 0, 0, C[b0].data_ptr(), N, R * N, stream), "gf_bgemm")
+            e1.record()
+            stages["product"] = [(e0, e1)]
+            half = torch.full((R,), 0.5, **f64)
+            q = quadform_gradients(engine, Jr, Jc, real, comp, C, half, rows)
+            stages["quadform"] = q["events"]
+            g_real = g_real + q["real"].cpu().numpy()[:, :, :Jr]
+            g_comp = g_comp + q["comp"].cpu().numpy()[:, :, :Jc]
+            g_diag = g_diag + q["diag_add"].cpu().numpy()
+    bad = ~ok
+    g_real[:, bad], g_comp[:, bad], g_diag[bad] = np.nan, np.nan, np.nan
+    return dict(real=g_real, comp=g_comp, diag_add=g_diag, stage_events=stages,
+                grad_plan=(g["workspace_bytes"], g["groups"], g["group_size"]))

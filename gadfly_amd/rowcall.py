@@ -79,12 +79,18 @@ class GroupedCall:
       where the pack has one, diag_add; six null pointers for a pack that is None;
     * ``data``: ``(t, tbs, diag, dbs, y, ybs)``, pointers at the group's first problem and batch strides;
     * ``work``: ``(pointer, doubles per problem)`` of the workspace; ``stream``: the current stream's handle;
+      ``y=``: a float64 device tensor (1 or B, N) that stands in for the engine's y (the residuals of a linear mean
+      model, :mod:`gadfly_amd.linmodel`); None: the engine's own;
     * :meth:`at`, the pointer of any other per-problem tensor at the group's first problem;
     * :meth:`launch`, the C call itself between a pair of HIP events, its status checked.
     """
 
-    def __init__(self, engine, name, plan, *packs):
+    def __init__(self, engine, name, plan, *packs, y=None):
         self.name, self.fn = name, getattr(engine.lib, name)
+        if y is not None and (y.ndim != 2 or y.shape[0] not in (1, engine.B) or y.shape[1] != engine.N
+                              or y.dtype != torch.float64 or not y.is_contiguous()):
+            raise ValueError(f"data of shape {tuple(y.shape)} for a batch of {engine.B} problems of {engine.N} rows")
+        self.y = y
         self.engine, self.B = engine, engine.B
         self.per, self.group, self.ngroups = plan
         self._f64 = dict(dtype=torch.float64, device=engine.device)
@@ -123,7 +129,7 @@ class GroupedCall:
         """``call(self)`` for each group in turn -- ``only``: for the groups of these indices --; returns the pairs
         of HIP events around the launches."""
         eng = self.engine
-        t, y, dg = eng.t, eng.y, eng.diag
+        t, y, dg = eng.t, eng.y if self.y is None else self.y, eng.diag
         tbs, ybs = eng._bs(t), eng._bs(y)
         dbs = 0 if dg is None else eng._bs(dg)
         only = None if only is None else {int(i) for i in only}

@@ -1118,6 +1118,35 @@ int gf_linear_gram(int B, int64_t N, int R, int Jr, int Jc,
                    const double *A, int64_t lda, int64_t a_bs, double *work, int64_t work_bs,
                    double *gram, double *logdet, int32_t *info, void *stream);
 
+/*
+ * Quadratic forms of the kernel's derivatives: for B problems with R vectors x_r of N rows each,
+ *     Q' = sum_r w_r x_r^T (d Sigma / d theta) x_r       for every celerite coefficient theta of the problem,
+ * in gf_loglike_grad's layout and convention: g_real [2][B][max(Jr, 1)] = d/d(a, c), g_comp [4][B][max(Jc, 1)] =
+ * d/d(a, b, c, d), g_diag [B] = sum_r w_r |x_r|^2 (the diagonal reaches Sigma through diag_add alone: lag zero is not
+ * part of d/da).  What the gradient of log det (A^T Sigma^-1 A) needs, with x_r the columns of Sigma^-1 A F,
+ * F F^T = (A^T Sigma^-1 A)^-1, and w = 1/2.  The sums are diagonal linear recurrences along the rows over the generator
+ * rows gf_loglike_grad differentiates (cos / sin of fl(d t_n)): no factor, no diagonal, no adjoint sweep.
+ *   coefficients, t, t_bs as gf_solve_batch; nobs [B] int64 or NULL: problem b's rows end at nobs[b] (held to 0 .. N),
+ *     later rows of t and x are never read
+ *   x [B][R][N]: batch stride x_bs (0 = shared by all problems), vector stride x_rs >= N; 1 <= R <= 256
+ *   w: NULL (every weight 1), or [R] with w_bs = 0, or [B][R] with w_bs >= R
+ *   work: work_bs >= gf_quadform_grad_work(W, R) doubles per problem
+ * One wave per problem and block of gf_quadform_grad_block() vectors, then one wave per problem that adds the blocks
+ * in order.  No atomics, one summation order per output: a problem's bits do not depend on the batch around it, and
+ * vectors of zeros (or of weight zero) behind its own leave them unchanged.  N = 1 gives exact zeros in g_real and
+ * g_comp.  Entries of g_real / g_comp of a kind the problem has no term of are not written.
+ * Returns -1 for bad shapes, strides or null pointers, -3 for W > 63; gf_quadform_grad_work returns 0 for them.
+ */
+int gf_quadform_grad_block(void);
+int64_t gf_quadform_grad_work(int W, int R);
+int gf_quadform_grad(int B, int64_t N, int R, int Jr, int Jc,
+                     const double *ar, const double *cr, const double *ac, const double *bc,
+                     const double *cc, const double *dc,
+                     const double *t, int64_t t_bs, const int64_t *nobs,
+                     const double *x, int64_t x_bs, int64_t x_rs, const double *w, int64_t w_bs,
+                     double *work, int64_t work_bs,
+                     double *g_real, double *g_comp, double *g_diag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
