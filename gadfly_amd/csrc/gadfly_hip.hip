@@ -1430,6 +1430,33 @@ __device__ __forceinline__ void stage_end() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// a complex number in double-double, (rh + rl) + i (ih + il), and the product of two of them: the set-up's powers of
+// lambda (steady_tail_rows, FOUR).  Products split exactly by FMA, sums by Knuth's two-sum; no fast-math here
+struct cdd { double rh, rl, ih, il; };
+__device__ __forceinline__ void dd_sum(const double a, const double b, double &s, double &e) {
+#pragma clang fp contract(off)
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+// hi + lo of p1 + sg p2 + tail, with p1, p2 given as exact products (p, e)
+__device__ __forceinline__ void dd_pair(const double a1, const double b1, const double a2, const double b2, const double sg,
+                                        const double tail, double &hi, double &lo) {
+#pragma clang fp contract(off)
+    const double p1 = a1 * b1, e1 = fma(a1, b1, -p1);
+    const double p2 = sg * (a2 * b2), e2 = sg * fma(a2, b2, -(a2 * b2));
+    double s, es;
+    dd_sum(p1, p2, s, es);
+    const double l = es + ((e1 + e2) + tail);
+    dd_sum(s, l, hi, lo);
+}
+__device__ __forceinline__ cdd cdd_mul(const cdd a, const cdd b) {
+    cdd c;
+    dd_pair(a.rh, b.rh, a.ih, b.ih, -1.0, fma(a.rh, b.rl, a.rl * b.rh) - fma(a.ih, b.il, a.il * b.ih), c.rh, c.rl);
+    dd_pair(a.rh, b.ih, a.ih, b.rh, 1.0, fma(a.rh, b.il, a.rl * b.ih) + fma(a.ih, b.rl, a.il * b.rh), c.ih, c.il);
+    return c;
+}
+
 #define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -1471,6 +1498,9 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     // 32 h + 31 of a block), and H off the chain from one block's state to the next, z = H (y + C s) = H y + Q s with
     // Q = H C (both below); k_steady_tail keeps the update on the lower half-wave and the three phases in series
     constexpr bool FOLD = !STORE;
+    // the folded block's state update takes four rows per step; ROWS = 64 has no registers for its constants (256
+    // VGPRs and a spill) and keeps the two-row step
+    constexpr bool FOUR = FOLD && ROWS < 64;
     const int lane = threadIdx.x, pr = blockIdx.x;
     const int half = lane >> 5, tk = FOLD ? (lane & 31) : lane;    // tk: the term whose constants this lane holds
     if (info[pr] != 0) return;
@@ -1771,6 +1801,41 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         sr = half ? 0.0 : fma(jr, slr, fma(-ji, sli, sur));
         si = half ? 0.0 : fma(jr, sli, fma(ji, slr, sui));
     };
+    // The four-row step's constants, lambda^4 and lambda^k G, k = 1 .. 3, and the join's lambda^32.  A constant that is
+    // off by a rounding is off the same way in every step of a tail, and lambda^32 by squarings in double gathers 30 of
+    // them: the powers are formed in double-double, once per launch, and each constant is rounded once
+    double l4r = 0.0, l4i = 0.0, g1r = 0.0, g1i = 0.0, g2r = 0.0, g2i = 0.0, g3r = 0.0, g3i = 0.0;
+    if constexpr (FOUR) {
+        const cdd l1{lr, 0.0, li, 0.0}, gd{Gr, 0.0, Gi, 0.0};
+        const cdd l2 = cdd_mul(l1, l1), l3 = cdd_mul(l2, l1), l4 = cdd_mul(l2, l2);
+        cdd lp = l4;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) lp = cdd_mul(lp, lp);
+        const cdd g1 = cdd_mul(l1, gd), g2 = cdd_mul(l2, gd), g3 = cdd_mul(l3, gd);
+        l4r = l4.rh; l4i = l4.ih;
+        l32r = lp.rh; l32i = lp.ih;
+        g1r = g1.rh; g1i = g1.ih; g2r = g2.rh; g2i = g2.ih; g3r = g3.rh; g3i = g3.ih;
+    }
+    // FOLD, the full block's forms.  The terms k (even) and k + 1 of Q s with the two accumulators in turn, so that no
+    // FMA waits on the one issued in front of it; each accumulator takes its terms in add_term's order: the same bits
+    auto add_pair = [&](const int k, const double2 sa, const double2 sb, double &x0, double &x1) {
+        x0 = fma(pcr[k], sa.x, x0);
+        x1 = fma(pcr[k + 1], sb.x, x1);
+        x0 = fma(pci[k], sa.y, x0);
+        x1 = fma(pci[k + 1], sb.y, x1);
+    };
+    // the state over four rows z_j .. z_j+3:  s <- lambda^4 s + w,  w = lambda^3 G z_j + lambda^2 G z_j+1 +
+    // lambda G z_j+2 + G z_j+3.  w does not depend on the state: eight instructions off the chain from block to block,
+    // which keeps the two dependent FMAs per component on lambda^4 -- half of what two two-row steps have
+    auto four_w = [&](const double2 za, const double2 zc, double &wr, double &wi) {
+        wr = fma(g3r, za.x, fma(g2r, za.y, fma(g1r, zc.x, Gr * zc.y)));
+        wi = fma(g3i, za.x, fma(g2i, za.y, fma(g1i, zc.x, Gi * zc.y)));
+    };
+    auto four_s = [&](const double wr, const double wi) {
+        const double nr = fma(l4r, sr, fma(-l4i, si, wr));
+        si = fma(l4r, si, fma(l4i, sr, wi));
+        sr = nr;
+    };
     int64_t cb = r_lo;
     // A group: its phase, then its blocks.  The full blocks: one basic block each, in stages.  A stage ends in a
     // scheduling barrier, so that its LDS reads are issued a stage before the FMAs that take them and no further ahead
@@ -1819,9 +1884,9 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             if (g + 1 < NG) s_ld(g + 1);
             stage_end();
 #pragma unroll
-            for (int i = 0; i < FG; ++i) {
+            for (int i = 0; i < FG; i += 2) {       // (FG and JT are even: a pair lies in one group)
                 const int k = g * FG + i;
-                if (k < JT) add_term(k, sv[g & 1][i], z0, z1);
+                if (k < JT) add_pair(k, sv[g & 1][i], sv[g & 1][i + 1], z0, z1);
             }
         }
         const double zv = z0 + z1;
@@ -1830,6 +1895,26 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         zsq = fma(zv, zv, zsq);
 #pragma unroll
         for (int i = 0; i < 8; ++i) zz[i] = ((const double2 *)zb)[i];
+        if constexpr (FOUR) {
+            // eight trips of four rows; w of a trip is formed in the stage of the trip in front of it, beside that
+            // trip's two FMAs on the state, and z is read two trips ahead of its w
+            double wr, wi;
+            stage_end();
+            four_w(zz[0], zz[1], wr, wi);
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                if (t == 1 || t == 3) {
+#pragma unroll
+                    for (int i = 6 + 2 * t; i < 10 + 2 * t; ++i) zz[i] = ((const double2 *)zb)[i];
+                }
+                stage_end();
+                double nwr = 0.0, nwi = 0.0;
+                if (t < 7) four_w(zz[2 * t + 2], zz[2 * t + 3], nwr, nwi);
+                four_s(wr, wi);
+                wr = nwr;
+                wi = nwi;
+            }
+        } else {
 #pragma unroll
         for (int j2 = 0; j2 < 16; ++j2) {
             if (j2 >= 4 && j2 < 12 && (j2 & 3) == 0) {
@@ -1838,6 +1923,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
             }
             stage_end();
             two_rows(zz[j2]);
+        }
         }
         join(l32r, l32i);
         if constexpr (CHUNK == 3) {
@@ -1867,9 +1953,20 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         zsq = (lane < lim) ? fma(zv, zv, zsq) : zsq;
         const int mine = half ? (lim > 32 ? lim - 32 : 0) : (lim < 32 ? lim : 32);
         int j = 0;
+        if constexpr (FOUR) {                       // four-row trips while they fit, then row by row
+#pragma unroll 1
+            for (; j + 3 < mine; j += 4) {
+                double wr, wi;
+                four_w(((const double2 *)zb)[j >> 1], ((const double2 *)zb)[(j >> 1) + 1], wr, wi);
+                four_s(wr, wi);
+            }
+#pragma unroll 1
+            for (; j < mine; ++j) one_row(zb[j]);
+        } else {
 #pragma unroll 1
         for (; j + 1 < mine; j += 2) two_rows(((const double2 *)zb)[j >> 1]);
         if (j < mine) one_row(zb[j]);
+        }
         double jr = 1.0, ji = 0.0;                  // lambda^(lim - 32)
         for (int q = 32; q < lim; ++q) {
             const double xr = fma(jr, lr, -ji * li);

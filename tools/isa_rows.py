@@ -6,7 +6,8 @@
     python tools/isa_rows.py --kernel k_factorw --rows 44 --sample   # the sampling instance (gf_sample_fused)
     python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: its full row loop, AND
                                                    # k_steady_tail<60>, k_steady_finish<60>: the block loop, per 64-row
-                                                   # block and per row
+                                                   # block and per row; k_steady_finish's full block by phase
+                                                   # (z = u + Q s, the state update, the join) with its dependent chains
     python tools/isa_rows.py --asm out.s --rank1   # k_steady_rank1: every block of its row loop
     python tools/isa_rows.py --asm out.s --compare parent.s    # which kernels' instructions differ between two listings
 
@@ -165,6 +166,60 @@ def steady_tail(lines, rows, kernel="k_steady_tail"):
               f"{g['mfma'] / 16:.2f} MFMA, {dyn['lds'] + g['lds'] / 16:.0f} LDS")
 
 
+def _regs(operand):
+    """The 32-bit vector registers an operand names: v5 -> {5}, v[4:5] -> {4, 5}, -v[4:5] -> {4, 5}; none for s, literals."""
+    m = re.match(r"^[-|]*v\[(\d+):(\d+)\]", operand)
+    if m:
+        return set(range(int(m.group(1)), int(m.group(2)) + 1))
+    m = re.match(r"^[-|]*v(\d+)\b", operand)
+    return {int(m.group(1))} if m else set()
+
+
+def finish_phases(lines, rows, kernel="k_steady_finish"):
+    """The full block of the finishing launch (one basic block: the one with the most FMAs) by phase: z = u + Q s up to
+    the store of z (ds_write_b64), the state update up to the join (its first v_permlane32_swap), and the rest.  Per
+    phase: vector instructions, FP64 FMAs and multiplies, LDS reads, s_waitcnt, the longest chain of dependent FP64
+    instructions, and the FMAs issued directly behind an FP64 instruction that writes the accumulator they add to."""
+    body = kernel_body(lines, kernel, rows, None)
+    cur, best = [], []
+    for ln in body + [".LBB_end:"]:
+        s = ln.strip()
+        if not ln.startswith("\t") and re.match(r"^(\.LBB\w+|; %bb\.\d+):?", s):
+            if sum(x[0].startswith(("v_fma_f64", "v_fmac_f64")) for x in cur) > \
+                    sum(x[0].startswith(("v_fma_f64", "v_fmac_f64")) for x in best):
+                best = cur
+            cur = []
+        elif s and not s.startswith((";", ".")):
+            parts = s.split(None, 1)
+            cur.append((parts[0], [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []))
+    cut1 = next((i for i, x in enumerate(best) if x[0] == "ds_write_b64"), len(best))
+    cut2 = next((i for i, x in enumerate(best) if x[0].startswith("v_permlane32_swap")), len(best))
+    print(f"{kernel}<{rows}>, the full block ({len(best)} instructions, {sum(x[0].startswith('v_') for x in best)} "
+          f"vector) by phase:")
+    for name, part in (("z = u + Q s", best[:cut1]), ("state update", best[cut1:cut2]), ("join and loop", best[cut2:])):
+        depth, deepest, behind, prev = {}, 0, 0, set()
+        for op, args in part:
+            f64 = op.startswith(("v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64"))
+            if not f64:
+                if op.startswith("v_"):         # (a wait or an LDS read between two FMAs takes no VALU slot)
+                    prev = set()
+                continue
+            dst = _regs(args[0])
+            src = set().union(*[_regs(a) for a in args[1:]]) | (dst if op.startswith("v_fmac") else set())
+            d = 1 + max((depth.get(r, 0) for r in src), default=0)
+            for r in dst:
+                depth[r] = d
+            deepest = max(deepest, d)
+            acc = dst if op.startswith("v_fmac") else _regs(args[-1])
+            behind += bool(acc & prev) and op.startswith(("v_fma_f64", "v_fmac_f64"))
+            prev = dst
+        c = counts([op for op, _ in part])
+        mul = sum(op.startswith("v_mul_f64") for op, _ in part)
+        print(f"  {name:14s}: {c['valu']:3d} VALU ({c['fma']} fma, {mul} mul), {sum(op.startswith('ds_read') for op, _ in part):2d} "
+              f"LDS reads, {sum(op == 's_waitcnt' for op, _ in part):2d} s_waitcnt; longest dependent FP64 chain {deepest}, "
+              f"{behind} FMAs directly behind the write of their accumulator")
+
+
 def functions(lines, twice=None):
     """name -> instruction lines of every function of a listing, with the per-function label numbers taken out (a
     function added in front renumbers the labels of all that follow).  `twice`, if given, collects the names that
@@ -303,6 +358,7 @@ def main():
     if a.steady and not a.all:
         steady_tail(lines, a.rows)
         steady_tail(lines, a.rows, "k_steady_finish")
+        finish_phases(lines, a.rows)
     return 0
 
 
