@@ -319,12 +319,12 @@ class BatchedLogLikelihood:
         Jr, Jc, real, comp, diag_add, _ = _coeff_pack([k.get_device_coefficients() for k in x])
         return Jr, Jc, real, comp, diag_add
 
-    def _grad_check_width(self):
+    def _grad_check_width(self, wide=False, hint=False):
         from .grad import check_width
         Jr, Jc = self.engine._struct0
-        check_width(Jr + 2 * Jc)
+        check_width(Jr + 2 * Jc, wide, hint=hint)
 
-    def value_and_grad_coefficients(self, pack_or_kernels, time_parallel=False, chunk_len=None):
+    def value_and_grad_coefficients(self, pack_or_kernels, time_parallel=False, chunk_len=None, wide=False):
         """log-likelihoods and their gradients with respect to the celerite coefficients.
         Returns ``(ll, grads)``: ll (B,) numpy (-inf where K is not positive definite, whose gradients are NaN);
         grads in the engine's stacked layout: ``real`` (2, B, Jr) = d/d(a, c), ``comp`` (4, B, Jc) =
@@ -333,31 +333,43 @@ class BatchedLogLikelihood:
         ``time_parallel``: cut every series into chunks of ``chunk_len`` rows (None: the library's default for the
         batch) that are swept concurrently -- the route for one long series or a few, where one
         wave per problem leaves the device idle.  Same results to rounding; the default keeps the one-wave route and
-        its bits."""
-        self._grad_check_width()
+        its bits.
+
+        ``wide``: one workgroup per problem, the route for celerite widths beyond 63 -- gadfly's
+        86-term default kernel among them -- up to :func:`gadfly_amd.grad.wide_max_width`; narrow kernels are taken
+        too.  Same results to rounding; not together with ``time_parallel`` or ``chunk_len`` (ValueError)."""
+        if wide and (time_parallel or chunk_len is not None):
+            raise ValueError("wide=True does not combine with time_parallel or chunk_len")
+        self._grad_check_width(wide, hint=True)
         from .grad import coefficient_gradients
         Jr, Jc, real, comp, diag_add = self._host_pack(pack_or_kernels)
         res = coefficient_gradients(self.engine, Jr, Jc, real, comp, diag_add, self.grad_workspace_bytes,
-                                    chunk_len=chunk_len, time_parallel=time_parallel)
+                                    chunk_len=chunk_len, time_parallel=time_parallel, wide=wide)
         #: (workspace bytes of a group, number of groups, problems per group) and the device time of the last call
         self.last_grad_plan = (res["workspace_bytes"], res["groups"], res["group_size"])
         self.last_grad_device_ms = res["device_ms"]
         #: rows per chunk of the last call (None: the one-wave route) and the problems it sent to the one-wave route
         self.last_grad_chunk_len = res.get("chunk_len")
         self.last_grad_reruns = res.get("reruns", 0)
+        #: rows per segment of the last call (None: not the wide route)
+        self.last_grad_seg = res.get("seg")
         ll = res["ll"]
         if self._pad_corr is not None:
             ll = ll + self._pad_corr.cpu().numpy()       # ragged batch: the missing-data rows' constants
         return ll, {k: res[k] for k in ("real", "comp", "diag_add", "mean")}
 
-    def value_and_grad(self, S0, w0, Q, delta, wrt=("S0", "w0", "Q"), time_parallel=False, chunk_len=None):
+    def value_and_grad(self, S0, w0, Q, delta, wrt=("S0", "w0", "Q"), time_parallel=False, chunk_len=None,
+                       wide=False):
         """log-likelihoods at (B, J) SHO hyperparameter arrays (as :meth:`pack_parameters` takes them) and their
         gradients.  Returns ``(ll, grads)``: ll (B,) numpy; grads a dict holding the names of ``wrt`` among
         ``"S0"``, ``"w0"``, ``"Q"`` ((B, J) each), ``"mean"`` ((B,): d/d of a constant mean, sum alpha) and
         ``"diag"`` ((B,): d/d of a constant added to the diagonal).  A problem whose matrix is not positive
         definite gets -inf and NaN gradients; the others are unaffected.  ``time_parallel``, ``chunk_len``: as
-        :meth:`value_and_grad_coefficients` (one long series, or a few)."""
-        self._grad_check_width()
+        :meth:`value_and_grad_coefficients` (one long series, or a few); ``wide``: as there (celerite widths beyond
+        63)."""
+        if wide and (time_parallel or chunk_len is not None):
+            raise ValueError("wide=True does not combine with time_parallel or chunk_len")
+        self._grad_check_width(wide, hint=True)
         from .grad import parameter_vjp
         wrt = tuple(wrt)
         unknown = set(wrt) - {"S0", "w0", "Q", "mean", "diag"}
@@ -367,7 +379,7 @@ class BatchedLogLikelihood:
         if len(shapes) != 1 or next(iter(shapes))[0] != self.B:
             raise ValueError(f"S0, w0, Q of shapes {sorted(shapes)} do not hold the batch's {self.B} problems")
         pk = sho_coefficient_pack(S0, w0, Q, delta)
-        ll, g = self.value_and_grad_coefficients(pk, time_parallel=time_parallel, chunk_len=chunk_len)
+        ll, g = self.value_and_grad_coefficients(pk, time_parallel=time_parallel, chunk_len=chunk_len, wide=wide)
         out = {}
         if {"S0", "w0", "Q"} & set(wrt):
             gS0, gw0, gQ = parameter_vjp(S0, w0, Q, delta, g["real"], g["comp"], g["diag_add"])

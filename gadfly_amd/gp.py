@@ -600,14 +600,19 @@ class GaussianProcess:
         return tuple(np.array([[getattr(x, n) for x in terms]], dtype=np.float64) for n in ("S0", "w0", "Q")) + (
             float(k.delta),)
 
-    def value_and_grad(self, y, wrt=("S0", "w0", "Q"), chunk_len=None):
+    def value_and_grad(self, y, wrt=("S0", "w0", "Q"), chunk_len=None, wide=False):
         """Marginalised log-likelihood of ``y`` and its gradient with respect to the kernel's SHO hyperparameters:
         ``(value, grads)``, grads a dict holding the names of ``wrt`` -- ``"S0"``, ``"w0"``, ``"Q"`` as (J,) arrays in
         the order of the kernel's terms, ``"mean"`` (a constant mean) and ``"diag"`` (a constant added to the
         diagonal) as scalars.  The time axis, diagonal and mean are those of :meth:`compute`, on the device; the
         series is cut into chunks that are swept concurrently (``chunk_len`` rows each, None: the
         library's default).  What ``BatchedLogLikelihood([kernel], t, y, ...).value_and_grad(..., time_parallel=True)``
-        returns for its one problem, to the bit.  Celerite widths up to 63 (NotImplementedError beyond)."""
+        returns for its one problem, to the bit.  Celerite widths up to 63 (NotImplementedError beyond).
+
+        ``wide``: one workgroup for the series instead, for celerite widths up to
+        :func:`gadfly_amd.grad.wide_max_width` -- the 86-term default kernel among them; what
+        ``BatchedLogLikelihood([kernel], t, y, ...).value_and_grad(..., wide=True)`` returns for its one problem, to
+        the bit.  Not together with ``chunk_len`` (ValueError)."""
         from . import grad as _grad
         from .batch import sho_coefficient_pack
         if _units.has_unit(y):
@@ -617,8 +622,10 @@ class GaussianProcess:
         unknown = set(wrt) - {"S0", "w0", "Q", "mean", "diag"}
         if unknown:
             raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        if wide and chunk_len is not None:
+            raise ValueError("wide=True does not combine with chunk_len")
         co = self.kernel.get_device_coefficients()
-        _grad.check_width(len(co[0]) + 2 * len(co[2]))
+        _grad.check_width(len(co[0]) + 2 * len(co[2]), wide, hint=True)
         S0, w0, Q, delta = self._sho_parameters()
         torch = _lib.require_device()
         if self._t_dev is None:
@@ -629,9 +636,12 @@ class GaussianProcess:
         eng = StreamingBatch([co], self._t_dev, self._resid_to_device(y), diag=self._diag_dev, device=self._device,
                              axis_stats=getattr(self, "_axis_stats", None))
         Jr, Jc, real, comp, diag_add = sho_coefficient_pack(S0, w0, Q, delta)[:5]
-        res = _grad.coefficient_gradients(eng, Jr, Jc, real, comp, diag_add, chunk_len=chunk_len, time_parallel=True)
+        res = _grad.coefficient_gradients(eng, Jr, Jc, real, comp, diag_add, chunk_len=chunk_len,
+                                          time_parallel=not wide, wide=wide)
         #: device time, rows per chunk and one-wave re-runs of the last :meth:`value_and_grad`
-        self.last_grad_device_ms, self.last_grad_chunk_len = res["device_ms"], res["chunk_len"]
+        self.last_grad_device_ms, self.last_grad_chunk_len = res["device_ms"], res.get("chunk_len")
+        #: rows per segment of the last call (None: not the wide route)
+        self.last_grad_seg = res.get("seg")
         out = {}
         if {"S0", "w0", "Q"} & set(wrt):
             g = _grad.parameter_vjp(S0, w0, Q, delta, res["real"], res["comp"], res["diag_add"])

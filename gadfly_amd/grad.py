@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .rowcall import GroupedCall, check_pack_batch, group_plan
 
-__all__ = ["sho_coefficient_pack_torch", "check_width", "check_pack_batch", "workspace_plan", "default_chunk_len",
+__all__ = ["sho_coefficient_pack_torch", "check_width", "wide_max_width", "check_pack_batch", "workspace_plan", "default_chunk_len",
            "coefficient_gradients", "parameter_vjp", "LogLikelihood", "LinearModelLogLikelihood",
            "DEFAULT_WORKSPACE_BYTES"]
 
@@ -62,21 +62,37 @@ def sho_coefficient_pack_torch(S0, w0, Q, delta, eps=1e-5):
     return Jr, Jc, real, comp, diag_add
 
 
-def check_width(W):
-    """The one-wave gradient kernel's width limit: NotImplementedError beyond it."""
-    if W > _lib.GF_GRAD_MAX_WIDTH:
+def wide_max_width():
+    """The widest celerite form the wide gradient route takes (``gf_grad_wide_max_width``)."""
+    return int(_lib.load().gf_grad_wide_max_width())
+
+
+def check_width(W, wide=False, hint=False):
+    """The gradient kernels' width limits: NotImplementedError beyond the one-wave kernel's, or with ``wide`` beyond
+    the workgroup kernel's.  ``hint``: the one-wave message also names the wide route (the callers that take
+    ``wide=`` ask for it)."""
+    if wide:
+        if W > wide_max_width():
+            raise NotImplementedError(
+                f"gradients take celerite widths W <= {wide_max_width()} (wide=True, one workgroup per problem); "
+                f"this kernel has W = {W}")
+    elif W > _lib.GF_GRAD_MAX_WIDTH:
         raise NotImplementedError(
             f"gradients take celerite widths W <= {_lib.GF_GRAD_MAX_WIDTH} (one wave per problem); this kernel "
-            f"has W = {W}")
+            f"has W = {W}" + (f": pass wide=True (one workgroup per problem, W <= {wide_max_width()})" if hint else ""))
 
 
-def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, chunk_len=None):
+def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, chunk_len=None, wide=False, seg=None):
     """(doubles per problem, problems per group, number of groups) of a gradient call: the one-wave route's, or,
-    with ``chunk_len``, the time-parallel route's at that chunk length."""
-    check_width(W)
+    with ``chunk_len``, the time-parallel route's at that chunk length, or, with ``wide``, the workgroup route's at
+    ``seg`` rows per segment (None: the library's default)."""
+    check_width(W, wide)
     lib = _lib.load()
-    per = (lib.gf_grad_work(int(N), int(W)) if chunk_len is None
-           else lib.gf_grad_chunked_work(int(N), int(W), int(chunk_len)))
+    if wide:
+        per = lib.gf_grad_wide_work(int(N), int(W), 0 if seg is None else int(seg))
+    else:
+        per = (lib.gf_grad_work(int(N), int(W)) if chunk_len is None
+               else lib.gf_grad_chunked_work(int(N), int(W), int(chunk_len)))
     return group_plan(per, B, cap_bytes, f"no gradient workspace for N = {N}, W = {W}")
 
 
@@ -87,7 +103,7 @@ def default_chunk_len(B, N, W):
 
 
 def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES,
-                          chunk_len=None, time_parallel=False, y=None, rows=None):
+                          chunk_len=None, time_parallel=False, y=None, rows=None, wide=False, seg=None):
     """Run ``gf_loglike_grad`` over an engine's data (t, y - mean, diag on the device) for stacked host
     coefficient arrays of its ORIGINAL term structure.  Returns a dict of numpy arrays: ``ll`` (B,),
     ``real`` (2, B, Jr) = d/d(a, c), ``comp`` (4, B, Jc) = d/d(a, b, c, d), ``diag_add`` (B,), ``mean`` (B,),
@@ -101,8 +117,18 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
 
     ``y``: a float64 device tensor (1 or B, N) that stands in for the engine's data (the residuals of a linear mean
     model); ``rows``: (B,) real rows per problem -- every problem is then swept on its own, over its
-    real rows alone (one-wave route only), and has the bits of a call of its own.  Without them nothing changes."""
+    real rows alone (one-wave route only), and has the bits of a call of its own.  Without them nothing changes.
+
+    ``wide``: the workgroup route (``gf_loglike_grad_wide``) for widths up to
+    :func:`wide_max_width`, narrow ones included, at ``seg`` rows per segment (None: the library's default; the
+    outputs do not depend on it, to the bit).  The result also holds ``seg``.  Not together with ``time_parallel``,
+    ``chunk_len`` or ``rows``."""
     W = Jr + 2 * Jc
+    if wide and (time_parallel or chunk_len is not None or rows is not None):
+        raise ValueError("wide=True does not combine with time_parallel, chunk_len or rows=")
+    if seg is not None and (not wide or int(seg) < 1):
+        raise ValueError("seg belongs to the wide route (wide=True) and is at least 1" if not wide
+                         else f"seg = {seg}")
     if (Jr, Jc) != engine._struct0:
         raise ValueError("coefficient pack does not match the batch structure")
     B, N = engine.B, engine.N
@@ -115,7 +141,11 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
         if chunk_len < 1:
             raise ValueError(f"chunk_len = {chunk_len}")
         name, head = "gf_loglike_grad_chunked", (N, min(chunk_len, N))
-    plan = workspace_plan(N, W, B, cap_bytes, head[1] if time_parallel else None)
+    if wide:
+        check_width(W, True)
+        seg = int(_lib.load().gf_grad_wide_seg(N, W)) if seg is None else min(int(seg), N)
+        name, head = "gf_loglike_grad_wide", (N, seg)
+    plan = workspace_plan(N, W, B, cap_bytes, head[1] if time_parallel else None, wide=wide, seg=seg)
     if rows is not None:
         if time_parallel:
             raise ValueError("rows= belongs to the one-wave route")
@@ -144,7 +174,7 @@ def coefficient_gradients(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAUL
             g_comp[:, g.b0:g.b0 + g.nb] = gc.cpu().numpy()
 
         events = list(rc.run(group))
-        extra = {}
+        extra = dict(seg=seg) if wide else {}
         if time_parallel:
             flagged = np.flatnonzero(info.cpu().numpy() != 0)
             extra = dict(chunk_len=head[1], reruns=len(flagged))
@@ -220,15 +250,15 @@ def parameter_vjp(S0, w0, Q, delta, g_real, g_comp, g_diag_add):
 
 
 class LogLikelihood(torch.autograd.Function):
-    """``LogLikelihood.apply(S0, w0, Q, evaluator, delta[, time_parallel])``: the (B,) log-likelihoods of a
+    """``LogLikelihood.apply(S0, w0, Q, evaluator, delta[, time_parallel[, wide]])``: the (B,) log-likelihoods of a
     :class:`gadfly_amd.BatchedLogLikelihood` at (B, J) tensors of SHO hyperparameters, differentiable with
     respect to S0, w0 and Q (the device gradient of :meth:`BatchedLogLikelihood.value_and_grad`, by its
-    time-parallel route where ``time_parallel`` is true)."""
+    time-parallel route where ``time_parallel`` is true, by its workgroup route for wide kernels where ``wide`` is)."""
 
     @staticmethod
-    def forward(ctx, S0, w0, Q, evaluator, delta, time_parallel=False):
+    def forward(ctx, S0, w0, Q, evaluator, delta, time_parallel=False, wide=False):
         host = [x.detach().cpu().numpy() for x in (S0, w0, Q)]
-        ll, g = evaluator.value_and_grad(*host, delta, time_parallel=bool(time_parallel))
+        ll, g = evaluator.value_and_grad(*host, delta, time_parallel=bool(time_parallel), wide=bool(wide))
         ctx.save_for_backward(*(torch.as_tensor(g[k], dtype=S0.dtype, device=S0.device)
                                 for k in ("S0", "w0", "Q")))
         return torch.as_tensor(ll, dtype=S0.dtype, device=S0.device)
@@ -237,7 +267,7 @@ class LogLikelihood(torch.autograd.Function):
     def backward(ctx, grad_output):
         gS0, gw0, gQ = ctx.saved_tensors
         go = grad_output[:, None]
-        return go * gS0, go * gw0, go * gQ, None, None, None
+        return go * gS0, go * gw0, go * gQ, None, None, None, None
 
 
 class LinearModelLogLikelihood(torch.autograd.Function):

@@ -17,6 +17,8 @@
  *                                                      <- gp.py:232 (predict at new times)
  *   gf_loglike_grad     driver.factor_rev + solve_lower_rev + the norm's adjoint
  *                                                      (no gadfly call site: gradients for samplers)
+ *   gf_loglike_grad_wide   the same for wide kernels, one workgroup per problem (W up to 192: the 86-term default
+ *                                                      kernel of gadfly/core.py, W = 172)
  *   gf_solve_batch      driver.factor + solve_lower + solve_upper + general_matmul_lower / _upper at t* = t
  *                                                      <- gp.py:370, :232 for B kernels at once
  *   gf_var_batch        the same plus the diagonal of K* - K*^T (K + diag)^-1 K* (celerite2's
@@ -832,6 +834,33 @@ int gf_loglike_grad_chunked(int B, int64_t N, int64_t chunk_len, int Jr, int Jc,
                             const double *y, int64_t y_bs, double *work, int64_t work_bs,
                             double *ll, double *g_real, double *g_comp, double *g_diag, double *g_mean,
                             int32_t *info, void *stream);
+
+/*
+ * Gradients for wide kernels: gf_loglike_grad's mathematics, layouts, outputs and failure
+ * convention with one WORKGROUP of several waves per problem, for 1 <= W = Jr + 2 Jc <= gf_grad_wide_max_width()
+ * (>= 176: gadfly's 86-term default kernel is W = 172; -3 beyond, the limit in gf_last_error()).  Narrow widths are
+ * accepted, so that the route can be set against gf_loglike_grad on one problem (same results to rounding, not to
+ * the bit).
+ *   gf_grad_wide_seg(N, W)          default rows per segment (0 for a shape the call refuses)
+ *   gf_grad_wide_work(N, W, seg)    doubles per problem (0 for a shape the call refuses): the checkpoints, one
+ *                                   segment's staged rows and one parked matrix
+ *   seg: rows per segment, 0 = gf_grad_wide_seg(N, W) (values above N mean N).  Every output is bit-identical for
+ *     every seg: it trades workspace against recomputation only
+ *   coefficients, t, diag, y, their strides and every output as gf_loglike_grad; work_bs >= gf_grad_wide_work
+ *   a problem with a non-positive pivot: ll = -inf, info = the 1-based failing row, every gradient NaN; the other
+ *     problems are unaffected
+ * No atomics: results are bit-identical from run to run; a problem's bits depend on its own data, N and W alone.
+ */
+int gf_grad_wide_max_width(void);
+int64_t gf_grad_wide_seg(int64_t N, int W);
+int64_t gf_grad_wide_work(int64_t N, int W, int64_t seg);
+int gf_loglike_grad_wide(int B, int64_t N, int64_t seg, int Jr, int Jc,
+                         const double *ar, const double *cr, const double *ac, const double *bc,
+                         const double *cc, const double *dc, const double *diag_add,
+                         const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                         const double *y, int64_t y_bs, double *work, int64_t work_bs,
+                         double *ll, double *g_real, double *g_comp, double *g_diag, double *g_mean,
+                         int32_t *info, void *stream);
 
 /*
  * alpha = K^-1 y and the conditional means of B problems: what celerite2's
