@@ -17,7 +17,8 @@ CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(CSRC, "libgadfly_hip.so")
 if os.environ.get("GADFLY_SO"):                 # another build of the same library (A/B measurements)
     SO_PATH = os.path.abspath(os.environ["GADFLY_SO"])
-SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_series.hip"),
+SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_stored.hip"),
+           os.path.join(CSRC, "gadfly_linear.hip"), os.path.join(CSRC, "gadfly_series.hip"),
            os.path.join(CSRC, "gadfly_dense.hip"),
            os.path.join(CSRC, "gadfly_ls.hip"), os.path.join(CSRC, "gadfly_grad.hip"),
            os.path.join(CSRC, "gadfly_solve.hip"), os.path.join(CSRC, "gadfly_predict.hip"),

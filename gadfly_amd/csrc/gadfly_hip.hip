@@ -1,31 +1,24 @@
-// gadfly_hip.hip -- hand-written HIP kernels for gfx950 (MI355X, CDNA4) + most of the C-ABI of
-// include/gadfly_hip.h, and the library's error state.  float64 throughout; wave = 64 lanes.
+// gadfly_hip.hip -- the sweep unit: the hand-written fused sweeps for gfx950 (MI355X, CDNA4) with their part of the
+// C-ABI of include/gadfly_hip.h, and the library's error state.  float64 throughout; wave = 64 lanes.
 //
 // What is replaced: the celerite2 C++ driver routines behind gadfly's GaussianProcess
 // (the reference's gadfly/gp.py:202,:232, :327, :350, :370, :391).
 // The arithmetic follows SURVEY.md Appendix A.4-A.8.
 //
 // Kernel inventory
-//   k_build, k_factor          A.4 generator rows U, V (+ a, + propagator rows P); A.5 LDL^T recurrence, state S (W x W)
-//                              in VGPRs, rows split over NW waves, optional fused forward solve (A.6)
-//   k_build2, k_factor2        the same in block-scaled coordinates (no per-row decay), one wave, W <= 64
 //   k_factor3, k_factor7       the FUSED sweep (build + factor + forward solve, rows never written; RowGen): one column
 //                              per lane, and the 2 x 32 lane tiling; SAMPLE instances draw
 //   k_steady_*                 the rows around the steady switch: tail, finish, chunked finish, rank-one rows
 //   k_phi7, k_phi, k_phiw      closed-loop transition sweeps of the time-parallel evaluation
 //   k_factorw                  the fused sweep for wide kernels (several waves)
 //   k_combine, k_tree_*        the chunk maps' combine, sequential and as a tree scan (cb_*: 64 x 64 LDS block algebra)
-//   k_lin*, k_mmR_mfma, k_lincombine*, k_segment_transition, k_chunk_decay   the stored scaled factor's
-//                              chunk-parallel linear sweeps and their combines
-//   k_dense_solve              batched Gauss-Jordan solve of the wide chunk maps (called from gadfly_dense.hip)
+//   k_segment_transition, k_transpose64   the composed transitions of the linear sweeps' segments (kept here: see there)
 //   k_reduce1, k_reduce2, k_finish   sum log d, sum z^2/d (deterministic fixed-shape tree), the log-likelihood
-//   k_solve_vec, k_solve_rhs   A.6/A.7 sweeps on stored rows: one right-hand side lane-resident, or one lane each
-//   k_gmm*, k_add2, k_cross    A.8 conditional mean at new times; cross-covariance block
-//   k_factor2w                 the block-scaled recurrence beyond one wave (64 < W <= 256)
-// Elsewhere: the wave-level primitives (gf_wave.h), the sweeps' shared row helpers and SC_SPAN (gf_sweep.h), the entry
-// points' argument checks and instance dispatch (gf_internal.h), and the power-spectrum and gap-filling kernels
-// (gadfly_series.hip).  gf_internal_error / gf_internal_check_launch / gf_internal_lds_opt_in are defined here for
-// every unit of the library.
+// Elsewhere: the sweeps on materialised rows (gadfly_stored.hip), the stored scaled factor's chunk-parallel linear
+// sweeps (gadfly_linear.hip), the batched dense solve of the wide chunk maps (gadfly_dense.hip), the wave-level
+// primitives (gf_wave.h), the sweeps' shared row helpers and SC_SPAN (gf_sweep.h), the entry points' argument checks
+// and instance dispatch (gf_internal.h), and the power-spectrum and gap-filling kernels (gadfly_series.hip).
+// gf_internal_error / gf_internal_check_launch / gf_internal_lds_opt_in are defined here for every unit of the library.
 //
 // No CUDA compatibility layer, no Triton, no CPU fallback.
 
@@ -41,7 +34,7 @@
 #include "../../include/gadfly_hip.h"
 #include "gf_internal.h"
 
-// sincos / exp with <= 1 ulp error for the argument ranges of k_build2 (validated against
+// sincos / exp with <= 1 ulp error for the argument ranges of the row generators (validated against
 // long-double libm by oracle/fastmath_check.c); ~4x fewer instructions than the general OCML
 // routines, which carry Payne-Hanek reduction for arbitrary arguments.
 #define FM_INLINE __device__ __forceinline__
@@ -108,530 +101,6 @@ int gf_internal_check_launch(const char *what) {
 }
 
 namespace {
-
-// ------------------------------------------------------------------------------------
-// K0: generator rows + propagator rows
-// ------------------------------------------------------------------------------------
-struct BuildArgs {
-    int64_t N, n_first;             // rows built: global n_first .. n_first + N - 1
-    int Jr, Jc, ld, units;          // units per row = Jr + Jc + (ld - W)
-    const double *ar, *cr, *ac, *bc, *cc, *dc, *diag_add;
-    const double *t; int64_t t_bs;
-    const double *diag; int64_t diag_bs;
-    double *a, *U, *V, *P;
-};
-
-__global__ void __launch_bounds__(256) k_build(const BuildArgs A) {
-    const int b = blockIdx.y;
-    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = id / A.units;
-    if (n >= A.N) return;
-    const int q = (int)(id - n * A.units);
-    const int W = A.Jr + 2 * A.Jc;
-    const double *t = A.t + (size_t)b * A.t_bs;
-    const int64_t ng = A.n_first + n;                // global row (t, diag are global arrays)
-    const double tn = t[ng];
-    const double dt = (ng > 0) ? (t[ng - 1] - tn) : 0.0;
-    const size_t row = ((size_t)b * A.N + n) * A.ld;
-    if (q == 0 && A.a) {
-        const double dg = A.diag ? A.diag[(size_t)b * A.diag_bs + ng] : 0.0;
-        A.a[(size_t)b * A.N + n] = dg + A.diag_add[b];
-    }
-    if (q < A.Jr) {                                  // real term: one column
-        const double ar = A.ar[(size_t)b * A.Jr + q], cr = A.cr[(size_t)b * A.Jr + q];
-        A.U[row + q] = ar;
-        A.V[row + q] = 1.0;
-        if (A.P) A.P[row + q] = (ng > 0) ? exp(cr * dt) : 1.0;
-    } else if (q < A.Jr + A.Jc) {                    // complex term: two columns
-        const int k = q - A.Jr;
-        const size_t ck = (size_t)b * A.Jc + k;
-        const double ac = A.ac[ck], bc = A.bc[ck], cc = A.cc[ck], dc = A.dc[ck];
-        const double arg = dc * tn;                  // ONE rounded multiply (parity hazard i)
-        double si, co;
-        sincos(arg, &si, &co);
-        const int j = A.Jr + 2 * k;
-        A.U[row + j]     = ac * co + bc * si;
-        A.U[row + j + 1] = ac * si - bc * co;
-        A.V[row + j]     = co;
-        A.V[row + j + 1] = si;
-        if (A.P) {
-            const double p = (ng > 0) ? exp(cc * dt) : 1.0;
-            A.P[row + j] = p;
-            A.P[row + j + 1] = p;
-        }
-    } else {                                         // pad column
-        const int j = W + (q - A.Jr - A.Jc);
-        A.U[row + j] = 0.0;
-        A.V[row + j] = 0.0;
-        if (A.P) A.P[row + j] = 1.0;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// K1: factor (+ fused forward solve).  One workgroup of NW waves per (problem, chunk).
-//   thread (wave w, lane l) holds S[i][j] for rows i = w*RB + r (r < RB) and
-//   columns j = c*64 + l (c < CT).  Per row n:
-//     S   <- P_n (S + d_{n-1} w_{n-1} w_{n-1}^T) P_n      (fused with the mat-vec below)
-//     tmp  = u_n^T S      (partial over this wave's rows; reduced across waves through LDS)
-//     d_n  = a_n - tmp . u_n        (DPP tree)
-//     w_n  = (v_n - tmp) / d_n
-//   Row-indexed operands (u_i, p_i, w_i) are wave-uniform: each wave stages the lane-form
-//   vectors in its private LDS slice and reads them back as broadcasts.
-// ------------------------------------------------------------------------------------
-struct FactorArgs {
-    int64_t N, chunk_len, n_first;  // n_first: global index of row 0 (tile streaming), for info
-    int W, ld;
-    const double *a, *U, *V, *P;
-    const double *y; int64_t y_bs;
-    double *d, *Wm, *z;
-    const double *S_in, *F_in;      // per (problem, chunk) state, or NULL = zero
-    double *S_out, *F_out;          // or NULL
-    int32_t *info;
-};
-
-template <int RB, int CT, int NW>
-__global__ void __launch_bounds__(64 * NW) k_factor(const FactorArgs A) {
-    constexpr int WPC = CT * 64;
-    constexpr int RT = RB * NW;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int b = blockIdx.y, ch = blockIdx.x;
-    const int nch = gridDim.x;
-    const int64_t n0 = (int64_t)ch * A.chunk_len;
-    const int64_t n1 = (n0 + A.chunk_len < A.N) ? (n0 + A.chunk_len) : A.N;
-    const int ld = A.ld;
-    const size_t pb = (size_t)b * A.N;
-    const double *__restrict__ Ug = A.U + pb * ld;
-    const double *__restrict__ Vg = A.V + pb * ld;
-    const double *__restrict__ Pg = A.P + pb * ld;
-    const double *__restrict__ ag = A.a + pb;
-    const double *__restrict__ yg = A.y ? (A.y + (size_t)b * A.y_bs) : nullptr;
-
-    __shared__ double s_part[2][NW][WPC];
-    __shared__ double s_vec[NW][3][WPC];
-    double *sv_u = s_vec[wave][0], *sv_p = s_vec[wave][1], *sv_w = s_vec[wave][2];
-
-    double S[RB][CT];
-    double Fv[CT], wv[CT];
-    bool colok[CT];
-    int colc[CT];                       // pad lanes read a clamped (valid) column and are masked at use
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        colok[c] = (c * 64 + lane) < ld;
-        colc[c] = colok[c] ? (c * 64 + lane) : (ld - 1);
-        wv[c] = 0.0;
-        Fv[c] = 0.0;
-    }
-    const size_t sidx = (size_t)b * nch + ch;
-    if (A.info[sidx] != 0) return;      // an earlier tile of this problem already failed
-    if (A.S_in) {
-        const double *Si = A.S_in + sidx * RT * WPC;
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-#pragma unroll
-            for (int c = 0; c < CT; ++c) S[r][c] = Si[(size_t)(wave * RB + r) * WPC + c * 64 + lane];
-        if (A.F_in) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) Fv[c] = A.F_in[sidx * WPC + c * 64 + lane];
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-#pragma unroll
-            for (int c = 0; c < CT; ++c) S[r][c] = 0.0;
-    }
-#pragma unroll
-    for (int c = 0; c < CT; ++c) sv_w[c * 64 + lane] = 0.0;
-
-    double dprev = 0.0, zprev = 0.0;
-    int32_t fail = 0;
-
-    // software prefetch of row n0: plain unconditional loads that nothing touches before the row
-    // is processed (a `colok ? load : 0` here makes the wave wait for HBM right where it issued the load)
-    double un[CT], vn[CT], pn[CT], an, yn;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const size_t o = (size_t)n0 * ld + colc[c];
-        un[c] = Ug[o];
-        vn[c] = Vg[o];
-        pn[c] = Pg[o];
-    }
-    // the per-row scalars travel in the vector-load queue too (opaque zero lane offset): a scalar load
-    // would be waited for at the next LDS access, which shares its counter
-    const int vz = __builtin_amdgcn_mbcnt_lo(0u, 0u);
-    const double *__restrict__ ys = yg ? yg : ag;          // always a valid address; dropped below
-    an = ag[n0 + vz];
-    yn = ys[n0 + vz];
-
-    for (int64_t n = n0; n < n1; ++n) {
-        double u[CT], v[CT], p[CT];
-        const double a_n = an, y_n = yg ? yn : 0.0;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            u[c] = colok[c] ? un[c] : 0.0; v[c] = colok[c] ? vn[c] : 0.0; p[c] = colok[c] ? pn[c] : 1.0;
-            sv_u[c * 64 + lane] = u[c];
-            sv_p[c * 64 + lane] = p[c];
-        }
-        // prefetch the next row (clamped: the last iteration re-reads its own row)
-        const int64_t nn = (n + 1 < n1) ? (n + 1) : n;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const size_t o = (size_t)nn * ld + colc[c];
-            un[c] = Ug[o];
-            vn[c] = Vg[o];
-            pn[c] = Pg[o];
-        }
-        an = ag[nn + vz];
-        yn = ys[nn + vz];
-
-        wave_lds_fence();
-
-        // fused: pending rank-1 update + decay, then the mat-vec partial for this wave's rows
-        double acc[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc[c] = 0.0;
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-            const int i = wave * RB + r;
-            const double ui = sv_u[i], pi = sv_p[i];
-            const double wid = sv_w[i] * dprev;
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const double s = (S[r][c] + wid * wv[c]) * (pi * p[c]);
-                S[r][c] = s;
-                acc[c] = fma(ui, s, acc[c]);
-            }
-        }
-        double tmp[CT];
-        if constexpr (NW > 1) {
-            const int buf = (int)(n & 1);
-#pragma unroll
-            for (int c = 0; c < CT; ++c) s_part[buf][wave][c * 64 + lane] = acc[c];
-            wg_lds_barrier();           // (not __syncthreads: the next row's prefetch stays in flight)
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                double s = s_part[buf][0][c * 64 + lane];
-#pragma unroll
-                for (int w2 = 1; w2 < NW; ++w2) s += s_part[buf][w2][c * 64 + lane];
-                tmp[c] = s;
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) tmp[c] = acc[c];
-        }
-        // F_n = P_n (F_{n-1} + w_{n-1} z_{n-1});  two dot products in one DPP tree
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            Fv[c] = p[c] * fma(wv[c], zprev, Fv[c]);
-            s1 = fma(u[c], tmp[c], s1);
-            s2 = fma(u[c], Fv[c], s2);
-        }
-        wave_sum2(s1, s2);
-        const double dn = a_n - s1;
-        const double zn = y_n - s2;
-        if (!(dn > 0.0)) {              // uniform across the whole workgroup
-            const int64_t ng = A.n_first + n + 1;
-            fail = (int32_t)(ng > 0x7fffffff ? 0x7fffffff : ng);
-            break;
-        }
-        const double inv_dn = fast_rcp(dn);     // one reciprocal (<= 1 ulp) instead of CT IEEE divisions
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            wv[c] = (v[c] - tmp[c]) * inv_dn;
-            sv_w[c * 64 + lane] = wv[c];
-        }
-        if (wave == 0) {
-            if (A.Wm) {
-#pragma unroll
-                for (int c = 0; c < CT; ++c)
-                    if (colok[c]) A.Wm[(pb + n) * ld + c * 64 + lane] = wv[c];
-            }
-            if (lane == 0) {
-                A.d[pb + n] = dn;
-                if (A.z) A.z[pb + n] = zn;
-            }
-        }
-        dprev = dn;
-        zprev = zn;
-    }
-
-    if (fail && wave == 0 && lane == 0) A.info[sidx] = fail;
-    if (fail) return;
-
-    if (A.S_out) {                      // state handed to the next chunk: pending update, no decay
-        wave_lds_fence();
-        double *So = A.S_out + sidx * RT * WPC;
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-            const int i = wave * RB + r;
-            const double wid = sv_w[i] * dprev;
-#pragma unroll
-            for (int c = 0; c < CT; ++c) So[(size_t)i * WPC + c * 64 + lane] = fma(wid, wv[c], S[r][c]);
-        }
-        if (A.F_out && wave == 0) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) A.F_out[sidx * WPC + c * 64 + lane] = fma(wv[c], zprev, Fv[c]);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// v2 log-likelihood path (W <= 64): block-scaled coordinates, one wave per problem.
-//
-// Within a block of rows [r, r') (r = "reset row") the state is kept in coordinates scaled by
-// rho_n = exp(-c (t_n - t_r)):   S_n = rho_n T_n rho_n,  u~_n = u_n o rho_n,  v~_n = v_n / rho_n,
-// w~_n = w_n / rho_n.  In these coordinates the celerite recurrence has NO per-row decay:
-//     T   <- T + d_{n-1} w~_{n-1} w~_{n-1}^T
-//     tmp  = T u~_n ;  d_n = a_n - u~_n . tmp ;  w~_n = (v~_n - tmp) / d_n
-//     F~  <- F~ + w~_{n-1} z_{n-1} ;  z_n = y_n - u~_n . F~
-// i.e. 2 FMAs per element of T per row instead of an update, two decays and a mat-vec.  At a
-// reset row the accumulated decay E = exp(-c (t_r' - t_r)) is applied once (T <- E T E).  This is
-// the un-preconditioned celerite (2017) recurrence made safe by bounding the block span:
-// reset(n) = (n % 8 == 0) or cmax (t_n - t_{n-1}) > 4  =>  |log rho| <= 28 inside a block.
-// k_build2 writes u~, v~ (and E at reset rows); k_factor2 reads the row operands u~_i as
-// wave-uniform scalar loads (SGPR operands of v_fma_f64), so only w~ needs an LDS broadcast.
-// ------------------------------------------------------------------------------------
-struct Build2Args {
-    int64_t N, n_first;
-    int Jr, Jc, ld, units, block;   // block: power of two, rows between forced resets
-    double gap;                     // cmax * dt above which a row is a reset of its own
-    const double *ar, *cr, *ac, *bc, *cc, *dc, *diag_add, *cmax;
-    const double *t; int64_t t_bs;
-    const double *diag; int64_t diag_bs;
-    double *a, *Ut, *Vt, *de;       // de[n] = t_ref(n) - t_ref(n-1) at reset rows, -1 elsewhere
-};
-
-__device__ __forceinline__ bool sc_is_reset(const double *t, int64_t g, double cmax, int block,
-                                            double gap) {
-    return (g & (block - 1)) == 0 || cmax * (t[g] - t[g - 1]) > gap;
-}
-
-// latest reset row <= g (bounded walk: g - g % block is always a reset)
-__device__ __forceinline__ int64_t sc_ref(const double *t, int64_t g, double cmax, int block,
-                                          double gap) {
-    while (!sc_is_reset(t, g, cmax, block, gap)) --g;
-    return g;
-}
-
-constexpr int B2_ROWS = 32;         // rows per workgroup of k_build2
-
-__global__ void __launch_bounds__(256) k_build2(const Build2Args A) {
-    const int b = blockIdx.y;
-    const int64_t n0 = (int64_t)blockIdx.x * B2_ROWS;          // first tile-local row of the block
-    const int nrows = (int)((A.N - n0 < B2_ROWS) ? (A.N - n0) : B2_ROWS);
-    const int W = A.Jr + 2 * A.Jc;
-    const double *t = A.t + (size_t)b * A.t_bs;
-    const double cmax = A.cmax[b];
-
-    // phase 1: one thread per row -- reset rule, distance to the block reference, block decay
-    __shared__ double s_t[B2_ROWS], s_ds[B2_ROWS];
-    if ((int)threadIdx.x < nrows) {
-        const int r = threadIdx.x;
-        const int64_t g = A.n_first + n0 + r;
-        const double tn = t[g];
-        const bool reset = sc_is_reset(t, g, cmax, A.block, A.gap);
-        const int64_t ref = reset ? g : sc_ref(t, g, cmax, A.block, A.gap);
-        const double de = reset ? ((g > 0) ? (tn - t[sc_ref(t, g - 1, cmax, A.block, A.gap)]) : 0.0)
-                                : -1.0;
-        s_t[r] = tn;
-        s_ds[r] = tn - t[ref];                                   // >= 0, 0 at a reset row
-        const size_t o = (size_t)b * A.N + n0 + r;
-        const double dg = A.diag ? A.diag[(size_t)b * A.diag_bs + g] : 0.0;
-        A.a[o] = dg + A.diag_add[b];
-        A.de[o] = de;
-    }
-    __syncthreads();
-
-    // phase 2: one thread per (row, term); the first (ld - W) units of a row also zero a pad column
-    const unsigned units = (unsigned)(A.Jr + A.Jc);
-    const unsigned total = (unsigned)nrows * units;
-    const int npad = A.ld - W;
-    for (unsigned idx = threadIdx.x; idx < total; idx += 256) {
-        const unsigned r = idx / units;
-        const int q = (int)(idx - r * units);
-        const double tn = s_t[r], ds = s_ds[r];
-        const size_t row = ((size_t)b * A.N + n0 + r) * A.ld;
-        if (q < A.Jr) {
-            const double ar = A.ar[(size_t)b * A.Jr + q], cr = A.cr[(size_t)b * A.Jr + q];
-            const double rho = fm_exp(-cr * ds);
-            A.Ut[row + q] = ar * rho;
-            A.Vt[row + q] = 1.0 / rho;
-        } else {
-            const int k = q - A.Jr;
-            const size_t ck = (size_t)b * A.Jc + k;
-            const double ac = A.ac[ck], bc = A.bc[ck], cc = A.cc[ck], dc = A.dc[ck];
-            const double arg = dc * tn;              // ONE rounded multiply (parity hazard i)
-            double si, co;
-            if (fabs(arg) < FM_SINCOS_RANGE) fm_sincos(arg, &si, &co);
-            else sincos(arg, &si, &co);                        // e.g. JD-based time axes
-            const double rho = fm_exp(-cc * ds), irho = 1.0 / rho;
-            const int j = A.Jr + 2 * k;
-            double2 u2, v2;
-            u2.x = (ac * co + bc * si) * rho;
-            u2.y = (ac * si - bc * co) * rho;
-            v2.x = co * irho;
-            v2.y = si * irho;
-            if ((j & 1) == 0) {                      // 16-byte aligned pair
-                *reinterpret_cast<double2 *>(A.Ut + row + j) = u2;
-                *reinterpret_cast<double2 *>(A.Vt + row + j) = v2;
-            } else {
-                A.Ut[row + j] = u2.x; A.Ut[row + j + 1] = u2.y;
-                A.Vt[row + j] = v2.x; A.Vt[row + j + 1] = v2.y;
-            }
-        }
-        if (q < npad) {
-            A.Ut[row + W + q] = 0.0;
-            A.Vt[row + W + q] = 0.0;
-        }
-    }
-    // more pad columns than units (tiny kernels only)
-    if (npad > (int)units) {
-        for (unsigned idx = threadIdx.x; idx < (unsigned)nrows * (unsigned)npad; idx += 256) {
-            const unsigned r = idx / (unsigned)npad;
-            const int q = (int)(idx - r * (unsigned)npad);
-            const size_t row = ((size_t)b * A.N + n0 + r) * A.ld;
-            A.Ut[row + W + q] = 0.0;
-            A.Vt[row + W + q] = 0.0;
-        }
-    }
-}
-
-// Per row n (scaled coordinates; r = v~ - tmp, so w~ = r/d and d w~ = r):
-//     sweep :  T_i += r_{n-1,i} * q_{n-1}  (q = r/d, lane-form) ;  tmp = sum_i u~_{n,i} T_i
-//     r_n = v~_n - tmp ;  stage r_n and u~_{n+1} in LDS, start reading the next row's operands
-//     d_n = a_n - u~_n . tmp ;  z_n = y_n - u~_n . F~ ;  q_n = r_n / d_n
-// The division and the DPP reduction sit between two sweeps; staging r (not w~) lets the LDS
-// traffic of the next sweep start before they finish.
-// Forward solve for free (W < 64): lane 63 is a pad column of T; loading it with F~ (as
-// T[i][63] = F~_i) and giving it the multiplier q_63 = z/d makes the sweep's rank-1 update
-// perform F~ += r z/d and its mat-vec return u~ . F~ in lane 63's partial sum, so the
-// solve needs neither its own recurrence nor a second DPP reduction.
-template <int ROWS>
-__global__ void __launch_bounds__(64, 2)     // 2 waves/SIMD: one wave alone gets half the VALU issue rate
-k_factor2(const int64_t N, const int64_t n_first, const int ld, const int W,
-          const double *__restrict__ c_,
-          const double *__restrict__ a_, const double *__restrict__ Ut_,
-          const double *__restrict__ Vt_, const double *__restrict__ de_,
-          const double *__restrict__ y_, const int64_t y_bs,
-          double *__restrict__ d_, double *__restrict__ z_,
-          double *__restrict__ S_state, double *__restrict__ F_state,
-          int32_t *__restrict__ info) {
-    const int lane = threadIdx.x;
-    const int b = blockIdx.x;
-    if (info[b] != 0) return;
-    const size_t pb = (size_t)b * N;
-    const double *__restrict__ ag = a_ + pb;
-    const double *__restrict__ Ug = Ut_ + pb * ld;
-    const double *__restrict__ Vg = Vt_ + pb * ld;
-    const double *__restrict__ eg = de_ + pb;
-    const double *__restrict__ yg = y_ + (size_t)b * y_bs;
-    double *__restrict__ dg = d_ + pb;
-    double *__restrict__ zg = z_ + pb;
-    // state layout [lane][64 rows]: one base address per lane, immediate offsets per row
-    double *__restrict__ Sg = S_state + (size_t)b * (64 * 64) + (size_t)lane * 64;
-    double *__restrict__ Fg = F_state + (size_t)b * 64;
-
-    __shared__ double s_w[64];      // r_{n-1}  (pending rank-1 update, row form)
-    __shared__ double s_u[64];      // u~_n
-    __shared__ double s_e[64];      // block decay E at reset rows
-    const bool colok = lane < ld;
-    const double cj = (lane < W) ? c_[(size_t)b * W + lane] : 0.0;
-
-    // PADF: the forward solve rides in pad lane 63 (needs W < 64, i.e. ld <= 64 and lane 63 unused)
-    const bool PADF = (ROWS < 64) || (W < 64);   // compile-time true except for ROWS == 64
-    const bool fl = PADF && lane == 63;
-    double T[ROWS];
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) T[i] = Sg[i];
-    double Fv = Fg[lane];                       // only used when !PADF
-    if (PADF) {
-        // F~ (row form in F_state) becomes lane 63's column of T
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) T[i] = fl ? Fg[i] : T[i];
-    }
-    double rprev = 0.0, q = 0.0, zq = 0.0;      // pending: T += r r^T/d, F~ += r z/d
-    int32_t fail = 0;
-
-    // Everything a row needs is prefetched two rows ahead, unconditionally (the caller pads
-    // every buffer, y included, by two rows/elements): a clamped index makes hipcc give up its
-    // scalarisation of uniform loads, and an un-prefetched scalar costs a full memory round
-    // trip per row.  Pad lanes (>= ld) re-read column ld-1 and are masked in registers.
-    const int lanec = colok ? lane : (ld - 1);
-    double ut_n = Ug[lanec], ut_n2 = Ug[ld + lanec];
-    double vt_n = Vg[lanec], vt_n2 = Vg[ld + lanec];
-    double a_nx = ag[0], y_nx = yg[0], e_nx = eg[0];
-    double a_nx2 = ag[1], y_nx2 = yg[1], e_nx2 = eg[1];
-
-    double ab[SW_AHEAD + 1][SW_BR], wb[SW_AHEAD + 1][SW_BR];
-    s_w[lane] = 0.0;
-    s_u[lane] = colok ? ut_n : 0.0;
-    wave_lds_fence();
-    sweep_preload<ROWS>(ab, wb, s_u, s_w);
-
-    for (int64_t n = 0; n < N; ++n) {
-        const double ut = colok ? ut_n : 0.0, vt = colok ? vt_n : 0.0;
-        const double a_n = a_nx, y_n = y_nx, e_n = e_nx;
-        ut_n = ut_n2; vt_n = vt_n2; a_nx = a_nx2; y_nx = y_nx2; e_nx = e_nx2;
-        ut_n2 = Ug[(size_t)(n + 2) * ld + lanec];
-        vt_n2 = Vg[(size_t)(n + 2) * ld + lanec];
-        a_nx2 = ag[n + 2];
-        y_nx2 = yg[n + 2];
-        e_nx2 = eg[n + 2];
-        if (e_n >= 0.0) {                   // wave-uniform: reset row
-            // fold the pending update, then decay by E = exp(-c * de) (de = t_ref - t_ref_prev)
-            const double el = colok ? exp(-cj * e_n) : 1.0;
-            s_e[lane] = el;
-            wave_lds_fence();
-            sweep_preload<ROWS>(ab, wb, s_e, s_w);      // ring reused, re-fetched below
-            (void)sweep_run<ROWS, true>(T, ab, wb, s_e, s_w, q, el);
-            sweep_preload<ROWS>(ab, wb, s_u, s_w);
-            Fv = el * fma(rprev, zq, Fv);
-            q = 0.0;
-            zq = 0.0;
-        }
-        const double tmp = sweep_run<ROWS, false>(T, ab, wb, s_u, s_w, q, 0.0);
-        const double r = fl ? 0.0 : (vt - tmp); // pad lanes: 0 - 0; lane 63 carries u~ . F~
-        Fv = fma(rprev, zq, Fv);
-        // stage the next row's operands and start fetching them under the reduction
-        wave_lds_fence();
-        s_w[lane] = r;
-        s_u[lane] = colok ? ut_n : 0.0;
-        wave_lds_fence();
-        sweep_preload<ROWS>(ab, wb, s_u, s_w);
-        double s1 = ut * tmp, s2;
-        if (PADF) {                             // wave-uniform
-            s1 = wave_sum(s1);                  // ut = 0 in lane 63
-            s2 = read_lane(tmp, 63);
-        } else {
-            s2 = ut * Fv;
-            wave_sum2(s1, s2);
-        }
-        const double dn = a_n - s1;
-        const double zn = y_n - s2;
-        if (!(dn > 0.0)) {
-            const int64_t gg = n_first + n + 1;
-            fail = (int32_t)(gg > 0x7fffffff ? 0x7fffffff : gg);
-            break;
-        }
-        const double inv = 1.0 / dn;
-        zq = zn * inv;
-        q = fl ? zq : r * inv;
-        rprev = r;
-        if (lane == 0) { dg[n] = dn; zg[n] = zn; }
-    }
-    if (fail) {
-        if (lane == 0) info[b] = fail;
-        return;
-    }
-    wave_lds_fence();
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) {
-        const double v = fma(s_w[i], q, T[i]);
-        if (fl) Fg[i] = v; else Sg[i] = v;
-    }
-    if (!PADF) Fg[lane] = fma(rprev, zq, Fv);
-}
 
 // ------------------------------------------------------------------------------------
 // k_factor3: the fully fused log-likelihood sweep (W < 64).  Same recurrence as k_factor2, but
@@ -1456,9 +925,6 @@ __device__ __forceinline__ cdd cdd_mul(const cdd a, const cdd b) {
     dd_pair(a.rh, b.ih, a.ih, b.rh, 1.0, fma(a.rh, b.il, a.rl * b.ih) + fma(a.ih, b.rl, a.il * b.rh), c.ih, c.il);
     return c;
 }
-
-#define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // STORE = true: the rows leave as d and z (k_steady_tail, tile by tile); STORE = false: no row is stored, every lane
 // keeps the running sum of z^2 of its row slot over all blocks, and the wave adds the problem's tail to acc
@@ -3785,525 +3251,12 @@ __global__ void __launch_bounds__(256) k_tree_apply(const TreeArgs A) {
 }
 
 // ------------------------------------------------------------------------------------
-// Triangular sweeps on the STORED scaled factor (u~, w~ = r/d rows, d, reset spans de), chunked:
-// every (problem, chunk) starts from the state in F_state and leaves its end state there.
-// In scaled coordinates the recurrences have no per-row decay (A.6/A.7 with P folded into the
-// block scaling); at a reset row the state is multiplied by E = exp(-c de) once:
-//   lower  : F <- [E](F + w~_{n-1} z_{n-1}) ;  z_n = y_n - u~_n . F           (ascending)
-//   upper  : G <- [E_{n+1}](G + u~_{n+1} z_{n+1}) ;  z_n = y_n - w~_n . G     (descending; the
-//            decay of reset row n+1 is crossed when stepping from n+1 down to n)
-//   matmul : F <- [E](F + w~_{n-1} y_{n-1}) ;  z_n = y_n + u~_n . F           (ascending)
-// with optional input scaling y <- y / d (upper: apply_inverse) or y <- y sqrt(d) (matmul:
-// dot_tril).  R = 1: the state is lane-resident, one DPP tree per row.
+// What the two-level combine of the stored scaled factor's linear sweeps (k_lincombine, gadfly_linear.hip) needs once
+// per factor: the segments' composed transitions, and the transposes for the backward solve.  These two kernels and
+// gf_chunk_segment_transitions stay in this unit although their family has left it: k_segment_transition compiles to
+// one instruction more in any other unit, also with the cb_* helpers it calls moved along in a header
+// (profiles/r30_isa_compare.txt), and the moves keep every kernel's instructions as they were.
 // ------------------------------------------------------------------------------------
-struct LinArgs {
-    int64_t N, chunk_len;
-    int nch, W, mode, scale, store;     // store: write z (final pass) or only the end state
-    const double *c;                    // [B][W]
-    const double *Ut, *Wt, *d, *de, *Y; // rows [B][N][64] / [B][N]; Y [B][N][R]
-    double *Z;
-    double *F_state;                    // [B*nch][64 * R]  (R = 1: [64])
-    int R;
-};
-
-// Rows in flight per lane.  The sweep itself is a DPP reduction and two FMAs per row (~400 cycles): what it waits
-// for is memory.  u~ / w~ of a row are one double per lane each: a register ring LIN1_RING rows deep, every slot
-// refilled with the row LIN1_RING ahead as soon as its row is used (static indices: the row loop is unrolled over the
-// ring).  The per-row scalars y, de, d are wave-uniform: fetched 64 rows at a time, lane j its row, one block ahead,
-// parked in LDS and read back as broadcasts a row before their use.  (Two batches of eight rows with five registers
-// per row and lane -- 241 VGPRs -- left every eighth row waiting on HBM: 0.18 of a pass' 0.45 ms at N = 1e6.)
-constexpr int LIN1_RING = 24;
-__global__ void __launch_bounds__(64) k_lin1(const LinArgs A) {
-    const int lane = threadIdx.x, b = blockIdx.x;
-    const int pr = b / A.nch, ch = b - pr * A.nch;
-    const int64_t c0 = (int64_t)ch * A.chunk_len;
-    const int64_t rows = (A.N - c0 < A.chunk_len) ? (A.N - c0) : A.chunk_len;
-    const size_t pb = (size_t)pr * A.N + c0;
-    const double *__restrict__ Ug = A.Ut + pb * 64 + lane;
-    const double *__restrict__ Wg = A.Wt + pb * 64 + lane;
-    const double *__restrict__ dg = A.d + pb;
-    const double *__restrict__ eg = A.de + pb;
-    const double *__restrict__ Yg = A.Y + pb;
-    double *__restrict__ Zg = A.Z + pb;
-    double *__restrict__ Fg = A.F_state + (size_t)b * 64;
-    const double cj = (lane < A.W) ? A.c[(size_t)pr * A.W + lane] : 0.0;
-    const bool up = A.mode == GF_SOLVE_UPPER, mm = A.mode == GF_MATMUL_LOWER;
-    double F = A.store ? Fg[lane] : 0.0;            // (the local pass starts from zero)
-    constexpr int D = LIN1_RING;
-    // step s of the sweep works on row n(s): ascending, or descending for the upper solve (clamped: reads past
-    // the chunk's last step fetch its last row again and are never used)
-    auto row_of = [&](int64_t s) { s = (s > rows - 1) ? rows - 1 : s; return up ? (rows - 1 - s) : s; };
-    __shared__ double sc[2][3][64];                 // y, de, d of 64 steps, two blocks
-    double ys, es, dv;                              // the block after those: this lane's step
-    auto load_sc = [&](const int64_t blk) {
-        const int64_t n = row_of(64 * blk + lane);
-        ys = Yg[n]; es = eg[n]; dv = A.scale ? dg[n] : 1.0;
-    };
-    auto put_sc = [&](const int buf) { sc[buf][0][lane] = ys; sc[buf][1][lane] = es; sc[buf][2][lane] = dv; };
-    load_sc(0);
-    double qu[D], qw[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) { const int64_t n = row_of(j); qu[j] = Ug[(size_t)n * 64]; qw[j] = Wg[(size_t)n * 64]; }
-    put_sc(0);
-    load_sc(1);
-    wave_lds_fence();
-    double y_n = sc[0][0][0], e_n = sc[0][1][0], d_n = sc[0][2][0];       // step 0's scalars
-    double carry = 0.0, prev = 0.0, de_up = -1.0;   // pending F += prev * carry (w~_{n-1} z_{n-1}, or u~_{n+1} z_{n+1})
-    for (int64_t s0 = 0; s0 < rows; s0 += D) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const int64_t s = s0 + j;
-            if (s < rows) {                         // (wave-uniform)
-                const int64_t n = up ? (rows - 1 - s) : s;
-                const double u = qu[j], w = qw[j];
-                double yn = y_n;
-                const double de = e_n, dd = d_n;
-                // the next step's scalars (a block boundary first hands the parked block over)
-                const int li = (int)(s & 63);
-                if (li == 63) { put_sc((int)(((s >> 6) + 1) & 1)); load_sc((s >> 6) + 2); wave_lds_fence(); }
-                {
-                    const int64_t s1 = s + 1;
-                    const int b1 = (int)((s1 >> 6) & 1), l1 = (int)(s1 & 63);
-                    y_n = sc[b1][0][l1]; e_n = sc[b1][1][l1]; d_n = sc[b1][2][l1];
-                }
-                if (!up) {
-                    if (A.scale) yn = mm ? yn * sqrt(dd) : yn / dd;
-                    F = fma(prev, carry, F);
-                    if (de >= 0.0) F *= fm_exp(-cj * de);
-                    const double dot = wave_sum(u * F);
-                    const double zn = mm ? (yn + dot) : (yn - dot);
-                    if (A.store && lane == 0) Zg[n] = zn;
-                    carry = mm ? yn : zn;
-                    prev = w;
-                } else {
-                    // the state handed DOWN to this chunk already carries the decay of the boundary it crossed
-                    if (A.scale) yn = yn / dd;
-                    F = fma(prev, carry, F);
-                    if (de_up >= 0.0) F *= fm_exp(-cj * de_up);
-                    const double dot = wave_sum(w * F);
-                    const double zn = yn - dot;
-                    if (A.store && lane == 0) Zg[n] = zn;
-                    carry = zn;
-                    prev = u;
-                    de_up = de;
-                }
-            }
-            {   // the slot's next tenant: the row LIN1_RING steps ahead
-                const int64_t n2 = row_of(s + D);
-                qu[j] = Ug[(size_t)n2 * 64];
-                qw[j] = Wg[(size_t)n2 * 64];
-            }
-        }
-    }
-    F = fma(prev, carry, F);                        // pending folded (lower: decay left to the next chunk)
-    if (up && de_up >= 0.0) F *= fm_exp(-cj * de_up);       // upper: cross the chunk's first-row boundary
-    Fg[lane] = F;
-}
-
-// R right-hand sides: lane r owns column r of Y/Z and F[:, r] (ROWS doubles in VGPRs); the
-// generator rows are staged per row in LDS and read back as wave-uniform operands.
-template <int ROWS>
-__global__ void __launch_bounds__(64) k_linR(const LinArgs A) {
-    const int lane = threadIdx.x;
-    const int b = blockIdx.x;                       // (problem, chunk)
-    const int rt = blockIdx.y;                      // RHS tile of 64 columns
-    const int pr = b / A.nch, ch = b - pr * A.nch;
-    const int R = A.R;
-    const int r = rt * 64 + lane;
-    const bool rok = r < R;
-    const int64_t c0 = (int64_t)ch * A.chunk_len;
-    const int64_t rows = (A.N - c0 < A.chunk_len) ? (A.N - c0) : A.chunk_len;
-    const size_t pb = (size_t)pr * A.N + c0;
-    const double *__restrict__ Ug = A.Ut + pb * 64 + lane;
-    const double *__restrict__ Wg = A.Wt + pb * 64 + lane;
-    const double *__restrict__ dg = A.d + pb;
-    const double *__restrict__ eg = A.de + pb;
-    const double *__restrict__ Yg = A.Y + pb * R;
-    double *__restrict__ Zg = A.Z + pb * R;
-    double *__restrict__ Fg = A.F_state + (size_t)b * 64 * R;      // [i][R]
-    const double cj = (lane < A.W) ? A.c[(size_t)pr * A.W + lane] : 0.0;
-    const bool up = A.mode == GF_SOLVE_UPPER, mm = A.mode == GF_MATMUL_LOWER;
-    __shared__ double s_a[64], s_b[64], s_e[64];
-    double F[ROWS];
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) F[i] = (rok && A.store) ? Fg[(size_t)i * R + r] : 0.0;
-    double carry = 0.0;
-    s_a[lane] = 0.0;                                // pending push row (w~_{n-1} or u~_{n+1})
-    double de_cross = -1.0;
-    // everything a row needs from memory is fetched three rows ahead (the loads used to sit at
-    // their point of use: one full memory round trip per row, 5 us)
-    struct RowIn { double y, pull, push, e, d; };
-    auto fetch = [&](int64_t s) {
-        if (s > rows - 1) s = rows - 1;
-        const int64_t n = up ? (rows - 1 - s) : s;
-        RowIn q;
-        q.y = rok ? Yg[(size_t)n * R + r] : 0.0;
-        q.pull = up ? Wg[(size_t)n * 64] : Ug[(size_t)n * 64];
-        q.push = up ? Ug[(size_t)n * 64] : Wg[(size_t)n * 64];
-        q.e = eg[n];
-        q.d = A.scale ? dg[n] : 1.0;
-        return q;
-    };
-    RowIn p0 = fetch(0), p1 = fetch(1), p2 = fetch(2);
-    for (int64_t s = 0; s < rows; ++s) {
-        const int64_t n = up ? (rows - 1 - s) : s;
-        const RowIn cur = p0;
-        p0 = p1; p1 = p2; p2 = fetch(s + 3);
-        double yn = cur.y;
-        if (A.scale) yn = mm ? yn * sqrt(cur.d) : yn / cur.d;
-        const double de = up ? de_cross : cur.e;    // decay to apply before this row's dot
-        wave_lds_fence();
-        s_b[lane] = cur.pull;
-        const bool dec = de >= 0.0;
-        if (dec) s_e[lane] = fm_exp(-cj * de);
-        wave_lds_fence();
-        double dot = 0.0, dot2 = 0.0;
-        if (dec) {
-#pragma unroll
-            for (int i = 0; i < ROWS; i += 2) {
-                F[i] = fma(s_a[i], carry, F[i]) * s_e[i];
-                dot = fma(s_b[i], F[i], dot);
-                F[i + 1] = fma(s_a[i + 1], carry, F[i + 1]) * s_e[i + 1];
-                dot2 = fma(s_b[i + 1], F[i + 1], dot2);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < ROWS; i += 2) {
-                F[i] = fma(s_a[i], carry, F[i]);
-                dot = fma(s_b[i], F[i], dot);
-                F[i + 1] = fma(s_a[i + 1], carry, F[i + 1]);
-                dot2 = fma(s_b[i + 1], F[i + 1], dot2);
-            }
-        }
-        dot += dot2;
-        const double zn = mm ? (yn + dot) : (yn - dot);
-        if (A.store && rok) Zg[(size_t)n * R + r] = zn;
-        carry = mm ? yn : zn;
-        wave_lds_fence();
-        s_a[lane] = cur.push;
-        if (up) de_cross = cur.e;
-    }
-    wave_lds_fence();
-    const bool dec = up && de_cross >= 0.0;
-    if (dec) s_e[lane] = fm_exp(-cj * de_cross);
-    wave_lds_fence();
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) {
-        double v = fma(s_a[i], carry, F[i]);
-        if (dec) v *= s_e[i];
-        if (rok) Fg[(size_t)i * R + r] = v;
-    }
-}
-
-// k_linR in k_factor7's lane tiling.  k_linR gives every lane ONE right-hand side and all ROWS state
-// rows, so each FMA takes a wave-uniform row operand through an LDS broadcast read: 2 ROWS reads per row,
-// and with eight waves per CU the LDS array -- not the 2 ROWS FMAs -- set the pace (4 % of the HBM roofline
-// on cfg5).  The per-row update is exactly k_factor7's sweep (T += a q^T ; dot += b^T T with T = the
-// state, columns = right-hand sides, q = the carries), so it takes the same tiling: lane (g, c) holds the
-// right-hand sides 2c, 2c + 1 of half the state rows (pairs 4k + 2g, 4k + 2g + 1), one ds_read_b128
-// feeds 8 FMAs (ROWS / 2 reads per row instead of 2 ROWS), and the lane's OWN right-hand side 2c + g
-// (its y, z and carry) is connected to its two state columns by the same two v_permlane32_swap pairs.
-// NODOT: the local pass of GF_MATMUL_LOWER (dot_tril) -- its carries are the inputs themselves, so the
-// pass only accumulates the state: half the FMAs, no reduction.
-template <int ROWS, bool NODOT>
-__global__ void __launch_bounds__(64, 2) k_linR7(const LinArgs A) {
-    const int lane = threadIdx.x;
-    const int g = lane >> 5, c = lane & 31;
-    const int b = blockIdx.x;                       // (problem, chunk)
-    const int rt = blockIdx.y;                      // RHS tile of 64 columns
-    const int pr = b / A.nch, ch = b - pr * A.nch;
-    const int R = A.R;
-    const int r = rt * 64 + 2 * c + g;              // this lane's own right-hand side
-    const bool rok = r < R;
-    const int r0 = rt * 64 + 2 * c;                 // its two state columns: r0, r0 + 1
-    const int64_t c0 = (int64_t)ch * A.chunk_len;
-    const int64_t rows = (A.N - c0 < A.chunk_len) ? (A.N - c0) : A.chunk_len;
-    const size_t pb = (size_t)pr * A.N + c0;
-    const double *__restrict__ Ug = A.Ut + pb * 64 + lane;
-    const double *__restrict__ Wg = A.Wt + pb * 64 + lane;
-    const double *__restrict__ dg = A.d + pb;
-    const double *__restrict__ eg = A.de + pb;
-    const double *__restrict__ Yg = A.Y + pb * R;
-    double *__restrict__ Zg = A.Z + pb * R;
-    double *__restrict__ Fg = A.F_state + (size_t)b * 64 * R;      // [i][R]
-    const double cj = (lane < A.W) ? A.c[(size_t)pr * A.W + lane] : 0.0;
-    const bool up = A.mode == GF_SOLVE_UPPER, mm = A.mode == GF_MATMUL_LOWER;
-    __shared__ __attribute__((aligned(16))) double s_a[64], s_b[64], s_e[64];
-    const double2 *pa = (const double2 *)s_a + g, *pb2 = (const double2 *)s_b + g;
-    const double2 *pe = (const double2 *)s_e + g;
-    double T[ROWS / 2][2];
-#pragma unroll
-    for (int m2 = 0; m2 < ROWS / 2; ++m2) {
-        const int i = 4 * (m2 >> 1) + 2 * g + (m2 & 1);
-        T[m2][0] = (r0 < R && A.store) ? Fg[(size_t)i * R + r0] : 0.0;
-        T[m2][1] = (r0 + 1 < R && A.store) ? Fg[(size_t)i * R + r0 + 1] : 0.0;
-    }
-    double q0 = 0.0, q1 = 0.0, carry = 0.0;
-    s_a[lane] = 0.0;                                // pending push row (w~_{n-1} or u~_{n+1})
-    double de_cross = -1.0;
-    struct RowIn { double y, pull, push, e, d; };
-    auto fetch = [&](int64_t s) {
-        if (s > rows - 1) s = rows - 1;
-        const int64_t n = up ? (rows - 1 - s) : s;
-        RowIn q;
-        q.y = rok ? Yg[(size_t)n * R + r] : 0.0;
-        q.pull = up ? Wg[(size_t)n * 64] : Ug[(size_t)n * 64];
-        q.push = up ? Ug[(size_t)n * 64] : Wg[(size_t)n * 64];
-        q.e = eg[n];
-        q.d = A.scale ? dg[n] : 1.0;
-        return q;
-    };
-    RowIn p0 = fetch(0), p1 = fetch(1), p2 = fetch(2);
-    double2 ub[S7_AHEAD + 1], wb[S7_AHEAD + 1];
-    for (int64_t s = 0; s < rows; ++s) {
-        const int64_t n = up ? (rows - 1 - s) : s;
-        const RowIn cur = p0;
-        p0 = p1; p1 = p2; p2 = fetch(s + 3);
-        double yn = cur.y;
-        if (A.scale) yn = mm ? yn * sqrt(cur.d) : yn / cur.d;
-        const double de = up ? de_cross : cur.e;    // decay to apply before this row's dot
-        wave_lds_fence();
-        s_b[lane] = cur.pull;
-        const bool dec = de >= 0.0;
-        if (dec) s_e[lane] = fm_exp(-cj * de);
-        wave_lds_fence();
-        if (dec) {                                  // fold the pending push, decay the state rows
-            double d0, d1;
-            sweep7_preload<ROWS>(ub, wb, pe, pa);
-            sweep7_run<ROWS, true>(T, ub, wb, pe, pa, q0, q1, 1.0, 1.0, d0, d1);
-            q0 = 0.0;
-            q1 = 0.0;
-        }
-        if constexpr (NODOT) {
-#pragma unroll
-            for (int k = 0; k < ROWS / 4; ++k) {
-                const double2 w = pa[2 * k];
-                T[2 * k][0] = fma(w.x, q0, T[2 * k][0]);
-                T[2 * k][1] = fma(w.x, q1, T[2 * k][1]);
-                T[2 * k + 1][0] = fma(w.y, q0, T[2 * k + 1][0]);
-                T[2 * k + 1][1] = fma(w.y, q1, T[2 * k + 1][1]);
-            }
-            carry = yn;
-        } else {
-            double acc0, acc1;
-            __builtin_amdgcn_s_setprio(0);
-            sweep7_preload<ROWS>(ub, wb, pb2, pa);
-            sweep7_run<ROWS, false>(T, ub, wb, pb2, pa, q0, q1, 0.0, 0.0, acc0, acc1);
-            __builtin_amdgcn_s_setprio(GF_CHAIN_PRIO);
-            const double dot = own_column_sum(acc0, acc1);
-            const double zn = mm ? (yn + dot) : (yn - dot);
-            if (A.store && rok) Zg[(size_t)n * R + r] = zn;
-            carry = mm ? yn : zn;
-        }
-        both_halves(carry, q0, q1);                 // the carries of this lane's two state columns
-        wave_lds_fence();
-        s_a[lane] = cur.push;
-        if (up) de_cross = cur.e;
-    }
-    wave_lds_fence();
-    const bool dec = up && de_cross >= 0.0;
-    if (dec) s_e[lane] = fm_exp(-cj * de_cross);
-    wave_lds_fence();
-#pragma unroll
-    for (int m2 = 0; m2 < ROWS / 2; ++m2) {
-        const int i = 4 * (m2 >> 1) + 2 * g + (m2 & 1);
-        double v0 = fma(s_a[i], q0, T[m2][0]), v1 = fma(s_a[i], q1, T[m2][1]);
-        if (dec) { v0 *= s_e[i]; v1 *= s_e[i]; }
-        if (r0 < R) Fg[(size_t)i * R + r0] = v0;
-        if (r0 + 1 < R) Fg[(size_t)i * R + r0 + 1] = v1;
-    }
-}
-
-// GF_MATMUL_LOWER (dot_tril, GP.sample) with many right-hand sides on the matrix pipe.  The sweep has no
-// feedback in this mode (the carries are the inputs), so 16 rows at a time are plain products:
-//     Z_b = Y_b + U_b F + strict_lower(U_b W_b^T) Y_b ,     F <- F + W_b^T Y_b
-// (U_b, W_b: the block's 16 rows of u~, w~; F: W x R state; decay E o F first when the block starts on a
-// reset row; a reset inside a block cuts it there, rows past the cut are masked).  k_linR7 does the same
-// arithmetic row by row and runs at the pace of its LDS broadcasts (30 ds_read_b128 per row and wave: 14.9 %
-// of the HBM roofline on cfg5).  Here one wave owns 64 right-hand sides of one chunk; everything is
-// v_mfma_f64_16x16x4 (lane (i, k) = (lane & 15, lane >> 4) supplies A[i][4 s + k], B[4 s + k][i] of slice s
-// and receives D[k + 4 r][i], r = 0..3), laid out so that no result ever changes lanes:
-//   * the accumulators of  F += W_b^T Y_b  (tile mt, register r = state 16 mt + k + 4 r) ARE the B
-//     operands of  U_b F  (slice s = 4 mt + r <-> state 4 s + k);
-//   * the C layout of  G^T = W_b U_b^T  is the A layout of  strict_lower(G) Y_b  (entry (i, k + 4 r));
-//   * the B operand rows of Y_b (4 s + k) are the C rows of Z_b (k + 4 r): one load serves both.
-// 16 + 36 T MFMAs per block and wave (T = 4 tiles of 16 right-hand sides: the rows are read once), 16 T for
-// the local pass; one wave per SIMD (the state alone is 128 accumulator registers).
-// The block's u~ / w~ rows (2 x 8 KB, contiguous in memory) come in as flat 16-byte loads issued one block
-// ahead, go through an LDS tile (row stride 66: the A-operand reads are conflict-free) and are read slice by
-// slice at their point of use.  Taking the operands from global in their MFMA layout instead cost more than
-// the MFMAs: a lane-per-row pattern is 64 separate sectors per load instruction (the texture addresser
-// serialises them), and a masked load in a branch of its own gets its own s_waitcnt (30 round trips per block).
-template <int MT, bool NODOT, int NWV>
-__global__ void __launch_bounds__(64 * NWV, (NWV == 1 && !NODOT) ? 1 : 2) k_mmR_mfma(const LinArgs A) {
-    constexpr int KS = 4 * MT, T = 2, LDT = 66, NQ = 8 / NWV;
-    const int lane = threadIdx.x & 63, i = lane & 15, k = lane >> 4;
-    const int wv = (NWV > 1) ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
-    const int b = blockIdx.x, rt = blockIdx.y;
-    const int pr = b / A.nch, ch = b - pr * A.nch;
-    const int R = A.R;
-    const int64_t c0 = (int64_t)ch * A.chunk_len;
-    const int rows = (int)((A.N - c0 < A.chunk_len) ? (A.N - c0) : A.chunk_len);
-    const size_t pb = (size_t)pr * A.N + c0;
-    const double *__restrict__ Ug = A.Ut + pb * 64;
-    const double *__restrict__ Wg = A.Wt + pb * 64;
-    const double *__restrict__ dg = A.d + pb;
-    const double *__restrict__ eg = A.de + pb;
-    const double *__restrict__ Yg = A.Y + pb * R;
-    double *__restrict__ Zg = A.Z + pb * R;
-    double *__restrict__ Fg = A.F_state + (size_t)b * 64 * R;      // [state][R]
-    __shared__ double s_e[NWV][64];                 // decays of the states at a reset row
-    const double c_lane = (lane < A.W) ? A.c[(size_t)pr * A.W + lane] : 0.0;
-    // the block's rows, two buffers: a wave that runs ahead stashes block n + 1 while its partner still
-    // reads block n (one barrier per block)
-    __shared__ __attribute__((aligned(16))) double s_u[NODOT ? 2 : 2 * 16 * LDT], s_w[2 * 16 * LDT];
-    int rhs[T], rhc[T];                             // (rhc: clamped, loads are unconditional; masks come after)
-    bool rok[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        rhs[t] = (rt * NWV + wv) * 16 * T + 16 * t + i; rok[t] = rhs[t] < R; rhc[t] = rok[t] ? rhs[t] : R - 1;
-    }
-    d4 F[T][MT];                                    // F[t][mt][r] = state 16 mt + k + 4 r, rhs[t]
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)     // (the local pass starts from zero)
-                F[t][mt][r] = NODOT ? 0.0 : Fg[(size_t)(16 * mt + k + 4 * r) * R + rhc[t]];
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) F[t][mt][r] = rok[t] ? F[t][mt][r] : 0.0;
-    // one block of inputs, as loaded (rows clamped to the chunk; no branch around any load); the waves of
-    // the workgroup share the copy of the u~ / w~ rows (row 2 NWV q + 2 wv + (lane >> 5) of the tile)
-    double pux[NODOT ? 1 : NQ], puy[NODOT ? 1 : NQ], pwx[NQ], pwy[NQ];
-    double e_raw, d_raw, yraw[T][4];
-#define GF_MM_FETCH(N0)                                                                             \
-    do {                                                                                            \
-        const int f_n0 = (N0);                                                                      \
-        const int f_lim = (rows - f_n0 < 16) ? rows - f_n0 : 16;                                    \
-        e_raw = eg[f_n0 + ((lane < f_lim) ? lane : f_lim - 1)];                                     \
-        d_raw = dg[f_n0 + (((lane & 15) < f_lim) ? (lane & 15) : f_lim - 1)];                       \
-        _Pragma("unroll")                                                                           \
-        for (int s4 = 0; s4 < 4; ++s4) {                                                            \
-            const int f_row = 4 * s4 + k;                                                           \
-            const size_t f_n = (size_t)(f_n0 + ((f_row < f_lim) ? f_row : f_lim - 1));              \
-            _Pragma("unroll")                                                                       \
-            for (int t = 0; t < T; ++t) yraw[t][s4] = Yg[f_n * R + rhc[t]];                         \
-        }                                                                                           \
-        _Pragma("unroll")                                                                           \
-        for (int q = 0; q < NQ; ++q) {  /* flat copy: 16-byte pieces of the 16 x 64 tile */         \
-            const int f_row = 2 * NWV * q + 2 * wv + (lane >> 5);                                   \
-            const size_t f_off = (size_t)(f_n0 + ((f_row < f_lim) ? f_row : f_lim - 1)) * 64 + 2 * (lane & 31); \
-            const double2 f_w = *reinterpret_cast<const double2 *>(Wg + f_off);                     \
-            pwx[q] = f_w.x; pwy[q] = f_w.y;                                                         \
-            if constexpr (!NODOT) {                                                                 \
-                const double2 f_u = *reinterpret_cast<const double2 *>(Ug + f_off);                 \
-                pux[q] = f_u.x; puy[q] = f_u.y;                                                     \
-            }                                                                                       \
-        }                                                                                           \
-    } while (0)
-    GF_MM_FETCH(0);
-    int buf = 0;
-    for (int n0 = 0; n0 < rows; buf ^= 1) {
-        const int lim = (rows - n0 < 16) ? rows - n0 : 16;
-        const double *su = s_u + (NODOT ? 0 : buf * 16 * LDT), *sw = s_w + buf * 16 * LDT;
-        if (NWV == 1) wave_lds_fence();             // (the block before the previous one has been read)
-        // the block: rows n0 .. n0 + cnt - 1, cut at the first reset row after n0
-        const double e_l = (lane < lim) ? e_raw : -1.0;
-        const unsigned long long inner = __ballot(e_l >= 0.0 && lane >= 1);
-        const int cnt = inner ? (int)__ffsll((long long)inner) - 1 : lim;
-        const double de0 = read_lane(e_l, 0);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {              // (rows past the cut enter the tile as zeros: no operand masks)
-            const int row = 2 * NWV * q + 2 * wv + (lane >> 5);
-            const int at = buf * 16 * LDT + row * LDT + 2 * (lane & 31);
-            const bool in = row < cnt;
-            *reinterpret_cast<double2 *>(&s_w[at]) = double2{in ? pwx[q] : 0.0, in ? pwy[q] : 0.0};
-            if constexpr (!NODOT) *reinterpret_cast<double2 *>(&s_u[at]) = double2{in ? pux[q] : 0.0, in ? puy[q] : 0.0};
-        }
-        double yv[T][4];                            // rows n0 + 4 s + k (B operand of slice s; C rows of Z_b)
-        bool okK[4];
-        const double sq = A.scale ? sqrt(d_raw) : 1.0;      // lane l: sqrt(d) of row n0 + (l & 15)
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            okK[s4] = 4 * s4 + k < cnt;
-            const double sc = A.scale ? __shfl(sq, 4 * s4 + k) : 1.0;
-#pragma unroll
-            for (int t = 0; t < T; ++t) yv[t][s4] = (okK[s4] && rok[t]) ? yraw[t][s4] * sc : 0.0;
-        }
-        if (NWV == 1) wave_lds_fence(); else wg_lds_barrier();
-        // the next block's loads fly under this block's MFMAs (past the chunk's end: the last row again,
-        // never used -- an unconditional fetch keeps the staging registers out of scratch)
-        GF_MM_FETCH((n0 + cnt < rows) ? n0 + cnt : rows - 1);
-        if (de0 >= 0.0) {
-            // reset row: F <- E o F before the block's products.  Lane l forms the decay of state l, the
-            // lanes pick theirs (state 16 mt + k + 4 r) up from LDS: one exponential and 8 T multiplies per
-            // lane.  (As diag(E) F on the matrix pipe -- the form this kernel had while F lived in accumulator
-            // registers -- the decay cost 16 T MFMAs per reset: half the local pass when every 16-row block
-            // starts on one, as with the solar-like kernels at one-minute cadence.)
-            s_e[wv][lane] = fm_exp(-c_lane * de0);
-            wave_lds_fence();
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double e = s_e[wv][16 * mt + k + 4 * r];
-#pragma unroll
-                    for (int t = 0; t < T; ++t) F[t][mt][r] *= e;
-                }
-        }
-        if constexpr (!NODOT) {
-            d4 G = {0.0, 0.0, 0.0, 0.0};            // G^T = W_b U_b^T: lane (i, k) gets u~_i . w~_{k + 4 r}
-            d4 Z[T];
-#pragma unroll
-            for (int t = 0; t < T; ++t) Z[t] = d4{yv[t][0], yv[t][1], yv[t][2], yv[t][3]};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {          // u~, w~[n0 + i][4 s + k]
-                const double ua = su[i * LDT + 4 * s + k], wa = sw[i * LDT + 4 * s + k];
-                G = GF_MFMA64(wa, ua, G);
-#pragma unroll
-                for (int t = 0; t < T; ++t) Z[t] = GF_MFMA64(ua, F[t][s >> 2][s & 3], Z[t]);
-                if ((s & 3) == 3) __builtin_amdgcn_sched_barrier(0);    // (operand reads stay near their use)
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (k + 4 * r >= i) G[r] = 0.0;        // strictly lower
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) Z[t] = GF_MFMA64(G[s4], yv[t][s4], Z[t]);
-                if (A.store && rok[t]) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (k + 4 * r < cnt) Zg[(size_t)(n0 + k + 4 * r) * R + rhs[t]] = Z[t][r];
-                }
-            }
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {        // w~[n0 + 4 s + k][16 mt + i]
-                const double wt = sw[(4 * s4 + k) * LDT + 16 * mt + i];
-#pragma unroll
-                for (int t = 0; t < T; ++t) F[t][mt] = GF_MFMA64(wt, yv[t][s4], F[t][mt]);
-            }
-        n0 += cnt;
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (rok[t]) Fg[(size_t)(16 * mt + k + 4 * r) * R + rhs[t]] = F[t][mt][r];
-}
-#undef GF_MM_FETCH
-
-constexpr int LC_TRANSPOSED = 0x100;     // (flag on the combine kernels' mode: transitions handed over transposed)
-
 // out[m] = in[m]^T for a batch of 64 x 64 matrices (the transitions' transposes for the backward solve: once per factor)
 __global__ void __launch_bounds__(256) k_transpose64(const double *__restrict__ in, double *__restrict__ out) {
     __shared__ double tile[64][65];
@@ -4311,215 +3264,6 @@ __global__ void __launch_bounds__(256) k_transpose64(const double *__restrict__ 
     for (int e = threadIdx.x; e < 4096; e += 256) tile[e >> 6][e & 63] = in[m * 4096 + e];
     __syncthreads();
     for (int e = threadIdx.x; e < 4096; e += 256) out[m * 4096 + e] = tile[e & 63][e >> 6];
-}
-
-// Linear combine of the chunk states of a sweep: on entry F_state slot c holds chunk c's end
-// state from a zero start (local pass); on exit it holds the TRUE start state of chunk c.
-//   lower  : F_{c+1} = Fbar_c + Phi_c F_c            (ascending; Phi = true closed-loop transition)
-//   upper  : G_{c-1} = Gbar_c + Phi_c^T G_c          (descending)
-//   matmul : F_{c+1} = Fbar_c + D_c o F_c            (D = product of the chunk's reset decays)
-// One workgroup of 64 x RT threads per (problem, RHS tile); Phi is stored [j][i].
-//
-// Two-level form (PHASE 1 / 2; PHASE 0 is the plain scan over all chunks): the chunks are cut into
-// segments of seg_len whose composed transitions Psi_s = Phi_{e-1} ... Phi_b are part of the factor
-// (k_segment_transition, once per factor; the backward solve uses Psi_s^T).  PHASE 1 scans every
-// segment concurrently from a zero start and leaves its end state in Vseg; a PHASE 0 scan of
-// (Psi, Vseg) turns those into the segments' true start states; PHASE 2 rescans every segment from
-// there and writes the chunks' start states.  Sequential depth 2 seg_len + nch / seg_len chunks
-// instead of nch.
-template <int PHASE>
-__global__ void __launch_bounds__(256)
-k_lincombine(const int nch, const int seg_len, const int mode_, const int R,
-             const double *__restrict__ Phi_, const double *__restrict__ Dch_,
-             double *__restrict__ F_state, double *__restrict__ Vseg) {
-    // mode_ | LC_TRANSPOSED: Phi_ holds the TRANSPOSED transitions (backward solve): its loads then run along the
-    // lanes like the forward solve's (a row of Phi^T per lane is one 128-byte run per lane and load: 0.12 against
-    // 0.07 ms for the scan of 1954 chunks)
-    const int mode = mode_ & ~LC_TRANSPOSED;
-    const bool pre_t = (mode_ & LC_TRANSPOSED) != 0;
-    // One workgroup of four waves per (problem, right-hand side): the scan is sequential over the
-    // chunks only.  Lane i owns state row i; wave w multiplies columns 16w..16w+15 of the chunk's
-    // 64 x 64 transition (rows of Phi^T for the backward solve), which it holds in registers and
-    // fetches THREE chunks ahead (a ring of four 16-double buffers: the 32 KB per chunk come from
-    // L2 with ~2 us latency, which a single buffer exposed on every step: 2.3 us per chunk, now
-    // ~0.4); the four partial sums meet in LDS, one barrier per chunk.
-    const int r = blockIdx.y, i = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const bool up = mode == GF_SOLVE_UPPER, mm = mode == GF_MATMUL_LOWER;
-    const int nseg = PHASE ? (nch + seg_len - 1) / seg_len : 1;
-    const int pr = blockIdx.x / nseg, sg = blockIdx.x - pr * nseg;
-    const int c_lo = PHASE ? sg * seg_len : 0;
-    const int c_hi = PHASE ? ((c_lo + seg_len < nch) ? c_lo + seg_len : nch) : nch;
-    const int len = c_hi - c_lo;
-    __shared__ __attribute__((aligned(16))) double s_cur[64];
-    __shared__ double s_part[2][4][64];
-    double P[4][16];
-    auto chunk_of = [&](int s) { return up ? (c_hi - 1 - s) : (c_lo + s); };
-    auto load_phi = [&](double (&buf)[16], int s) {
-        if (s >= len) return;
-        const double *Pg = Phi_ + ((size_t)pr * nch + chunk_of(s)) * 4096;
-        if (!up || pre_t) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) buf[j] = Pg[(size_t)(16 * w + j) * 64 + i];    // Phi(i, j) (or Phi^T's)
-        } else {
-            const double2 *row = reinterpret_cast<const double2 *>(Pg + (size_t)i * 64 + 16 * w);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const double2 v = row[j]; buf[2 * j] = v.x; buf[2 * j + 1] = v.y; }  // Phi(j, i)
-        }
-    };
-    double cur = 0.0;                               // state row i (carried by wave 0)
-    double *Vg = PHASE ? Vseg + ((size_t)pr * nseg + sg) * 64 * R + (size_t)i * R + r : nullptr;
-    if (PHASE == 2 && w == 0) cur = *Vg;
-    if (PHASE == 0 && mm) {                         // diagonal transitions: one wave does it all
-        if (w != 0) return;
-        constexpr int GB = 16;                      // (loads of sixteen chunks ahead of their dependent FMAs)
-        for (int s0 = 0; s0 < nch; s0 += GB) {
-            double loc[GB], dd[GB];
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                const int s = (s0 + k < nch) ? s0 + k : nch - 1;
-                const size_t slot = (size_t)pr * nch + s;
-                loc[k] = F_state[slot * 64 * R + (size_t)i * R + r];
-                dd[k] = Dch_[slot * 64 + i];
-            }
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                if (s0 + k < nch) {
-                    const size_t slot = (size_t)pr * nch + s0 + k;
-                    F_state[slot * 64 * R + (size_t)i * R + r] = cur;
-                    cur = fma(dd[k], cur, loc[k]);
-                }
-            }
-        }
-        return;
-    }
-    load_phi(P[0], 0); load_phi(P[1], 1); load_phi(P[2], 2);
-    if (threadIdx.x < 64) s_cur[i] = cur;
-    __syncthreads();
-    auto step = [&](double (&buf)[16], double (&next)[16], int s) {
-        const size_t slot = (size_t)pr * nch + chunk_of(s);
-        double *Fg = F_state + slot * 64 * R + (size_t)i * R + r;
-        double loc = 0.0;
-        if (w == 0) { loc = *Fg; if (PHASE != 1) *Fg = cur; }   // local end state in, true start state out
-        load_phi(next, s + 3);
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < 16; j += 2) {
-            a0 = fma(buf[j], s_cur[16 * w + j], a0);
-            a1 = fma(buf[j + 1], s_cur[16 * w + j + 1], a1);
-        }
-        s_part[s & 1][w][i] = a0 + a1;
-        __syncthreads();
-        if (w == 0) {                               // wave 0 carries the state
-            const double *sp = &s_part[s & 1][0][0];
-            cur = loc + ((sp[i] + sp[64 + i]) + (sp[128 + i] + sp[192 + i]));
-            s_cur[i] = cur;
-        }
-        __syncthreads();
-    };
-    int s = 0;
-    for (; s + 4 <= len; s += 4) {
-        step(P[0], P[3], s);
-        step(P[1], P[0], s + 1);
-        step(P[2], P[1], s + 2);
-        step(P[3], P[2], s + 3);
-    }
-    if (s < len) step(P[0], P[3], s);
-    if (s + 1 < len) step(P[1], P[0], s + 1);
-    if (s + 2 < len) step(P[2], P[1], s + 2);
-    if (PHASE == 1 && w == 0) *Vg = cur;            // the segment's end state from a zero start
-}
-
-// The segment scans (PHASE 1 / 2 of k_lincombine) for MANY right-hand sides: 64 at a time, the chunk step
-// S <- Fbar_c + Phi_c S (Phi_c^T for the backward solve) as one 64 x 64 x 64 product on the matrix pipe.  One
-// workgroup per (problem, segment, 64 right-hand sides): the state S [j][r] sits in LDS as the B operand, Phi_c is
-// the A operand straight from global -- lane (i, k) of wave w supplies Phi(16 w + i, 4 ks + k) -- fetched one chunk
-// ahead together with the chunk's local end state (in accumulator layout: the MFMAs start from it).  One workgroup
-// per right-hand side re-read every Phi_c 64 times and took 0.38 ms per phase for 64 right-hand sides at 1954
-// chunks (a quarter of predict(return_var=True)); this one streams them once.
-template <int PHASE>
-__global__ void __launch_bounds__(256)
-k_lincombine_R(const int nch, const int seg_len, const int mode_, const int R,
-               const double *__restrict__ Phi_, double *__restrict__ F_state, double *__restrict__ Vseg) {
-    const int mode = mode_ & ~LC_TRANSPOSED;
-    const bool pre_t = (mode_ & LC_TRANSPOSED) != 0;         // (Phi_ holds the transposed transitions)
-    constexpr int LDB = 80;                         // (rows k, k + 1 of the B operand 32 banks apart)
-    __shared__ __attribute__((aligned(16))) double Sb[64 * LDB];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, k = lane >> 4;
-    const bool up = mode == GF_SOLVE_UPPER;
-    const int nseg = (nch + seg_len - 1) / seg_len;
-    const int pr = blockIdx.x / nseg, sg = blockIdx.x - pr * nseg;
-    const int r0 = 64 * blockIdx.y;
-    const int c_lo = sg * seg_len, c_hi = (c_lo + seg_len < nch) ? c_lo + seg_len : nch, len = c_hi - c_lo;
-    auto chunk_of = [&](int sidx) { return up ? (c_hi - 1 - sidx) : (c_lo + sidx); };
-    // a 64 x 64 block of a state array [64][R] in accumulator layout: x[q][rr] = (row 16 w + k + 4 rr, column r0 + 16 q + i)
-    auto ld_state = [&](const double *base, d4 (&x)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int col = r0 + 16 * q + i;
-                x[q][rr] = (col < R) ? base[(size_t)(16 * w + k + 4 * rr) * R + col] : 0.0;
-            }
-    };
-    auto st_state = [&](double *base, const d4 (&x)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int col = r0 + 16 * q + i;
-                if (col < R) base[(size_t)(16 * w + k + 4 * rr) * R + col] = x[q][rr];
-            }
-    };
-    auto ld_A = [&](double (&a)[16], const int sidx) {
-        if (sidx >= len) return;
-        const double *Pg = Phi_ + ((size_t)pr * nch + chunk_of(sidx)) * 4096;      // Phi(i, j) at [j][i]
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks)
-            a[ks] = (up && !pre_t) ? Pg[(size_t)(16 * w + i) * 64 + 4 * ks + k] : Pg[(size_t)(4 * ks + k) * 64 + 16 * w + i];
-    };
-    auto slot_of = [&](int sidx) { return F_state + ((size_t)pr * nch + chunk_of(sidx)) * 64 * R; };
-    d4 cur[4];
-    double *Vg = Vseg + ((size_t)pr * nseg + sg) * 64 * R;
-    if (PHASE == 2) ld_state(Vg, cur);
-    else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = d4{0.0, 0.0, 0.0, 0.0};
-    }
-    auto put = [&]() {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) Sb[(16 * w + k + 4 * rr) * LDB + 16 * q + i] = cur[q][rr];
-    };
-    put();
-    double a0[16], a1[16];
-    d4 l0[4], l1[4];
-    ld_A(a0, 0);
-    ld_state(slot_of(0), l0);
-    __syncthreads();
-    auto step = [&](double (&a)[16], d4 (&loc)[4], double (&an)[16], d4 (&locn)[4], const int sidx) {
-        ld_A(an, sidx + 1);
-        if (sidx + 1 < len) ld_state(slot_of(sidx + 1), locn);
-        if (PHASE == 2) st_state(slot_of(sidx), cur);           // local end state in (above), true start state out
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = loc[q];
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-            const double av = a[ks];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) cur[q] = GF_MFMA64(av, Sb[(4 * ks + k) * LDB + 16 * q + i], cur[q]);
-        }
-        __syncthreads();                            // every wave has read the old state
-        put();
-        __syncthreads();
-    };
-    int sidx = 0;
-    for (; sidx + 2 <= len; sidx += 2) {
-        step(a0, l0, a1, l1, sidx);
-        step(a1, l1, a0, l0, sidx + 1);
-    }
-    if (sidx < len) step(a0, l0, a1, l1, sidx);
-    if (PHASE == 1) st_state(Vg, cur);              // the segment's end state from a zero start
 }
 
 // Composed transition of every segment of seg_len chunks:  Psi_s = Phi_{e-1} ... Phi_{b+1} Phi_b
@@ -4551,334 +3295,6 @@ k_segment_transition(const int nch, const int seg_len, const double *__restrict_
     }
     double *Og = Psi_ + ((size_t)pr * nseg + sg) * 4096;
     for (int e = tid; e < 4096; e += 256) Og[e] = Ps[(e & 63) * 64 + (e >> 6)];
-}
-
-// ---- dense batched solve for the chunk maps of WIDE kernels --------------------------------------
-// The time-parallel combine of a W > 63 kernel composes dense W x W maps (W <= 192): GEMMs and one
-// LU solve per tree level and pair.  The GEMMs go to rocBLAS; the solves do not: hipSOLVER's blocked
-// getrf / getrs is ~300 tiny launches per call at this size (3 ms per tree level, all of it launch
-// latency -- two thirds of `compute` with gadfly's 86-term solar kernel at N = 1e5).  This kernel does
-// one batched solve in ONE launch: Gauss-Jordan with implicit partial pivoting (rows are never
-// swapped) on [A | B], held in registers.
-//   16 waves per system, every wave holds ALL rows (lane l: rows l, l + 64, l + 128) of its columns:
-//   column j of A belongs to wave j mod 16 (slot j / 16), the right-hand sides are dealt the same
-//   way; blockIdx.y cuts B into slices of 64 columns, each slice eliminates its own copy of A.
-//   Step k: the pivot search is local to the wave that owns column k; it publishes the multipliers
-//   f_i = a_ik / a_pk (f_p = 0), the pivot's lane and row set through LDS.  After ONE barrier every
-//   wave updates its slots; the pivot row's entry of a column is a readlane of the wave's own
-//   registers (an SGPR operand of the FMAs: no LDS traffic in the update).  The owner of column
-//   k + 1 forms that column first and runs the next search before its update, so the search overlaps
-//   the other waves' FMAs.
-//   The k loop is cut into phases of 16 steps, unrolled at compile time: in phase q the slots below q
-//   hold eliminated columns and are left alone, and the owner's slot index is a constant.  All
-//   register updates are unconditional straight-line code: alternatives that merge (one per row set
-//   of the pivot, say) cost a copy of the whole register array per step, so the row set only selects
-//   which registers the readlanes read.
-//   A, B and X move through an LDS tile of 32 rows so that global accesses are contiguous (lanes
-//   along a row); lane = row gathers of a row-major matrix cost more than the elimination.
-// Singular systems (maps of chunks after a failed pivot) produce garbage, never a fault.
-constexpr int DS_WAVES = 16;                        // 16 NR right-hand sides per workgroup (NR: template parameter)
-constexpr int DS_TROWS = 32, DS_LDT = 193;          // LDS tile: 32 rows, odd leading dimension
-
-template <int RS>
-struct DenseSolveShared {
-    double tile[DS_TROWS * DS_LDT];
-    double f[2][RS][64];                            // multipliers of step k, buffer k & 1
-    double rowpinv[64 * RS];
-    int pl[2], rs[2], rowk[64 * RS];
-    int seen[64 * RS];                              // (log-determinant: cycle walk of the row -> pivot map)
-};
-
-// pivot search on column k (values C of this wave's rows) by its owner; publishes into buffer k & 1
-template <int RS>
-__device__ __forceinline__ void ds_search(DenseSolveShared<RS> &sh, const double (&C)[RS], const unsigned used,
-                                          const int k, const int lane) {
-    const int buf = k & 1;
-    double bx = 0.0, bc = -2.0;
-    int br = 0;
-#pragma unroll
-    for (int r = 0; r < RS; ++r) {
-        double a = fabs(C[r]);
-        a = (a == a) ? a : 0.0;
-        const double cnd = ((used >> r) & 1u) ? -1.0 : a;
-        if (cnd > bc) { bc = cnd; bx = C[r]; br = r; }
-    }
-    const double vm = wave_max(bc);
-    const unsigned long long hit = __ballot(bc == vm);
-    const int pl = __builtin_amdgcn_readfirstlane(hit ? (int)__ffsll((long long)hit) - 1 : 0);
-    const int rsel = __builtin_amdgcn_readlane(br, pl);
-    const double pinv = fast_rcp(read_lane(bx, pl));
-#pragma unroll
-    for (int r = 0; r < RS; ++r)
-        sh.f[buf][r][lane] = (lane == pl && r == rsel) ? 0.0 : C[r] * pinv;
-    if (lane == 0) {
-        sh.pl[buf] = pl; sh.rs[buf] = rsel;
-        sh.rowk[64 * rsel + pl] = k; sh.rowpinv[64 * rsel + pl] = pinv;
-    }
-}
-
-// entry (lane pl, row set RSEL) of slots [Q, NS) as wave-uniform values; the empty asm keeps the three
-// instances apart (merged, the compiler selects among the register sets with per-step copies)
-template <int RS, int NS, int RSEL, int Q>
-__device__ __forceinline__ void ds_pivot_row(double (&pe)[NS], const double (&R)[RS][NS], const int pl) {
-#pragma unroll
-    for (int c = Q; c < NS; ++c) {
-        int lo = __builtin_amdgcn_readlane(__double2loint(R[RSEL][c]), pl);
-        int hi = __builtin_amdgcn_readlane(__double2hiint(R[RSEL][c]), pl);
-        if (RSEL == 0) asm volatile("; row set 0" : "+s"(lo), "+s"(hi));
-        else if (RSEL == 1) asm volatile("; row set 1" : "+s"(lo), "+s"(hi));
-        else asm volatile("; row set 2" : "+s"(lo), "+s"(hi));
-        pe[c] = __hiloint2double(hi, lo);
-    }
-}
-
-// phase Q of the elimination: steps k = 16 Q ... 16 Q + 15 (< n), slots [Q, NA + NR)
-template <int RS, int NA, int NR, int Q>
-__device__ __forceinline__ void ds_phase(DenseSolveShared<RS> &sh, double (&R)[RS][NA + NR], unsigned &used,
-                                         const int n, const int wave, const int lane) {
-    constexpr int NS = NA + NR;
-    const int kend = (n - DS_WAVES * Q < DS_WAVES) ? n - DS_WAVES * Q : DS_WAVES;
-    for (int kk = 0; kk < kend; ++kk) {
-        const int k = DS_WAVES * Q + kk, buf = k & 1;
-        // the owner of the next column is the critical path of the step: it outranks the three waves
-        // that share its SIMD until its search is published
-        const bool owner = k + 1 < n && wave == ((k + 1) & (DS_WAVES - 1));
-        if (owner) __builtin_amdgcn_s_setprio(3);
-        wg_lds_barrier();
-        double f[RS];
-#pragma unroll
-        for (int r = 0; r < RS; ++r) f[r] = sh.f[buf][r][lane];
-        const int pl = __builtin_amdgcn_readfirstlane(sh.pl[buf]);
-        const int rsel = __builtin_amdgcn_readfirstlane(sh.rs[buf]);
-        if (lane == pl) used |= 1u << rsel;
-        double pe[NS];                              // the pivot row's entries of this wave's slots
-        if (RS == 1 || rsel == 0) ds_pivot_row<RS, NS, 0, Q>(pe, R, pl);
-        else if (RS == 2 || rsel == 1) ds_pivot_row<RS, NS, (RS > 1 ? 1 : 0), Q>(pe, R, pl);
-        else ds_pivot_row<RS, NS, (RS > 2 ? 2 : 0), Q>(pe, R, pl);
-        if (owner) {
-            // column k + 1 sits in slot Q, or in slot Q + 1 when this is the last step of the phase (both
-            // formed, then selected: an index that depends on kk would make the register arrays dynamic)
-            constexpr int Q1 = (Q + 1 < NA) ? Q + 1 : Q;
-            const bool same = kk + 1 < DS_WAVES;
-            double C[RS];
-#pragma unroll
-            for (int r = 0; r < RS; ++r) {
-                const double ca = fma(-f[r], pe[Q], R[r][Q]), cb = fma(-f[r], pe[Q1], R[r][Q1]);
-                C[r] = same ? ca : cb;
-            }
-            ds_search<RS>(sh, C, used, k + 1, lane);
-            __builtin_amdgcn_s_setprio(0);
-        }
-#pragma unroll
-        for (int c = Q; c < NS; ++c)
-#pragma unroll
-            for (int r = 0; r < RS; ++r) R[r][c] = fma(-f[r], pe[c], R[r][c]);
-    }
-}
-
-// NR right-hand-side slots per wave: 4 (64 per workgroup) for many systems; 1 when few systems leave the chip
-// empty -- every workgroup eliminates its own copy of A, so narrower slices only shorten the step
-template <int RS, int NA, int NR>
-__global__ void __launch_bounds__(64 * DS_WAVES)
-k_dense_solve(const int n, const int nrhs, const double *__restrict__ A_, double *__restrict__ B_,
-              double *__restrict__ logdet_out) {
-    constexpr int NS = NA + NR, NT = 64 * DS_WAVES, BC = DS_WAVES * NR;
-    const int b = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const double *Ab = A_ + (size_t)b * n * n;
-    double *Bb = B_ + (size_t)b * n * nrhs + (size_t)sl * BC;
-    const int ncol = (nrhs - sl * BC < BC) ? nrhs - sl * BC : BC;      // columns of this slice
-    __shared__ __attribute__((aligned(16))) DenseSolveShared<RS> sh;
-    double R[RS][NS];                               // [0, NA): columns wave + 16 slot of A; then B
-    const int half = lane >> 5, l32 = lane & 31;
-    static_for([&](auto tt) {                       // A: 32 rows at a time, as a flat contiguous copy
-        constexpr int t = decltype(tt)::value, r = t >> 1;
-        const int row0 = DS_TROWS * t;
-        for (int e = tid; e < DS_TROWS * n; e += NT) {
-            const int rr = e / n, cc = e - rr * n;
-            sh.tile[rr * DS_LDT + cc] = (row0 + rr < n) ? Ab[(size_t)row0 * n + e] : 0.0;
-        }
-        __syncthreads();
-        if (half == (t & 1)) {
-#pragma unroll
-            for (int la = 0; la < NA; ++la) {
-                const int j = wave + DS_WAVES * la;
-                R[r][la] = (j < n) ? sh.tile[l32 * DS_LDT + j] : 0.0;
-            }
-        }
-        __syncthreads();
-    }, std::make_integer_sequence<int, 2 * RS>{});
-    static_for([&](auto tt) {                       // this slice of B
-        constexpr int t = decltype(tt)::value, r = t >> 1;
-        const int row0 = DS_TROWS * t;
-        for (int e = tid; e < DS_TROWS * BC; e += NT) {
-            const int rr = e / BC, cc = e - rr * BC;
-            sh.tile[rr * DS_LDT + cc] = (row0 + rr < n && cc < ncol) ? Bb[(size_t)(row0 + rr) * nrhs + cc] : 0.0;
-        }
-        __syncthreads();
-        if (half == (t & 1)) {
-#pragma unroll
-            for (int lr = 0; lr < NR; ++lr) R[r][NA + lr] = sh.tile[l32 * DS_LDT + wave + DS_WAVES * lr];
-        }
-        __syncthreads();
-    }, std::make_integer_sequence<int, 2 * RS>{});
-    unsigned used = 0;                              // bit r: row 64 r + lane already served as a pivot
-#pragma unroll
-    for (int r = 0; r < RS; ++r) if (64 * r + lane >= n) used |= 1u << r;
-    for (int e = tid; e < 64 * RS; e += NT) { sh.rowk[e] = -1; sh.rowpinv[e] = 0.0; }
-    __syncthreads();
-    if (wave == 0) {
-        double C[RS];
-#pragma unroll
-        for (int r = 0; r < RS; ++r) C[r] = R[r][0];
-        ds_search<RS>(sh, C, used, 0, lane);
-    }
-    static_for([&](auto q) { ds_phase<RS, NA, NR, decltype(q)::value>(sh, R, used, n, wave, lane); },
-               std::make_integer_sequence<int, NA>{});
-    __syncthreads();
-    // row 64 r + lane solved variable rowk[...]: X(rowk, :) = its B slots / pivot, through the tile
-    int myk[RS];
-#pragma unroll
-    for (int r = 0; r < RS; ++r) {
-        myk[r] = sh.rowk[64 * r + lane];
-        const double pinv = sh.rowpinv[64 * r + lane];
-#pragma unroll
-        for (int lr = 0; lr < NR; ++lr) R[r][NA + lr] *= pinv;
-    }
-    for (int row0 = 0; row0 < n; row0 += DS_TROWS) {
-#pragma unroll
-        for (int r = 0; r < RS; ++r) {
-            const int rel = myk[r] - row0;
-            if (rel >= 0 && rel < DS_TROWS) {
-#pragma unroll
-                for (int lr = 0; lr < NR; ++lr) sh.tile[rel * DS_LDT + wave + DS_WAVES * lr] = R[r][NA + lr];
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < DS_TROWS * BC; e += NT) {
-            const int rr = e / BC, cc = e - rr * BC;
-            if (row0 + rr < n && cc < ncol) Bb[(size_t)(row0 + rr) * nrhs + cc] = sh.tile[rr * DS_LDT + cc];
-        }
-        __syncthreads();
-    }
-    // log det A = sum over the pivots of log |pivot|, when det A > 0 (sign of the pivots' product times the
-    // parity of the row -> pivot-step permutation); NaN otherwise (det <= 0, a row never chosen, not finite)
-    if (logdet_out != nullptr && sl == 0 && wave == 0) {
-        double acc = 0.0;
-        int neg = 0;
-        bool bad = false;
-#pragma unroll
-        for (int r = 0; r < RS; ++r) {
-            const int row = 64 * r + lane;
-            if (row < n) {
-                const double pinv = sh.rowpinv[row];
-                const int kk = sh.rowk[row];
-                bad = bad || kk < 0 || kk >= n || !(fabs(pinv) > 0.0) || !(fabs(pinv) < 1.79e308);
-                acc -= log(fabs(pinv));
-                neg += (pinv < 0.0) ? 1 : 0;
-            }
-            sh.seen[row] = 0;
-        }
-        acc = wave_sum(acc);
-        neg = (int)__popcll(__ballot(neg & 1));     // parity of the number of negative pivots
-        const bool anybad = __ballot(bad) != 0ull;
-        wave_lds_fence();
-        if (lane == 0) {
-            int swaps = 0, steps = 0;
-            bool ok = !anybad;
-            for (int s0 = 0; ok && s0 < n; ++s0) {      // cycles of row -> rowk[row]; every walk is bounded by n
-                if (sh.seen[s0]) continue;
-                int j = s0, len = 0;
-                do {
-                    sh.seen[j] = 1;
-                    j = sh.rowk[j];
-                    ++len;
-                    ++steps;
-                } while (j != s0 && j >= 0 && j < n && !sh.seen[j] && steps <= n);
-                ok = ok && j == s0;                 // (anything else: not a permutation)
-                swaps += len - 1;
-            }
-            const bool positive = ok && (((neg + swaps) & 1) == 0) && (acc == acc);
-            logdet_out[b] = positive ? acc : __longlong_as_double(0x7ff8000000000000LL);
-        }
-    }
-}
-
-// Combine of GF_MATMUL_LOWER (dot_tril): the chunk transitions are DIAGONAL (D_c), so the start states are
-// a plain scan  F_{c+1} = loc_c + D_c o F_c  of 64 x R independent scalar sequences.  One workgroup of 16
-// waves per (problem, state row, 16 right-hand sides): a wave's four 16-lane groups take one segment of the
-// chunks each (64 segments per workgroup), lane & 15 = right-hand side (the states are stored [row][R]: 128-byte
-// pieces of a row; with lane = state row every lane touched its own cache line).  The segments are scanned
-// concurrently (zero start; eight chunks of loads in flight per lane: the loop is otherwise one dependent memory
-// round trip per chunk), the 64 segment summaries are chained in LDS, and every group rescans its segment from
-// its true start state, writing the start state of every chunk.  (With lane = right-hand side over all 64 and
-// 16 segments there were 64 workgroups per problem: a quarter of the chip, 45 us at cfg5's size.)
-constexpr int LCM_WAVES = 16, LCM_BATCH = 8, LCM_SEGS = 4 * LCM_WAVES;
-__global__ void __launch_bounds__(64 * LCM_WAVES)
-k_lincombine_mm(const int nch, const int R, const int rows, const double *__restrict__ Dch_,
-                double *__restrict__ F_state) {
-    const int pr = blockIdx.x, i = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int rr = lane & 15, sg = 4 * w + (lane >> 4);        // right-hand side within the 16, segment
-    const int rq = 16 * blockIdx.z + rr;
-    const int r = (rq < R) ? rq : (R - 1);          // idle lanes shadow the last right-hand side (no stores)
-    const bool rok = rq < R;
-    const int seg = (nch + LCM_SEGS - 1) / LCM_SEGS;
-    const int s0 = (sg * seg < nch) ? sg * seg : nch, s1 = (s0 + seg < nch) ? (s0 + seg) : nch;
-    __shared__ double s_end[LCM_SEGS][16], s_dec[LCM_SEGS][16];
-    auto F_at = [&](int s) { return F_state + ((size_t)pr * nch + s) * rows * R + (size_t)i * R + r; };
-    auto D_at = [&](int s) { return Dch_[((size_t)pr * nch + s) * rows + i]; };
-    // phase 1: segment end state from a zero start, and the segment's total decay
-    double cur = 0.0, dec = 1.0;
-    for (int s = s0; s < s1; s += LCM_BATCH) {
-        double loc[LCM_BATCH], dd[LCM_BATCH];
-#pragma unroll
-        for (int j = 0; j < LCM_BATCH; ++j) {
-            const bool ok = s + j < s1;
-            loc[j] = ok ? *F_at(s + j) : 0.0;
-            dd[j] = ok ? D_at(s + j) : 1.0;
-        }
-#pragma unroll
-        for (int j = 0; j < LCM_BATCH; ++j) { cur = fma(dd[j], cur, loc[j]); dec *= dd[j]; }
-    }
-    s_end[sg][rr] = cur;
-    s_dec[sg][rr] = dec;
-    __syncthreads();
-    // phase 2: this segment's true start state (chain of the summaries before it)
-    double start = 0.0;
-    for (int g2 = 0; g2 < sg; ++g2) start = fma(s_dec[g2][rr], start, s_end[g2][rr]);
-    // phase 3: rescan, leaving the true start state of every chunk in its slot
-    cur = start;
-    for (int s = s0; s < s1; s += LCM_BATCH) {
-        double loc[LCM_BATCH], dd[LCM_BATCH];
-#pragma unroll
-        for (int j = 0; j < LCM_BATCH; ++j) {
-            const bool ok = s + j < s1;
-            loc[j] = ok ? *F_at(s + j) : 0.0;
-            dd[j] = ok ? D_at(s + j) : 1.0;
-        }
-#pragma unroll
-        for (int j = 0; j < LCM_BATCH; ++j) {
-            if (rok && s + j < s1) *F_at(s + j) = cur;
-            cur = fma(dd[j], cur, loc[j]);
-        }
-    }
-}
-
-// D_c[j] = exp(-c_j * (sum of the reset spans inside chunk c))   (diagonal chunk transition of
-// matmul_lower; the first row of every chunk is a reset row)
-__global__ void __launch_bounds__(64)
-k_chunk_decay(const int64_t N, const int64_t chunk_len, const int nch, const int W,
-              const double *__restrict__ c_, const double *__restrict__ de_, double *__restrict__ D_out) {
-    const int lane = threadIdx.x, b = blockIdx.x;
-    const int pr = b / nch, ch = b - pr * nch;
-    const int64_t c0 = (int64_t)ch * chunk_len;
-    const int64_t rows = (N - c0 < chunk_len) ? (N - c0) : chunk_len;
-    const double *eg = de_ + (size_t)pr * N + c0;
-    double acc = 0.0;
-    for (int64_t n = lane; n < rows; n += 64) { const double v = eg[n]; if (v > 0.0) acc += v; }
-    acc = wave_sum(acc);
-    const double cj = (lane < W) ? c_[(size_t)pr * W + lane] : 0.0;
-    D_out[(size_t)b * 64 + lane] = fm_exp(-cj * acc);
 }
 
 // ------------------------------------------------------------------------------------
@@ -4957,975 +3373,6 @@ __global__ void k_finish(int B, int64_t N, const double *acc, const int32_t *inf
     if (out) out[b] = bad ? -INFINITY : (-0.5 * (s1 + (double)N * 1.8378770664093453) - 0.5 * s2);
 }
 
-// ------------------------------------------------------------------------------------
-// K2/K3/K4 with ONE right-hand side: F lane-resident (column j = c*64 + lane), one wave
-// per problem, one DPP tree per row.
-// ------------------------------------------------------------------------------------
-struct SolveArgs {
-    int64_t N;
-    int W, ld, R, mode;
-    const double *U, *Wm, *P, *scale, *Y;
-    double *Z;
-    // chunk mode of k_solve_vec (gf_solve_chunk): the grid is (problem, chunk); chunk c sweeps its rows
-    // from the state in F_state slot (problem * nch + c) -- [ld] doubles, pending push folded, the decay
-    // of the boundary left to the receiving chunk -- and leaves its end state there; store = 0: no Z
-    int64_t chunk_len;
-    int nch, store;
-    double *F_state;
-};
-
-// MODE and SCALED are compile-time (the three sweeps x with / without the per-row scale): no
-// branches on the chain.  CT = 3 covers the full solar kernel (W = 172, ld = 176).
-template <int CT, int MODE, bool SCALED>
-__global__ void __launch_bounds__(64) k_solve_vec(const SolveArgs A) {
-    const int lane = threadIdx.x;
-    const int b = blockIdx.x / A.nch, ch = blockIdx.x - b * A.nch;     // (problem, chunk); nch = 1: whole series
-    const int64_t N = A.N;
-    const int ld = A.ld;
-    const size_t pb = (size_t)b * N;
-    const int64_t c0 = (int64_t)ch * A.chunk_len;
-    const int64_t L = (N - c0 < A.chunk_len) ? (N - c0) : A.chunk_len;         // rows of this chunk
-    constexpr bool up = (MODE == GF_SOLVE_UPPER);
-    constexpr bool mm = (MODE == GF_MATMUL_LOWER);
-    // "push" rows multiply the carried value into F; "pull" rows are dotted with F
-    const double *__restrict__ push = (up ? A.U : A.Wm) + pb * ld;
-    const double *__restrict__ pull = (up ? A.Wm : A.U) + pb * ld;
-    const double *__restrict__ Pg = A.P + pb * ld;
-    const double *Y = A.Y + pb;         // (Z may alias Y: rows are read ahead of, never behind, the writes)
-    const double *__restrict__ sc = SCALED ? A.scale + pb : nullptr;
-    double *Z = A.Z + pb;
-    // The sweep is one dependent chain per row (two FMAs, a 64-lane reduction: a few hundred cycles),
-    // so a row's operands -- three generator rows, y, the scale -- must already be in registers when
-    // the chain reaches it.  They are fetched DEPTH rows ahead into a register ring, by plain
-    // unconditional vector loads that nothing touches until the row is processed: pad lanes read a
-    // clamped column and are switched off by a 0/1 factor on P, the per-row scalars go through the
-    // same (in-order) vector-load queue via an opaque zero lane offset instead of scalar loads the
-    // wave would have to wait for on the spot.  Without the ring every row waited for its own HBM
-    // round trip: 1.6 us per row.
-    constexpr int DEPTH = 8;
-    const int vz = __builtin_amdgcn_mbcnt_lo(0u, 0u);      // 0 in every lane, not known to be uniform
-    int col[CT];
-    double okf[CT], F[CT];
-    double *__restrict__ Fs = A.F_state ? A.F_state + (size_t)blockIdx.x * ld : nullptr;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const int j = c * 64 + lane;
-        col[c] = j < ld ? j : ld - 1;
-        okf[c] = j < ld ? 1.0 : 0.0;
-        F[c] = Fs ? Fs[col[c]] * okf[c] : 0.0;
-    }
-    auto row_of = [&](const int64_t s) { return up ? (c0 + L - 1 - s) : (c0 + s); };
-    auto scaled = [&](const double yv, const double sv) {
-        if constexpr (SCALED) return mm ? yv * sqrt(sv) : yv / sv;
-        else return yv;
-    };
-
-    // the first row of the sweep carries nothing itself (carry = 0): the state handed over already holds
-    // the pending push of the row before it (F = 0 at the very start).  The decay of a chunk boundary is
-    // applied by the chunk that OWNS the boundary row -- its first row: ascending sweeps apply it on entry
-    // (the first processed row), the descending sweep on exit, so that the homogeneous part of a chunk is
-    // exactly its closed-loop transition Phi_c (Phi_c^T going down), as in k_lin1.
-    double carry = 0.0;
-    double rp[DEPTH][CT], ra[DEPTH][CT], rb[DEPTH][CT], ry[DEPTH], rs[DEPTH];
-    auto clampN = [&](const int64_t n) { return n < 0 ? (int64_t)0 : (n > N - 1 ? N - 1 : n); };
-    auto fetch = [&](const int slot, int64_t s) {
-        s = s < L ? s : L - 1;                      // past the end: re-read the last row, never used
-        const int64_t n = row_of(s);
-        const int64_t prev = clampN(up ? (n + 1) : (n - 1));    // (rows outside the series: multiplied by 0)
-        const int64_t prow = clampN(up ? (n + 1) : n);
-        ry[slot] = Y[n + vz];
-        rs[slot] = SCALED ? sc[n + vz] : 1.0;
-        const bool entry = up && Fs != nullptr && s == 0;      // descending chunk entry: no decay here
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            rp[slot][c] = entry ? 1.0 : Pg[(size_t)prow * ld + col[c]];
-            ra[slot][c] = push[(size_t)prev * ld + col[c]];
-            rb[slot][c] = pull[(size_t)n * ld + col[c]];
-        }
-    };
-    auto process = [&](const int64_t s, const double (&p)[CT], const double (&a)[CT],
-                       const double (&q)[CT], const double yv, const double sv) {
-        const int64_t n = row_of(s);
-        const double yn = scaled(yv, sv);
-        double dot = 0.0;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            F[c] = (p[c] * okf[c]) * fma(a[c], carry, F[c]);
-            dot = fma(q[c], F[c], dot);
-        }
-        dot = wave_sum(dot);
-        const double zn = mm ? (yn + dot) : (yn - dot);
-        if (A.store && lane == 0) Z[n] = zn;
-        carry = mm ? yn : zn;
-    };
-    int64_t s0 = 0;
-    if (L >= DEPTH) {
-#pragma unroll
-        for (int k = 0; k < DEPTH; ++k) fetch(k, k);
-        for (; s0 + DEPTH <= L; s0 += DEPTH) {
-#pragma unroll
-            for (int k = 0; k < DEPTH; ++k) {
-                process(s0 + k, rp[k], ra[k], rb[k], ry[k], rs[k]);
-                fetch(k, s0 + k + DEPTH);
-            }
-        }
-    }
-    for (; s0 < L; ++s0) {                          // fewer than DEPTH rows left
-        fetch(0, s0);
-        process(s0, rp[0], ra[0], rb[0], ry[0], rs[0]);
-    }
-    if (Fs) {                                       // end state: pending push folded, no decay
-        const int64_t last = row_of(L - 1);
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const double a = push[(size_t)last * ld + col[c]];
-            double v = fma(a, carry, F[c]);
-            if (up) v *= Pg[(size_t)last * ld + col[c]];       // cross the chunk's first-row boundary
-            if (c * 64 + lane < ld) Fs[c * 64 + lane] = v;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// K2/K3/K4 with R right-hand sides: lane r of a wave owns column r of Y/Z and the W-vector
-// F[:, r] in VGPRs; the generator rows are wave-uniform operands (prefetched by vector loads,
-// broadcast through LDS).  Widths above 64 split j over NWV waves (one LDS exchange/row).
-// ------------------------------------------------------------------------------------
-template <int JB, int NWV>
-__global__ void __launch_bounds__(64 * NWV) k_solve_rhs(const SolveArgs A) {
-    static_assert(JB % 2 == 0 && JB <= 64, "column slice: even, at most one wave wide");
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // (problem, chunk): nch = 1 is the whole series; chunk mode (F_state != nullptr) as in k_solve_vec --
-    // start state in, end state out (pending push folded; ascending sweeps apply a boundary's decay on
-    // entry, the descending one on exit), Z only when A.store
-    const int b = blockIdx.y / A.nch, ch = blockIdx.y - b * A.nch;
-    const int r = blockIdx.x * 64 + lane;
-    const int R = A.R;
-    const bool rok = r < R;
-    const int rc = rok ? r : (R - 1);   // idle lanes re-read the last right-hand side, never store
-    const int64_t N = A.N;
-    const int ld = A.ld;
-    const size_t pb = (size_t)b * N;
-    const int64_t c0 = (int64_t)ch * A.chunk_len;
-    const int64_t L = (N - c0 < A.chunk_len) ? (N - c0) : A.chunk_len;
-    const bool up = (A.mode == GF_SOLVE_UPPER);
-    const bool mm = (A.mode == GF_MATMUL_LOWER);
-    const double *__restrict__ push = (up ? A.U : A.Wm) + pb * ld;
-    const double *__restrict__ pull = (up ? A.Wm : A.U) + pb * ld;
-    const double *__restrict__ Pg = A.P + pb * ld;
-    const double *Y = A.Y + pb * R;     // (Z may alias Y: rows are read ahead of, never behind, the writes)
-    const double *__restrict__ sc = A.scale ? A.scale + pb : nullptr;
-    double *Z = A.Z + pb * R;
-    double *__restrict__ Fs = A.F_state ? A.F_state + (size_t)blockIdx.y * ld * R : nullptr;     // [ld][R]
-    const int j0 = wave * JB;
-    int jn = ld - j0;                    // valid columns in this wave's slice
-    if (jn > JB) jn = JB;
-    if (jn < 0) jn = 0;
-    // The generator rows of this wave's slice are wave-uniform operands of the per-lane recurrences.
-    // Lane l fetches column j0 + l of the three rows DEPTH rows ahead (plain vector loads into a
-    // register ring), the row being processed is staged in LDS and read back as broadcasts.  (As
-    // scalar loads issued when the row needed them, they cost a memory round trip per row: 5.6 us
-    // per row at W = 172.)
-    constexpr int DEPTH = 8;
-    const bool lok = lane < jn;
-    const int jl = j0 + (lok ? lane : (jn > 0 ? jn - 1 : 0));
-    const int jc = jl < ld ? jl : ld - 1;
-    const int vz = __builtin_amdgcn_mbcnt_lo(0u, 0u);
-
-    __shared__ __attribute__((aligned(16))) double s_row[NWV][3][64];
-    __shared__ double s_dot[2][NWV][64];
-    double *sp = s_row[wave][0], *sa = s_row[wave][1], *sb = s_row[wave][2];
-
-    double F[JB];
-#pragma unroll
-    for (int j = 0; j < JB; ++j) F[j] = (Fs && j < jn) ? Fs[(size_t)(j0 + j) * R + rc] : 0.0;
-    auto row_of = [&](const int64_t s) { return up ? (c0 + L - 1 - s) : (c0 + s); };
-    auto scaled = [&](const double yv, const double sv) {
-        return sc ? (mm ? yv * sqrt(sv) : yv / sv) : yv;
-    };
-    // the first row of the sweep carries nothing itself: the state handed over already holds the pending
-    // push of the row before it (zero at the very start)
-    double carry = 0.0;
-    double rp[DEPTH], ra[DEPTH], rb[DEPTH], ry[DEPTH], rs[DEPTH];
-    auto clampN = [&](const int64_t n) { return n < 0 ? (int64_t)0 : (n > N - 1 ? N - 1 : n); };
-    auto fetch = [&](const int slot, int64_t s) {
-        s = s < L ? s : L - 1;                      // past the end: re-read the last row, never used
-        const int64_t n = row_of(s);
-        const int64_t prev = clampN(up ? (n + 1) : (n - 1));    // (rows outside the series: multiplied by 0)
-        const int64_t prow = clampN(up ? (n + 1) : n);
-        ry[slot] = Y[(size_t)n * R + rc];
-        rs[slot] = sc ? sc[n + vz] : 1.0;
-        const bool entry = up && Fs != nullptr && s == 0;      // descending chunk entry: no decay here
-        rp[slot] = entry ? 1.0 : Pg[(size_t)prow * ld + jc];
-        ra[slot] = push[(size_t)prev * ld + jc];
-        rb[slot] = pull[(size_t)n * ld + jc];
-    };
-    auto process = [&](const int64_t s, const double pv, const double av, const double bv,
-                       const double yv, const double sv) {
-        const int64_t n = row_of(s);
-        const double yn = scaled(yv, sv);
-        wave_lds_fence();                           // the previous row's broadcasts are done
-        sp[lane] = lok ? pv : 0.0;                  // columns past the slice: all zero, F stays 0
-        sa[lane] = lok ? av : 0.0;
-        sb[lane] = lok ? bv : 0.0;
-        wave_lds_fence();
-        double dot = 0.0;
-#pragma unroll
-        for (int j = 0; j < JB; j += 2) {
-            const double2 p2 = *(const double2 *)(sp + j), a2 = *(const double2 *)(sa + j);
-            const double2 b2 = *(const double2 *)(sb + j);
-            F[j] = p2.x * fma(a2.x, carry, F[j]);
-            F[j + 1] = p2.y * fma(a2.y, carry, F[j + 1]);
-            dot = fma(b2.x, F[j], dot);
-            dot = fma(b2.y, F[j + 1], dot);
-        }
-        if constexpr (NWV > 1) {
-            const int buf = (int)(s & 1);
-            s_dot[buf][wave][lane] = dot;
-            wg_lds_barrier();
-            dot = s_dot[buf][0][lane];
-#pragma unroll
-            for (int w2 = 1; w2 < NWV; ++w2) dot += s_dot[buf][w2][lane];
-        }
-        const double zn = mm ? (yn + dot) : (yn - dot);
-        if (A.store && rok && wave == 0) Z[(size_t)n * R + r] = zn;
-        carry = mm ? yn : zn;
-    };
-    int64_t s0 = 0;
-    if (L >= DEPTH) {
-#pragma unroll
-        for (int k = 0; k < DEPTH; ++k) fetch(k, k);
-        for (; s0 + DEPTH <= L; s0 += DEPTH) {
-#pragma unroll
-            for (int k = 0; k < DEPTH; ++k) {
-                process(s0 + k, rp[k], ra[k], rb[k], ry[k], rs[k]);
-                fetch(k, s0 + k + DEPTH);
-            }
-        }
-    }
-    for (; s0 < L; ++s0) {                          // fewer than DEPTH rows left
-        fetch(0, s0);
-        process(s0, rp[0], ra[0], rb[0], ry[0], rs[0]);
-    }
-    if (Fs) {                                       // end state: pending push folded, no decay
-        const int64_t last = row_of(L - 1);
-        wave_lds_fence();
-        sa[lane] = lok ? push[(size_t)last * ld + jc] : 0.0;
-        sp[lane] = (lok && up) ? Pg[(size_t)last * ld + jc] : 1.0;     // cross the chunk's first-row boundary
-        wave_lds_fence();
-        if (rok) {
-#pragma unroll
-            for (int j = 0; j < JB; ++j)
-                if (j < jn) Fs[(size_t)(j0 + j) * R + r] = sp[j] * fma(sa[j], carry, F[j]);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// K5: conditional mean at new times.  One wave per (problem, direction);
-// F lane-resident; consecutive observed rows advance with the stored propagator rows P2,
-// only the hop from the last observed row to the query time needs an exp.
-//   dir 0 (lower): ascending;  dir 1 (upper): descending.  Partial results go to work[dir].
-// ------------------------------------------------------------------------------------
-struct GmmArgs {
-    int64_t M, N;
-    int W, ld;
-    const double *c;
-    const double *t1; int64_t t1_bs;
-    const double *U1, *V1;
-    const double *t2; int64_t t2_bs;
-    const double *U2, *V2, *P2, *alpha;
-    const int64_t *qidx;            // [B][M]: number of observed rows with t2 <= t1[m]
-    double *work;
-};
-
-// Rows are streamed in unrolled blocks of GB (all loads of a block are issued before its
-// FMAs: one dependent FMA per row instead of one memory round trip per row); a query is
-// emitted when the sweep passes its row:  lower: after row qidx-1;  upper: after row qidx.
-template <int CT>
-__global__ void __launch_bounds__(64) k_gmm(const GmmArgs A) {
-    constexpr int GB = 8;
-    const int lane = threadIdx.x, b = blockIdx.x, dir = blockIdx.y;
-    const int64_t M = A.M, N = A.N;
-    const int ld = A.ld;
-    const double *t1 = A.t1 + (size_t)b * A.t1_bs;
-    const double *t2 = A.t2 + (size_t)b * A.t2_bs;
-    const double *__restrict__ Q1 = (dir == 0 ? A.U1 : A.V1) + (size_t)b * M * ld;   // query-side rows
-    const double *__restrict__ G2 = (dir == 0 ? A.V2 : A.U2) + (size_t)b * N * ld;   // data-side rows
-    const double *__restrict__ P2 = A.P2 + (size_t)b * N * ld;
-    const double *__restrict__ al = A.alpha + (size_t)b * N;
-    const int64_t *__restrict__ qi = A.qidx + (size_t)b * M;
-    double *out = A.work + ((size_t)b * 2 + dir) * M;
-    bool colok[CT];
-    int col[CT];
-    double F[CT], cj[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const int j = c * 64 + lane;
-        colok[c] = j < A.W;
-        col[c] = colok[c] ? j : 0;      // pad lanes re-read column 0 and are masked in registers
-        F[c] = 0.0;
-        cj[c] = colok[c] ? A.c[(size_t)b * A.W + j] : 0.0;
-    }
-    auto emit = [&](int64_t m, double tdata) {
-        const double dt = (dir == 0) ? (tdata - t1[m]) : (t1[m] - tdata);   // <= 0
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-            if (colok[c]) acc = fma(Q1[(size_t)m * ld + col[c]] * exp(cj[c] * dt), F[c], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) out[m] = acc;
-    };
-    if (dir == 0) {
-        int64_t m = 0;
-        while (m < M && qi[m] == 0) { if (lane == 0) out[m] = 0.0; ++m; }
-        int64_t next = (m < M) ? qi[m] : (N + 1);          // emit after row next-1
-        int64_t n = 0;
-        for (; n + GB <= N; n += GB) {
-            double pr[GB][CT], gr[GB][CT], an[GB];
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                an[k] = al[n + k];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const size_t o = (size_t)(n + k) * ld + col[c];
-                    pr[k][c] = P2[o];                       // exp(c (t2[n-1] - t2[n])); row 0: 1
-                    gr[k][c] = G2[o];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-#pragma unroll
-                for (int c = 0; c < CT; ++c) F[c] = colok[c] ? fma(pr[k][c], F[c], gr[k][c] * an[k]) : 0.0;
-                while (next == n + k + 1) {                 // wave-uniform, rare
-                    emit(m, t2[n + k]);
-                    ++m;
-                    next = (m < M) ? qi[m] : (N + 1);
-                }
-            }
-        }
-        for (; n < N; ++n) {
-            const double a1 = al[n];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const size_t o = (size_t)n * ld + col[c];
-                F[c] = colok[c] ? fma(P2[o], F[c], G2[o] * a1) : 0.0;
-            }
-            while (next == n + 1) {
-                emit(m, t2[n]);
-                ++m;
-                next = (m < M) ? qi[m] : (N + 1);
-            }
-        }
-    } else {
-        int64_t m = M - 1;
-        while (m >= 0 && qi[m] == N) { if (lane == 0) out[m] = 0.0; --m; }
-        int64_t next = (m >= 0) ? qi[m] : -1;               // emit after row next (descending)
-        int64_t n = N - 1;
-        for (; n - GB + 1 >= 0; n -= GB) {
-            double pr[GB][CT], gr[GB][CT], an[GB];
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                const int64_t r = n - k;
-                an[k] = al[r];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const size_t o = (size_t)r * ld + col[c];
-                    // exp(c (t2[r] - t2[r+1])) is propagator row r+1 (the last row decays nothing)
-                    pr[k][c] = (r + 1 < N) ? P2[o + ld] : 1.0;
-                    gr[k][c] = G2[o];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-#pragma unroll
-                for (int c = 0; c < CT; ++c) F[c] = colok[c] ? fma(pr[k][c], F[c], gr[k][c] * an[k]) : 0.0;
-                while (next == n - k) {
-                    emit(m, t2[n - k]);
-                    --m;
-                    next = (m >= 0) ? qi[m] : -1;
-                }
-            }
-        }
-        for (; n >= 0; --n) {
-            const double a1 = al[n];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const size_t o = (size_t)n * ld + col[c];
-                const double pj = (n + 1 < N) ? P2[o + ld] : 1.0;
-                F[c] = colok[c] ? fma(pj, F[c], G2[o] * a1) : 0.0;
-            }
-            while (next == n) {
-                emit(m, t2[n]);
-                --m;
-                next = (m >= 0) ? qi[m] : -1;
-            }
-        }
-    }
-}
-
-// ---- chunk-parallel form (long series): the recurrence F <- p o F + g alpha is linear with a
-// DIAGONAL transition, so chunks of rows are swept concurrently:
-//   k_gmm_chunk<CT, 0>  local pass from F = 0: end state F_loc and the chunk's decay D = prod p
-//   k_gmm_scan          F_start of every chunk (sequential over chunks, 64-wide FMAs)
-//   k_gmm_chunk<CT, 1>  chunks that contain queries are swept again from F_start and emit
-// Row ranges: dir 0 sweeps rows a..b ascending with p_n = P2[n]; dir 1 sweeps b..a descending
-// with p_n = P2[n+1] (1 for the last row of the series).  A query is emitted after row
-// qidx-1 (dir 0) / row qidx (dir 1), as in k_gmm.
-struct GmmChunk {
-    int64_t chunk_len;
-    int nch;
-    double *Floc, *Dloc, *Fstart;   // [B][2][nch][CT*64]
-};
-
-__device__ __forceinline__ int64_t gmm_lower_bound(const int64_t *q, int64_t M, int64_t v) {
-    int64_t lo = 0, hi = M;         // first m with q[m] >= v
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (q[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
-template <int CT, int PHASE>
-__global__ void __launch_bounds__(64) k_gmm_chunk(const GmmArgs A, const GmmChunk C) {
-    const int lane = threadIdx.x, b = blockIdx.x, dir = blockIdx.y, ch = blockIdx.z;
-    const int64_t M = A.M, N = A.N;
-    const int ld = A.ld;
-    const int64_t a = (int64_t)ch * C.chunk_len;
-    const int64_t e = (a + C.chunk_len < N) ? (a + C.chunk_len) : N;      // rows [a, e)
-    const double *t1 = A.t1 + (size_t)b * A.t1_bs;
-    const double *t2 = A.t2 + (size_t)b * A.t2_bs;
-    const double *__restrict__ Q1 = (dir == 0 ? A.U1 : A.V1) + (size_t)b * M * ld;
-    const double *__restrict__ G2 = (dir == 0 ? A.V2 : A.U2) + (size_t)b * N * ld;
-    const double *__restrict__ P2 = A.P2 + (size_t)b * N * ld;
-    const double *__restrict__ al = A.alpha + (size_t)b * N;
-    const int64_t *__restrict__ qi = A.qidx + (size_t)b * M;
-    double *out = A.work + ((size_t)b * 2 + dir) * M;
-    const size_t slot = (((size_t)b * 2 + dir) * C.nch + ch) * (CT * 64);
-    bool colok[CT];
-    int col[CT];
-    double F[CT], D[CT], cj[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const int j = c * 64 + lane;
-        colok[c] = j < A.W;
-        col[c] = colok[c] ? j : 0;
-        F[c] = (PHASE == 1) ? C.Fstart[slot + c * 64 + lane] : 0.0;
-        D[c] = 1.0;
-        cj[c] = colok[c] ? A.c[(size_t)b * A.W + j] : 0.0;
-    }
-    // queries of this chunk: [m_lo, m_hi)
-    int64_t m_lo = 0, m_hi = 0;
-    if (PHASE == 1) {
-        if (dir == 0) { m_lo = gmm_lower_bound(qi, M, a + 1); m_hi = gmm_lower_bound(qi, M, e + 1); }
-        else          { m_lo = gmm_lower_bound(qi, M, a);     m_hi = gmm_lower_bound(qi, M, e); }
-        // queries before the first / after the last observed row get no contribution
-        if (dir == 0 && ch == 0) for (int64_t m = lane; m < m_lo; m += 64) out[m] = 0.0;
-        if (dir == 1 && ch == C.nch - 1) for (int64_t m = m_hi + lane; m < M; m += 64) out[m] = 0.0;
-        if (m_lo == m_hi) return;
-    }
-    auto emit = [&](int64_t m, double tdata) {
-        const double dt = (dir == 0) ? (tdata - t1[m]) : (t1[m] - tdata);   // <= 0
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-            if (colok[c]) acc = fma(Q1[(size_t)m * ld + col[c]] * exp(cj[c] * dt), F[c], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) out[m] = acc;
-    };
-    constexpr int GB = 8;
-    if (dir == 0) {
-        int64_t m = m_lo;
-        int64_t next = (PHASE == 1) ? qi[m] : (N + 2);                      // emit after row next-1
-        const int64_t last = (PHASE == 1) ? qi[m_hi - 1] : e;               // rows [a, last)
-        for (int64_t n = a; n < last; n += GB) {
-            double pr[GB][CT], gr[GB][CT], an[GB];
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                const int64_t r = (n + k < last) ? (n + k) : (last - 1);
-                an[k] = al[r];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const size_t o = (size_t)r * ld + col[c];
-                    pr[k][c] = P2[o];
-                    gr[k][c] = G2[o];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                if (n + k < last) {                                          // wave-uniform
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        F[c] = colok[c] ? fma(pr[k][c], F[c], gr[k][c] * an[k]) : 0.0;
-                        if (PHASE == 0) D[c] *= pr[k][c];
-                    }
-                    if (PHASE == 1) {
-                        while (m < m_hi && next == n + k + 1) {
-                            emit(m, t2[n + k]);
-                            ++m;
-                            next = (m < m_hi) ? qi[m] : (N + 2);
-                        }
-                    }
-                }
-            }
-        }
-    } else {
-        int64_t m = m_hi - 1;
-        int64_t next = (PHASE == 1) ? qi[m] : -2;                           // emit after row next
-        const int64_t first = (PHASE == 1) ? qi[m_lo] : a;                  // rows (e-1) .. first
-        for (int64_t n = e - 1; n >= first; n -= GB) {
-            double pr[GB][CT], gr[GB][CT], an[GB];
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                const int64_t r = (n - k >= first) ? (n - k) : first;
-                an[k] = al[r];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const size_t o = (size_t)r * ld + col[c];
-                    pr[k][c] = (r + 1 < N) ? P2[o + ld] : 1.0;
-                    gr[k][c] = G2[o];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                if (n - k >= first) {
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) {
-                        F[c] = colok[c] ? fma(pr[k][c], F[c], gr[k][c] * an[k]) : 0.0;
-                        if (PHASE == 0) D[c] *= pr[k][c];
-                    }
-                    if (PHASE == 1) {
-                        while (m >= m_lo && next == n - k) {
-                            emit(m, t2[n - k]);
-                            --m;
-                            next = (m >= m_lo) ? qi[m] : -2;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (PHASE == 0) {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            C.Floc[slot + c * 64 + lane] = F[c];
-            C.Dloc[slot + c * 64 + lane] = colok[c] ? D[c] : 0.0;
-        }
-    }
-}
-
-// F_start of every chunk.  dir 0: F_start[0] = 0, F_start[c+1] = D_c F_start[c] + F_loc[c];
-// dir 1 runs from the last chunk down.
-__global__ void __launch_bounds__(256) k_gmm_scan(const int CTW, const GmmChunk C) {
-    const int b = blockIdx.x, dir = blockIdx.y;
-    const size_t base = ((size_t)b * 2 + dir) * C.nch * CTW;
-    // sixteen chunks' (D, F_loc) are fetched before their sixteen dependent FMAs: one memory round trip per
-    // chunk made the scan 0.28 ms for the 1024 chunks of a 1e6-row series (a tenth of predict at new times)
-    constexpr int GB = 16;
-    for (int j = threadIdx.x; j < CTW; j += 256) {
-        double F = 0.0;
-        for (int s0 = 0; s0 < C.nch; s0 += GB) {
-            double d[GB], f[GB];
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                int sidx = s0 + k;
-                sidx = (sidx < C.nch) ? sidx : C.nch - 1;
-                const int c = (dir == 0) ? sidx : C.nch - 1 - sidx;
-                const size_t o = base + (size_t)c * CTW + j;
-                d[k] = C.Dloc[o];
-                f[k] = C.Floc[o];
-            }
-#pragma unroll
-            for (int k = 0; k < GB; ++k) {
-                const int sidx = s0 + k;
-                if (sidx < C.nch) {
-                    const int c = (dir == 0) ? sidx : C.nch - 1 - sidx;
-                    C.Fstart[base + (size_t)c * CTW + j] = F;
-                    F = fma(d[k], F, f[k]);
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// k_cross: cross-covariance block K(t_n, t*_r) of the celerite kernel, written in the
-// [B][N][R] layout the multi-RHS sweeps take (conditional variance / covariance:
-// celerite2's ConditionalDistribution builds the same dense block on the host).
-//   K = sum_r a_r e^{-c_r tau} + sum_c (a_c cos d_c tau + b_c sin d_c tau) e^{-c_c tau},
-//   tau = |t_n - t*_r|.
-// A term is Re[(a - i b) w(tau)] with w(tau) = e^{(-c + i d) tau}, and w(tau_b + delta) = w(tau_b) w(delta): one
-// workgroup takes 256 rows, whose times span [tmin, tmax].  A query at or beyond tmax has tau = (t* - tmax) +
-// (tmax - t_n), one at or before tmin tau = (tmin - t*) + (t_n - tmin) -- both parts non-negative, both factors
-// decaying.  So per workgroup and term: (a - i b) w(t* - tmax) or w(tmin - t*) for every query (a table in LDS), and
-// per row w(tmax - t_n), w(t_n - tmin); an entry is then TWO FMAs per term instead of a sine, a cosine and an
-// exponential (1.9e9 of each per 64 queries at N = 1e6, J = 30: 5.3 ms, half of predict(return_var=True)).  Queries
-// inside the workgroup's span are evaluated entry by entry, as before (one workgroup per query).  Lane = row, RT
-// accumulators per lane; the row's RT entries leave as one contiguous run.
-// The exposure-integrated kernel differs from its coefficient form for tau < delta; the caller
-// patches those (at most a few per query) entries.
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ void cross_w(const double cc, const double dd, const double x, double &re, double &im) {
-    const double e = fm_exp(-cc * x);               // x >= 0
-    if (dd == 0.0) { re = e; im = 0.0; return; }    // (real term)
-    double si, cs;
-    const double ph = dd * x;
-    if (fabs(ph) < FM_SINCOS_RANGE) fm_sincos(ph, &si, &cs); else sincos(ph, &si, &cs);
-    re = e * cs;
-    im = e * si;
-}
-
-template <int RT>
-__global__ void __launch_bounds__(256)
-k_cross(const int64_t N, const int R, const int Jr, const int Jc,
-        const double *__restrict__ ar_, const double *__restrict__ cr_,
-        const double *__restrict__ ac_, const double *__restrict__ bc_,
-        const double *__restrict__ cc_, const double *__restrict__ dc_,
-        const double *__restrict__ t_, const int64_t t_bs,
-        const double *__restrict__ ts_, const int64_t ts_bs, double *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int J = Jr + Jc, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double *co = lds;                               // [J][4]: a, b, c, d (real terms: b = d = 0)
-    double2 *AE = reinterpret_cast<double2 *>(co + 4 * J);      // [RT][J]: (a - i b) w(tau_b), zero for queries inside
-    double *tq = reinterpret_cast<double *>(AE + (size_t)RT * J);  // [RT]
-    __shared__ double s_mm[2][4];
-    __shared__ unsigned long long s_side[3];        // bit r: query at / beyond tmax, at / before tmin, inside
-    for (int i = tid; i < J; i += 256) {
-        double *q = co + 4 * i;
-        if (i < Jr) { q[0] = ar_[(size_t)b * Jr + i]; q[1] = 0.0; q[2] = cr_[(size_t)b * Jr + i]; q[3] = 0.0; }
-        else {
-            const size_t o = (size_t)b * Jc + (i - Jr);
-            q[0] = ac_[o]; q[1] = bc_[o]; q[2] = cc_[o]; q[3] = dc_[o];
-        }
-    }
-    const int64_t n = (int64_t)blockIdx.x * 256 + tid;
-    const bool row = n < N;
-    const double tn = t_[(size_t)b * t_bs + (row ? n : N - 1)];
-    {
-        const double hi = wave_max(tn), lo = -wave_max(-tn);
-        if (lane == 0) { s_mm[0][wave] = hi; s_mm[1][wave] = lo; }
-    }
-    __syncthreads();
-    const double tmax = fmax(fmax(s_mm[0][0], s_mm[0][1]), fmax(s_mm[0][2], s_mm[0][3]));
-    const double tmin = fmin(fmin(s_mm[1][0], s_mm[1][1]), fmin(s_mm[1][2], s_mm[1][3]));
-    const double dL = tmax - tn, dR = tn - tmin;   // >= 0
-    double *og = out + ((size_t)b * N + (row ? n : 0)) * R;
-    for (int r0 = 0; r0 < R; r0 += RT) {
-        const int rt = (R - r0 < RT) ? R - r0 : RT;
-        __syncthreads();
-        if (tid < 64) {
-            const double q = (tid < rt) ? ts_[(size_t)b * ts_bs + r0 + tid] : 0.0;
-            if (tid < RT) tq[tid] = q;
-            const bool L = tid < rt && q >= tmax, Rr = tid < rt && !L && q <= tmin, in = tid < rt && !L && !Rr;
-            const unsigned long long mL = __ballot(L), mR = __ballot(Rr), mI = __ballot(in);
-            if (tid == 0) { s_side[0] = mL; s_side[1] = mR; s_side[2] = mI; }
-        }
-        __syncthreads();
-        const unsigned long long mL = s_side[0], mR = s_side[1], mI = s_side[2];
-        for (int e = tid; e < rt * J; e += 256) {
-            const int r = e / J, i = e - r * J;
-            const double *q = co + 4 * i;
-            double re = 0.0, im = 0.0;
-            if (!((mI >> r) & 1ull)) {
-                const double taub = ((mL >> r) & 1ull) ? tq[r] - tmax : tmin - tq[r];
-                double wr, wi;
-                cross_w(q[2], q[3], taub, wr, wi);
-                re = fma(q[0], wr, q[1] * wi);      // (a - i b)(wr + i wi)
-                im = fma(q[0], wi, -q[1] * wr);
-            }
-            AE[(size_t)r * J + i] = double2{re, im};
-        }
-        __syncthreads();
-        double acc[RT];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) acc[r] = 0.0;
-        // (the masks as scalars: the tests below become scalar branches, not exec-mask switches)
-        const unsigned mLlo = __builtin_amdgcn_readfirstlane((unsigned)mL), mLhi = __builtin_amdgcn_readfirstlane((unsigned)(mL >> 32));
-        const unsigned mRlo = __builtin_amdgcn_readfirstlane((unsigned)mR), mRhi = __builtin_amdgcn_readfirstlane((unsigned)(mR >> 32));
-        for (int i = 0; i < J; ++i) {
-            const double *q = co + 4 * i;
-            double lr = 0.0, li = 0.0, rr = 0.0, ri = 0.0;
-            if (mL) cross_w(q[2], q[3], dL, lr, li);            // (workgroup-uniform)
-            if (mR) cross_w(q[2], q[3], dR, rr, ri);
-            const double2 *ae = AE + i;
-#pragma unroll
-            for (int r = 0; r < RT; ++r) {
-                const bool isL = ((r < 32 ? mLlo : mLhi) >> (r & 31)) & 1u, isR = ((r < 32 ? mRlo : mRhi) >> (r & 31)) & 1u;
-                if (isL) { const double2 v = ae[(size_t)r * J]; acc[r] = fma(v.x, lr, fma(-v.y, li, acc[r])); }
-                else if (isR) { const double2 v = ae[(size_t)r * J]; acc[r] = fma(v.x, rr, fma(-v.y, ri, acc[r])); }
-            }
-        }
-        if (mI) {                                   // queries inside this workgroup's span: entry by entry
-#pragma unroll
-            for (int r = 0; r < RT; ++r) {
-                if ((mI >> r) & 1ull) {
-                    const double tau = fabs(tn - tq[r]);
-                    double k = 0.0;
-                    for (int i = 0; i < J; ++i) {
-                        const double *q = co + 4 * i;
-                        double wr, wi;
-                        cross_w(q[2], q[3], tau, wr, wi);
-                        k = fma(q[0], wr, fma(q[1], wi, k));
-                    }
-                    acc[r] = k;
-                }
-            }
-        }
-        if (row) {
-#pragma unroll
-            for (int r = 0; r < RT; ++r)
-                if (r < rt) og[r0 + r] = acc[r];
-        }
-    }
-}
-
-// mu[b][m] = work[b][0][m] + work[b][1][m]
-__global__ void k_add2(int64_t M, const double *work, double *mu) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t b = blockIdx.y;
-    if (m < M) mu[b * M + m] = work[(b * 2) * M + m] + work[(b * 2 + 1) * M + m];
-}
-
-// ------------------------------------------------------------------------------------
-// k_factor2w: the block-scaled recurrence of k_factor2 for widths beyond one wave (64 < W <= 256),
-// in k_factor's multi-wave mapping.  Scaled coordinates turn the per-row decay
-// S <- P (S + ...) P (two multiplies per element and row) into a rescaling at reset rows only:
-// per element and row one FMA for the pending rank-1 update and one for the mat-vec, instead of
-// the four operations of k_factor.  Inputs are gf_build_scaled's rows (U~, V~, a, de); the state
-// handed from tile to tile is k_factor's layout [RT rows][CT * 64 columns] with the pending
-// update folded in, F~ in column form.  Log-likelihood path only (no factor rows are stored).
-// ------------------------------------------------------------------------------------
-struct Factor2wArgs {
-    int64_t N, n_first;
-    int W, ld;
-    const double *c, *a, *Ut, *Vt, *de, *y;
-    int64_t y_bs;
-    double *d, *z, *S_state, *F_state;
-    int32_t *info;
-};
-
-template <int RB, int CT, int NW>
-__global__ void __launch_bounds__(64 * NW, 2) k_factor2w(const Factor2wArgs A) {     // 2 waves per SIMD
-    static_assert(RB % 4 == 0, "rows per wave must be a multiple of 4");
-    constexpr int WPC = CT * 64;
-    constexpr int RT = RB * NW;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int b = blockIdx.x;
-    if (A.info[b] != 0) return;         // an earlier tile of this problem already failed
-    const int ld = A.ld;
-    const size_t pb = (size_t)b * A.N;
-    const double *__restrict__ ag = A.a + pb;
-    const double *__restrict__ Ug = A.Ut + pb * ld;
-    const double *__restrict__ Vg = A.Vt + pb * ld;
-    const double *__restrict__ eg = A.de + pb;
-    const double *__restrict__ yg = A.y + (size_t)b * A.y_bs;
-    double *__restrict__ Sg = A.S_state + (size_t)b * RT * WPC;
-    double *__restrict__ Fg = A.F_state + (size_t)b * WPC;
-
-    __shared__ double s_part[2][NW][WPC];
-    __shared__ double s_vec[NW][3][WPC];
-    double *sv_u = s_vec[wave][0], *sv_w = s_vec[wave][1], *sv_e = s_vec[wave][2];
-
-    double S[RB][CT], Fv[CT], q[CT];         // pending update: S += w q^T, F~ += q z (q = r / d)
-    bool colok[CT];
-    int colc[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const int j = c * 64 + lane;
-        colok[c] = j < ld;
-        colc[c] = colok[c] ? j : (ld - 1);
-        Fv[c] = Fg[j];
-        q[c] = 0.0;
-        sv_w[j] = 0.0;
-#pragma unroll
-        for (int r = 0; r < RB; ++r) S[r][c] = Sg[(size_t)(wave * RB + r) * WPC + j];
-    }
-    double zp = 0.0;                    // z of the pending row
-    int32_t fail = 0;
-
-    // row operands one row ahead: plain unconditional loads (clamped pad columns, masked at use; the
-    // per-row scalars through the vector-load queue): the caller pads every buffer by two rows
-    const int vz = __builtin_amdgcn_mbcnt_lo(0u, 0u);
-    double un[CT], vn[CT], an, yn, en;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) { un[c] = Ug[colc[c]]; vn[c] = Vg[colc[c]]; }
-    an = ag[vz]; yn = yg[vz]; en = eg[vz];
-
-    for (int64_t n = 0; n < A.N; ++n) {
-        double u[CT], v[CT];
-        const double a_n = an, y_n = yn;
-        const double e_n = read_lane(en, 0);    // wave-uniform: say so
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            u[c] = colok[c] ? un[c] : 0.0;
-            v[c] = colok[c] ? vn[c] : 0.0;
-            sv_u[c * 64 + lane] = u[c];
-        }
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const size_t o = (size_t)(n + 1) * ld + colc[c];
-            un[c] = Ug[o];
-            vn[c] = Vg[o];
-        }
-        an = ag[n + 1 + vz]; yn = yg[n + 1 + vz]; en = eg[n + 1 + vz];
-
-        if (e_n >= 0.0) {               // reset row: fold the pending update, decay by exp(-c de)
-            double el[CT];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const int j = c * 64 + lane;     // (decay rates are read here: resets are rare, registers are not)
-                el[c] = (j < A.W) ? exp(-A.c[(size_t)b * A.W + j] * e_n) : 1.0;
-                sv_e[c * 64 + lane] = el[c];
-            }
-            wave_lds_fence();
-#pragma unroll
-            for (int r0 = 0; r0 < RB; r0 += 4) {    // batches of 4 rows, fenced: hipcc otherwise hoists
-                double wi[4], ei[4];                // every LDS read of the loop (and spills)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { wi[k] = sv_w[wave * RB + r0 + k]; ei[k] = sv_e[wave * RB + r0 + k]; }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int c = 0; c < CT; ++c)
-                        S[r0 + k][c] = fma(wi[k], q[c], S[r0 + k][c]) * (ei[k] * el[c]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int c = 0; c < CT; ++c) { Fv[c] = el[c] * fma(q[c], zp, Fv[c]); q[c] = 0.0; }
-            zp = 0.0;
-        }
-        wave_lds_fence();
-
-        double acc[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc[c] = 0.0;
-#pragma unroll
-        for (int r0 = 0; r0 < RB; r0 += 4) {
-            double wi[4], ui[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { wi[k] = sv_w[wave * RB + r0 + k]; ui[k] = sv_u[wave * RB + r0 + k]; }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    S[r0 + k][c] = fma(wi[k], q[c], S[r0 + k][c]);
-                    acc[c] = fma(ui[k], S[r0 + k][c], acc[c]);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        double tmp[CT];
-        if constexpr (NW > 1) {
-            const int buf = (int)(n & 1);
-#pragma unroll
-            for (int c = 0; c < CT; ++c) s_part[buf][wave][c * 64 + lane] = acc[c];
-            wg_lds_barrier();
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                double t2 = s_part[buf][0][c * 64 + lane];
-#pragma unroll
-                for (int w2 = 1; w2 < NW; ++w2) t2 += s_part[buf][w2][c * 64 + lane];
-                tmp[c] = t2;
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) tmp[c] = acc[c];
-        }
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            Fv[c] = fma(q[c], zp, Fv[c]);
-            s1 = fma(u[c], tmp[c], s1);
-            s2 = fma(u[c], Fv[c], s2);
-        }
-        wave_sum2(s1, s2);
-        const double dn = a_n - s1;
-        const double zn = y_n - s2;
-        if (!(dn > 0.0)) {              // uniform across the whole workgroup
-            const int64_t ng = A.n_first + n + 1;
-            fail = (int32_t)(ng > 0x7fffffff ? 0x7fffffff : ng);
-            break;
-        }
-        const double inv = fast_rcp(dn);
-        zp = zn;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const double r = v[c] - tmp[c];     // pad lanes: 0 - 0
-            q[c] = r * inv;
-            sv_w[c * 64 + lane] = r;
-        }
-        if (wave == 0 && lane == 0) { A.d[pb + n] = dn; A.z[pb + n] = zn; }
-    }
-    if (fail) {
-        if (wave == 0 && lane == 0) A.info[b] = fail;
-        return;
-    }
-    wave_lds_fence();
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-        const int i = wave * RB + r;
-        const double wi = sv_w[i];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) Sg[(size_t)i * WPC + c * 64 + lane] = fma(wi, q[c], S[r][c]);
-    }
-    if (wave == 0) {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) Fg[c * 64 + lane] = fma(q[c], zp, Fv[c]);
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// dispatch helpers
-// ------------------------------------------------------------------------------------
-template <int RB, int CT, int NW>
-int launch_factor(const FactorArgs &A, int B, int nch, hipStream_t st) {
-    hipLaunchKernelGGL((k_factor<RB, CT, NW>), dim3(nch, B), dim3(64 * NW), 0, st, A);
-    return check_launch("gf_factor");
-}
-
-int dispatch_factor(const FactorArgs &A, int B, int nch, hipStream_t st) {
-    const int W = A.W;
-    if (W <= 16)  return launch_factor<4, 1, 4>(A, B, nch, st);
-    if (W <= 32)  return launch_factor<8, 1, 4>(A, B, nch, st);
-    if (W <= 48)  return launch_factor<12, 1, 4>(A, B, nch, st);
-    if (W <= 64)  return launch_factor<16, 1, 4>(A, B, nch, st);
-    if (W <= 96)  return launch_factor<24, 2, 4>(A, B, nch, st);
-    if (W <= 128) return launch_factor<32, 2, 4>(A, B, nch, st);
-    if (W <= 192) return launch_factor<24, 3, 8>(A, B, nch, st);
-    return launch_factor<32, 4, 8>(A, B, nch, st);
-}
-
-template <int RB, int CT, int NW>
-int launch_factor2w(const Factor2wArgs &A, int B, hipStream_t st) {
-    hipLaunchKernelGGL((k_factor2w<RB, CT, NW>), dim3(B), dim3(64 * NW), 0, st, A);
-    return check_launch("gf_factor_scaled");
-}
-
-int dispatch_factor2w(const Factor2wArgs &A, int B, hipStream_t st) {      // same shapes as dispatch_factor
-    const int W = A.W;
-    if (W <= 96)  return launch_factor2w<24, 2, 4>(A, B, st);
-    if (W <= 128) return launch_factor2w<32, 2, 4>(A, B, st);
-    if (W <= 192) return launch_factor2w<24, 3, 8>(A, B, st);
-    return launch_factor2w<32, 4, 8>(A, B, st);
-}
-
-// Propagator rows of a factor stored in block-scaled form (rows u~, w~ = r/d and the reset spans de of
-// gf_chunk_sweep): in scaled coordinates the row-to-row propagator is 1, and exp(-c de) at a reset row.
-// With these rows the general-width sweeps (gf_solve) run on the scaled factor unchanged.
-__global__ void __launch_bounds__(256)
-k_scaled_propagator(const int64_t N, const int W, const int ld, const double *__restrict__ c_,
-                    const double *__restrict__ de_, double *__restrict__ P_out) {
-    const int b = blockIdx.y;
-    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = id / ld;
-    if (n >= N) return;
-    const int j = (int)(id - n * ld);
-    const double de = de_[(size_t)b * N + n];
-    const double cj = (j < W) ? c_[(size_t)b * W + j] : 0.0;
-    P_out[((size_t)b * N + n) * ld + j] = (de > 0.0) ? exp(-cj * de) : 1.0;
-}
-
 // wide fused sweep: NW = sweep waves for W + 1 columns (32 per wave, one spare column for the forward
 // solve), TR = rows per lane = W / 4 rounded up to a multiple of 4; one more wave generates the rows
 struct WideShape { int nw, tr; };
@@ -5988,129 +3435,6 @@ extern "C" {
 int gf_version(void) { return 100; }
 
 const char *gf_last_error(void) { return g_err; }
-
-int gf_leading_dim(int W) {
-    if (W < 1 || W > GF_MAX_WIDTH) return -1;
-    return (W + 15) / 16 * 16;
-}
-
-int gf_build_matrices(int B, int64_t N, int64_t n_first, int Jr, int Jc, int ld,
-                      const double *ar, const double *cr, const double *ac,
-                      const double *bc, const double *cc, const double *dc,
-                      const double *diag_add,
-                      const double *t, int64_t t_bs,
-                      const double *diag, int64_t diag_bs,
-                      double *a, double *U, double *V, double *P, void *stream) {
-    const int W = Jr + 2 * Jc;
-    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_build_matrices: empty problem (B=%d, N=%lld)", B, (long long)N);
-    if (check_width_ld("gf_build_matrices", W, ld)) return -1;
-    if (!t || !U || !V || (a && !diag_add)) return gf_internal_error(-1, "gf_build_matrices: null pointer");
-    BuildArgs A;
-    if (n_first < 0) return gf_internal_error(-1, "gf_build_matrices: negative n_first");
-    A.N = N; A.n_first = n_first; A.Jr = Jr; A.Jc = Jc; A.ld = ld; A.units = Jr + Jc + (ld - W);
-    A.ar = ar; A.cr = cr; A.ac = ac; A.bc = bc; A.cc = cc; A.dc = dc; A.diag_add = diag_add;
-    A.t = t; A.t_bs = t_bs; A.diag = diag; A.diag_bs = diag_bs;
-    A.a = a; A.U = U; A.V = V; A.P = P;
-    const int64_t total = N * A.units;
-    const int64_t blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_build_matrices: problem too large");
-    hipLaunchKernelGGL(k_build, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, A);
-    return check_launch("gf_build_matrices");
-}
-
-int64_t gf_state_size(int W) {
-    if (W < 1 || W > GF_MAX_WIDTH) return -1;
-    if (W <= 16)  return 16 * 64;
-    if (W <= 32)  return 32 * 64;
-    if (W <= 48)  return 48 * 64;
-    if (W <= 64)  return 64 * 64;
-    if (W <= 96)  return 96 * 128;
-    if (W <= 128) return 128 * 128;
-    if (W <= 192) return 192 * 192;
-    return 256 * 256;
-}
-
-int gf_state_cols(int W) {
-    if (W < 1 || W > GF_MAX_WIDTH) return -1;
-    return (W + 63) / 64 * 64;
-}
-
-int gf_factor(int B, int64_t N, int64_t n_first, int W, int ld,
-              const double *a, const double *U, const double *V, const double *P,
-              const double *y, int64_t y_bs,
-              double *d, double *Wm, double *z,
-              double *S_state, double *F_state, int32_t *info, void *stream) {
-    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_factor: empty problem (B=%d, N=%lld)", B, (long long)N);
-    if (check_width_ld("gf_factor", W, ld)) return -1;
-    if (!a || !U || !V || !P || !d || !info) return gf_internal_error(-1, "gf_factor: null pointer");
-    if (z && !y) return gf_internal_error(-1, "gf_factor: z requested without y");
-    FactorArgs A;
-    if (F_state && !S_state) return gf_internal_error(-1, "gf_factor: F_state without S_state");
-    A.N = N; A.chunk_len = N; A.n_first = n_first; A.W = W; A.ld = ld;
-    A.a = a; A.U = U; A.V = V; A.P = P; A.y = y; A.y_bs = y_bs;
-    A.d = d; A.Wm = Wm; A.z = z;
-    A.S_in = S_state; A.F_in = F_state; A.S_out = S_state; A.F_out = F_state;
-    A.info = info;
-    return dispatch_factor(A, B, 1, (hipStream_t)stream);
-}
-
-int gf_scaled_supported(int W) { return (W >= 1 && W <= 64) ? 1 : 0; }
-
-double gf_scaled_span(int long_span) { return long_span ? SC_SPAN_LONG : SC_SPAN; }
-
-// widths the block-scaled build + multi-wave sweep (k_build2 + k_factor2w) take beyond one wave
-int gf_scaled_wide_supported(int W) { return (W > 64 && W <= 192) ? 1 : 0; }   // (beyond: register spills, gf_factor is faster)
-
-int gf_build_scaled(int B, int64_t N, int64_t n_first, int Jr, int Jc, int ld,
-                    const double *ar, const double *cr, const double *ac,
-                    const double *bc, const double *cc, const double *dc,
-                    const double *diag_add, const double *cmax, int block,
-                    const double *t, int64_t t_bs,
-                    const double *diag, int64_t diag_bs,
-                    double *a, double *Ut, double *Vt, double *de, void *stream) {
-    const int W = Jr + 2 * Jc;
-    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_build_scaled: empty problem (B=%d, N=%lld)", B, (long long)N);
-    if (!gf_scaled_supported(W) && !gf_scaled_wide_supported(W)) return gf_internal_error(-1, "gf_build_scaled: width %d unsupported", W);
-    if (check_ld("gf_build_scaled", W, ld) || check_block("gf_build_scaled", block)
-        || check_n_first("gf_build_scaled", n_first, block)) return -1;
-    if (!t || !a || !Ut || !Vt || !de || !diag_add || !cmax) return gf_internal_error(-1, "gf_build_scaled: null pointer");
-    Build2Args A;
-    A.N = N; A.n_first = n_first; A.Jr = Jr; A.Jc = Jc; A.ld = ld; A.units = Jr + Jc + (ld - W);
-    A.block = block; A.gap = sweep_gap(block, GF_SWEEP_AUTO);
-    A.ar = ar; A.cr = cr; A.ac = ac; A.bc = bc; A.cc = cc; A.dc = dc; A.diag_add = diag_add; A.cmax = cmax;
-    A.t = t; A.t_bs = t_bs; A.diag = diag; A.diag_bs = diag_bs;
-    A.a = a; A.Ut = Ut; A.Vt = Vt; A.de = de;
-    const int64_t blocks = (N + B2_ROWS - 1) / B2_ROWS;
-    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_build_scaled: problem too large");
-    hipLaunchKernelGGL(k_build2, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, A);
-    return check_launch("gf_build_scaled");
-}
-
-int gf_factor_scaled(int B, int64_t N, int64_t n_first, int W, int ld, const double *c,
-                     const double *a, const double *Ut, const double *Vt, const double *de,
-                     const double *y, int64_t y_bs,
-                     double *d, double *z, double *S_state, double *F_state,
-                     int32_t *info, void *stream) {
-    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_factor_scaled: empty problem (B=%d, N=%lld)", B, (long long)N);
-    if (!gf_scaled_supported(W) && !gf_scaled_wide_supported(W)) return gf_internal_error(-1, "gf_factor_scaled: width %d unsupported", W);
-    if (check_ld("gf_factor_scaled", W, ld)) return -1;
-    if (!c || !a || !Ut || !Vt || !de || !y || !d || !z || !S_state || !F_state || !info)
-        return gf_internal_error(-1, "gf_factor_scaled: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (W > 64) {                       // state: gf_state_size(W) / gf_state_cols(W) doubles per problem
-        Factor2wArgs A;
-        A.N = N; A.n_first = n_first; A.W = W; A.ld = ld;
-        A.c = c; A.a = a; A.Ut = Ut; A.Vt = Vt; A.de = de; A.y = y; A.y_bs = y_bs;
-        A.d = d; A.z = z; A.S_state = S_state; A.F_state = F_state; A.info = info;
-        return dispatch_factor2w(A, B, st);
-    }
-    if (!dispatch_rows((W + 3) / 4 * 4, [&](auto r) {
-            hipLaunchKernelGGL((k_factor2<decltype(r)::value>), dim3(B), dim3(64), 0, st, N, n_first, ld, W, c, a, Ut, Vt,
-                               de, y, y_bs, d, z, S_state, F_state, info);
-        }))
-        return gf_internal_error(-1, "gf_factor_scaled: internal dispatch error");
-    return check_launch("gf_factor_scaled");
-}
 
 // Fused sweeps exist for W <= 63 (any mix of terms) and, for kernels of complex terms only, up to
 // W = 176 (k_factorw).  gf_fused_state_size: doubles of S_state per (problem, chunk) slot.
@@ -6615,73 +3939,6 @@ int gf_fused_row_stride(int Jr, int Jc) {
     return (W <= 63) ? 64 : 32 * wide_shape(W).nw;
 }
 
-int gf_scaled_propagator(int B, int64_t N, int W, int ld, const double *c, const double *de,
-                         double *P_out, void *stream) {
-    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_scaled_propagator: empty problem (N=%lld)", (long long)N);
-    if (W < 1 || ld < W) return gf_internal_error(-1, "gf_scaled_propagator: bad width / ld (W=%d, ld=%d)", W, ld);
-    if (!c || !de || !P_out) return gf_internal_error(-1, "gf_scaled_propagator: null pointer");
-    const int64_t blocks = (N * ld + 255) / 256;
-    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_scaled_propagator: problem too large");
-    hipLaunchKernelGGL(k_scaled_propagator, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream,
-                       N, W, ld, c, de, P_out);
-    return check_launch("gf_scaled_propagator");
-}
-
-int gf_chunk_linear(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int R,
-                    int scale, int store, const double *c,
-                    const double *Ut, const double *Wt, const double *d, const double *de,
-                    const double *Y, double *Z, double *F_state, void *stream) {
-    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_chunk_linear: bad mode %d", mode);
-    if (B < 1 || N < 1 || R < 1) return gf_internal_error(-1, "gf_chunk_linear: empty problem (N=%lld, R=%d)", (long long)N, R);
-    if (W < 1 || W > 63) return gf_internal_error(-1, "gf_chunk_linear: width %d unsupported (1..63)", W);
-    if (check_chunking("gf_chunk_linear", N, chunk_len, nch, 1)) return -1;
-    if (!c || !Ut || !Wt || !d || !de || !Y || !Z || !F_state) return gf_internal_error(-1, "gf_chunk_linear: null pointer");
-    LinArgs A;
-    A.N = N; A.chunk_len = chunk_len; A.nch = nch; A.W = W; A.mode = mode; A.scale = scale; A.store = store;
-    A.c = c; A.Ut = Ut; A.Wt = Wt; A.d = d; A.de = de; A.Y = Y; A.Z = Z; A.F_state = F_state; A.R = R;
-    hipStream_t st = (hipStream_t)stream;
-    bool ok = true;
-    if (R == 1) {
-        hipLaunchKernelGGL(k_lin1, dim3(B * nch), dim3(64), 0, st, A);
-    } else if (mode == GF_MATMUL_LOWER && R >= 16) {
-        // no feedback in this mode: blocks of 16 rows as matrix products (k_mmR_mfma)
-        // two waves per workgroup share the block's rows (32 right-hand sides each); one when R <= 32
-        const int nwv = (R > 32) ? 2 : 1;
-        const dim3 grid(B * nch, (R + 32 * nwv - 1) / (32 * nwv));
-        ok = dispatch_among<1, 2, 3, 4>((W + 15) / 16, [&](auto mt) {
-            constexpr int MT = decltype(mt)::value;
-            if (nwv == 2) hipLaunchKernelGGL((store ? k_mmR_mfma<MT, false, 2> : k_mmR_mfma<MT, true, 2>), grid, dim3(128), 0, st, A);
-            else          hipLaunchKernelGGL((store ? k_mmR_mfma<MT, false, 1> : k_mmR_mfma<MT, true, 1>), grid, dim3(64), 0, st, A);
-        });
-    } else {
-        ok = dispatch_rows((W + 3) / 4 * 4, [&](auto r) {
-            constexpr int Rw = decltype(r)::value;
-            hipLaunchKernelGGL((mode == GF_MATMUL_LOWER && !store ? k_linR7<Rw, true> : k_linR7<Rw, false>),
-                               dim3(B * nch, (R + 63) / 64), dim3(64), 0, st, A);
-        });
-    }
-    if (!ok) return gf_internal_error(-1, "gf_chunk_linear: internal dispatch error");
-    return check_launch("gf_chunk_linear");
-}
-
-int gf_chunk_linear_combine(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int R,
-                            const double *c, const double *de, const double *Phi,
-                            double *D_work, double *F_state, void *stream) {
-    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_chunk_linear_combine: bad mode %d", mode);
-    if (B < 1 || nch < 1 || R < 1) return gf_internal_error(-1, "gf_chunk_linear_combine: empty problem");
-    if (!F_state || (mode == GF_MATMUL_LOWER ? (!D_work || !c || !de) : !Phi))
-        return gf_internal_error(-1, "gf_chunk_linear_combine: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (mode == GF_MATMUL_LOWER) {
-        hipLaunchKernelGGL(k_chunk_decay, dim3(B * nch), dim3(64), 0, st, N, chunk_len, nch, W, c, de, D_work);
-        hipLaunchKernelGGL(k_lincombine_mm, dim3(B, 64, (R + 15) / 16), dim3(64 * LCM_WAVES), 0, st, nch, R, 64, D_work, F_state);
-        return check_launch("gf_chunk_linear_combine");
-    }
-    hipLaunchKernelGGL(k_lincombine<0>, dim3(B, R), dim3(256), 0, st, nch, nch, mode, R, Phi, D_work, F_state,
-                       (double *)nullptr);
-    return check_launch("gf_chunk_linear_combine");
-}
-
 int gf_chunk_segment_transitions(int B, int nch, int seg_len, const double *Phi, double *Psi_out,
                                  double *PhiT_out, double *PsiT_out, void *stream) {
     if (B < 1 || nch < 1 || seg_len < 1) return gf_internal_error(-1, "gf_chunk_segment_transitions: empty problem");
@@ -6695,56 +3952,6 @@ int gf_chunk_segment_transitions(int B, int nch, int seg_len, const double *Phi,
         hipLaunchKernelGGL(k_transpose64, dim3(B * nseg), dim3(256), 0, st, (const double *)Psi_out, PsiT_out);
     }
     return check_launch("gf_chunk_segment_transitions");
-}
-
-int gf_chunk_linear_combine_seg(int mode, int B, int nch, int seg_len, int R, const double *Phi,
-                                const double *Psi, const double *PhiT, const double *PsiT,
-                                double *F_state, double *V_work, void *stream) {
-    if (mode != GF_SOLVE_LOWER && mode != GF_SOLVE_UPPER)
-        return gf_internal_error(-1, "gf_chunk_linear_combine_seg: bad mode %d (the solves only)", mode);
-    if ((PhiT != nullptr) != (PsiT != nullptr)) return gf_internal_error(-1, "gf_chunk_linear_combine_seg: PhiT and PsiT go together");
-    if (mode == GF_SOLVE_UPPER && PhiT) { Phi = PhiT; Psi = PsiT; mode |= LC_TRANSPOSED; }
-    if (B < 1 || nch < 1 || R < 1 || seg_len < 1) return gf_internal_error(-1, "gf_chunk_linear_combine_seg: empty problem");
-    if (!Phi || !Psi || !F_state || !V_work) return gf_internal_error(-1, "gf_chunk_linear_combine_seg: null pointer");
-    const int nseg = (nch + seg_len - 1) / seg_len;
-    hipStream_t st = (hipStream_t)stream;
-    // the segment scans: per right-hand side, or 64 right-hand sides at a time on the matrix pipe
-    const bool many = R >= 16;
-    const dim3 gridR(B * nseg, (R + 63) / 64);
-    if (many) hipLaunchKernelGGL(k_lincombine_R<1>, gridR, dim3(256), 0, st, nch, seg_len, mode, R, Phi, F_state, V_work);
-    else hipLaunchKernelGGL(k_lincombine<1>, dim3(B * nseg, R), dim3(256), 0, st, nch, seg_len, mode, R, Phi,
-                            (const double *)nullptr, F_state, V_work);
-    hipLaunchKernelGGL(k_lincombine<0>, dim3(B, R), dim3(256), 0, st, nseg, nseg, mode, R, Psi,
-                       (const double *)nullptr, V_work, (double *)nullptr);
-    if (many) hipLaunchKernelGGL(k_lincombine_R<2>, gridR, dim3(256), 0, st, nch, seg_len, mode, R, Phi, F_state, V_work);
-    else hipLaunchKernelGGL(k_lincombine<2>, dim3(B * nseg, R), dim3(256), 0, st, nch, seg_len, mode, R, Phi,
-                            (const double *)nullptr, F_state, V_work);
-    return check_launch("gf_chunk_linear_combine_seg");
-}
-
-int gf_dense_solve_logdet(int batch, int n, int nrhs, const double *A, double *B, double *logdet_out, void *stream) {
-    if (batch < 1 || n < 1 || nrhs < 1) return gf_internal_error(-1, "gf_dense_solve: empty problem (n=%d, nrhs=%d)", n, nrhs);
-    if (n > 192) return gf_internal_error(-1, "gf_dense_solve: n=%d unsupported (max %d)", n, 192);
-    if (!A || !B) return gf_internal_error(-1, "gf_dense_solve: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    // few systems: 16 right-hand sides per workgroup (more, shorter-stepping workgroups); else 64
-    const int slices4 = (nrhs + DS_WAVES * 4 - 1) / (DS_WAVES * 4);
-    const bool narrow = (long long)batch * slices4 <= 64;
-    const int per = DS_WAVES * (narrow ? 1 : 4);
-    const dim3 grid(batch, (nrhs + per - 1) / per);
-#define GF_DS(RSv, NAv) do { if (narrow) hipLaunchKernelGGL((k_dense_solve<RSv, NAv, 1>), grid, dim3(64 * DS_WAVES), 0, st, n, nrhs, A, B, logdet_out); \
-                             else hipLaunchKernelGGL((k_dense_solve<RSv, NAv, 4>), grid, dim3(64 * DS_WAVES), 0, st, n, nrhs, A, B, logdet_out); } while (0)
-    if (n <= 64) GF_DS(1, 4);
-    else if (n <= 96) GF_DS(2, 6);
-    else if (n <= 128) GF_DS(2, 8);
-    else if (n <= 176) GF_DS(3, 11);
-    else GF_DS(3, 12);
-#undef GF_DS
-    return check_launch("gf_dense_solve");
-}
-
-int gf_dense_solve(int batch, int n, int nrhs, const double *A, double *B, void *stream) {
-    return gf_dense_solve_logdet(batch, n, nrhs, A, B, nullptr, stream);
 }
 
 int64_t gf_reduce_work(int64_t N) { return RED_NACC * (int64_t)red_groups(N); }
@@ -6778,200 +3985,6 @@ int gf_loglike_finish(int B, int64_t N, const double *acc, const int32_t *info,
     if (!acc || (!out && !logdet)) return gf_internal_error(-1, "gf_loglike_finish: null pointer");
     hipLaunchKernelGGL(k_finish, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, N, acc, info, out, logdet);
     return check_launch("gf_loglike_finish");
-}
-
-// one-right-hand-side sweeps: `grid` single-wave workgroups (problems x chunks)
-static void launch_solve_vec(const SolveArgs &A, int grid, hipStream_t st) {
-    const int mode = A.mode;
-#define GF_SV(CT, M, S) hipLaunchKernelGGL((k_solve_vec<CT, M, S>), dim3(grid), dim3(64), 0, st, A)
-#define GF_SV_MODE(CT) do { const bool sd = A.scale != nullptr; \
-        if (mode == GF_SOLVE_LOWER) { if (sd) GF_SV(CT, GF_SOLVE_LOWER, true); else GF_SV(CT, GF_SOLVE_LOWER, false); } \
-        else if (mode == GF_SOLVE_UPPER) { if (sd) GF_SV(CT, GF_SOLVE_UPPER, true); else GF_SV(CT, GF_SOLVE_UPPER, false); } \
-        else { if (sd) GF_SV(CT, GF_MATMUL_LOWER, true); else GF_SV(CT, GF_MATMUL_LOWER, false); } } while (0)
-    if (A.ld <= 64)       GF_SV_MODE(1);
-    else if (A.ld <= 128) GF_SV_MODE(2);
-    else if (A.ld <= 192) GF_SV_MODE(3);
-    else                  GF_SV_MODE(4);
-#undef GF_SV_MODE
-#undef GF_SV
-}
-
-// several right-hand sides: one workgroup per (tile of 64 right-hand sides, problem x chunk)
-static void launch_solve_rhs(const SolveArgs &A, int slots, hipStream_t st) {
-    const int ld = A.ld;
-    const dim3 grid((A.R + 63) / 64, slots);
-    if (ld <= 16)       hipLaunchKernelGGL((k_solve_rhs<16, 1>), grid, dim3(64), 0, st, A);
-    else if (ld <= 32)  hipLaunchKernelGGL((k_solve_rhs<32, 1>), grid, dim3(64), 0, st, A);
-    else if (ld <= 48)  hipLaunchKernelGGL((k_solve_rhs<48, 1>), grid, dim3(64), 0, st, A);
-    else if (ld <= 64)  hipLaunchKernelGGL((k_solve_rhs<64, 1>), grid, dim3(64), 0, st, A);
-    else if (ld <= 96)  hipLaunchKernelGGL((k_solve_rhs<48, 2>), grid, dim3(128), 0, st, A);
-    else if (ld <= 128) hipLaunchKernelGGL((k_solve_rhs<64, 2>), grid, dim3(128), 0, st, A);
-    else if (ld <= 192) hipLaunchKernelGGL((k_solve_rhs<48, 4>), grid, dim3(256), 0, st, A);
-    else                hipLaunchKernelGGL((k_solve_rhs<64, 4>), grid, dim3(256), 0, st, A);
-}
-
-// Chunk-parallel form of the one-right-hand-side sweeps of gf_solve (any width; what the wide stored
-// factor uses): local pass (F_state zeroed by the caller, store = 0) -> combine of the chunk states on the
-// caller's side (GF_MATMUL_LOWER: diagonal decays, gf_chunk_diag_scan; the solves: the chunks' closed-loop
-// transitions) -> final pass from the true start states (store = 1).  F_state: [B * nch][ld].
-int gf_solve_chunk(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int ld,
-                   const double *U, const double *Wm, const double *P, const double *scale,
-                   const double *Y, double *Z, double *F_state, int store, void *stream) {
-    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_solve_chunk: bad mode %d", mode);
-    if (B < 1 || N < 1) return gf_internal_error(-1, "gf_solve_chunk: empty problem (N=%lld)", (long long)N);
-    if (check_width_ld("gf_solve_chunk", W, ld)) return -1;
-    if (check_chunking("gf_solve_chunk", N, chunk_len, nch, 1)) return -1;
-    if (!U || !Wm || !P || !Y || !Z || !F_state) return gf_internal_error(-1, "gf_solve_chunk: null pointer");
-    if ((int64_t)B * nch > 0x7fffffffLL) return gf_internal_error(-1, "gf_solve_chunk: problem too large");
-    SolveArgs A;
-    A.N = N; A.W = W; A.ld = ld; A.R = 1; A.mode = mode;
-    A.U = U; A.Wm = Wm; A.P = P; A.scale = scale; A.Y = Y; A.Z = Z;
-    A.chunk_len = chunk_len; A.nch = nch; A.store = store; A.F_state = F_state;
-    launch_solve_vec(A, B * nch, (hipStream_t)stream);
-    return check_launch("gf_solve_chunk");
-}
-
-// gf_solve_chunk with R right-hand sides (k_solve_rhs in chunk mode): Y, Z [B][N][R]; F_state
-// [B * nch][ld][R].  The combine between the two passes is the caller's (W x W chunk transitions applied to
-// W x R states: batched GEMMs).
-int gf_solve_chunk_rhs(int mode, int B, int64_t N, int64_t chunk_len, int nch, int W, int ld, int R,
-                       const double *U, const double *Wm, const double *P, const double *scale,
-                       const double *Y, double *Z, double *F_state, int store, void *stream) {
-    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_solve_chunk_rhs: bad mode %d", mode);
-    if (B < 1 || N < 1 || R < 1) return gf_internal_error(-1, "gf_solve_chunk_rhs: empty problem (N=%lld, R=%d)", (long long)N, R);
-    if (check_width_ld("gf_solve_chunk_rhs", W, ld)) return -1;
-    if (check_chunking("gf_solve_chunk_rhs", N, chunk_len, nch, 1)) return -1;
-    if (!U || !Wm || !P || !Y || !Z || !F_state) return gf_internal_error(-1, "gf_solve_chunk_rhs: null pointer");
-    if ((int64_t)B * nch > 65535) return gf_internal_error(-1, "gf_solve_chunk_rhs: too many chunks (B * nch = %lld > 65535)", (long long)B * nch);
-    SolveArgs A;
-    A.N = N; A.W = W; A.ld = ld; A.R = R; A.mode = mode;
-    A.U = U; A.Wm = Wm; A.P = P; A.scale = scale; A.Y = Y; A.Z = Z;
-    A.chunk_len = chunk_len; A.nch = nch; A.store = store; A.F_state = F_state;
-    launch_solve_rhs(A, B * nch, (hipStream_t)stream);
-    return check_launch("gf_solve_chunk_rhs");
-}
-
-// Scan of chunk states with DIAGONAL transitions: F_state slot c [rows][R] <- true start state of chunk c
-// from the local end states, F_{c+1} = loc_c + D_c o F_c (D [B * nch][rows]); gf_chunk_linear_combine's
-// GF_MATMUL_LOWER branch for any number of state rows.
-int gf_chunk_diag_scan(int B, int nch, int rows, int R, const double *D, double *F_state, void *stream) {
-    if (B < 1 || nch < 1 || rows < 1 || R < 1 || R > 64)
-        return gf_internal_error(-1, "gf_chunk_diag_scan: bad shape (rows=%d, R=%d)", rows, R);
-    if (!D || !F_state) return gf_internal_error(-1, "gf_chunk_diag_scan: null pointer");
-    hipLaunchKernelGGL(k_lincombine_mm, dim3(B, rows, (R + 15) / 16), dim3(64 * LCM_WAVES), 0, (hipStream_t)stream,
-                       nch, R, rows, D, F_state);
-    return check_launch("gf_chunk_diag_scan");
-}
-
-int gf_solve(int mode, int B, int64_t N, int W, int ld, int R,
-             const double *U, const double *Wm, const double *P, const double *scale,
-             const double *Y, double *Z, void *stream) {
-    if (mode < 0 || mode > 2) return gf_internal_error(-1, "gf_solve: bad mode %d", mode);
-    if (B < 1 || N < 1 || R < 1) return gf_internal_error(-1, "gf_solve: empty problem (N=%lld, R=%d)", (long long)N, R);
-    if (check_width_ld("gf_solve", W, ld)) return -1;
-    if (!U || !Wm || !P || !Y || !Z) return gf_internal_error(-1, "gf_solve: null pointer");
-    if (mode == GF_MATMUL_LOWER && Y == Z) return gf_internal_error(-1, "gf_solve: GF_MATMUL_LOWER cannot run in place");
-    SolveArgs A;
-    A.N = N; A.W = W; A.ld = ld; A.R = R; A.mode = mode;
-    A.U = U; A.Wm = Wm; A.P = P; A.scale = scale; A.Y = Y; A.Z = Z;
-    A.chunk_len = N; A.nch = 1; A.store = 1; A.F_state = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (R == 1) {
-        launch_solve_vec(A, B, st);
-    } else {
-        launch_solve_rhs(A, B, st);
-    }
-    return check_launch("gf_solve");
-}
-
-// K(t_n, t*_r) for n < N, r < R into out [B][N][R] (row-major; R <= 4096 query times per call).
-int gf_cross_covariance(int B, int64_t N, int R, int Jr, int Jc,
-                        const double *ar, const double *cr, const double *ac,
-                        const double *bc, const double *cc, const double *dc,
-                        const double *t, int64_t t_bs, const double *ts, int64_t ts_bs,
-                        double *out, void *stream) {
-    if (B < 1 || N < 1 || R < 1 || R > 4096) return gf_internal_error(-1, "gf_cross_covariance: bad shape (N=%lld, R=%d)", (long long)N, R);
-    if (Jr < 0 || Jc < 0 || Jr + Jc < 1 || Jr + 2 * Jc > GF_MAX_WIDTH) return gf_internal_error(-1, "gf_cross_covariance: bad term counts");
-    if (!t || !ts || !out || (Jr && (!ar || !cr)) || (Jc && (!ac || !bc || !cc || !dc)))
-        return gf_internal_error(-1, "gf_cross_covariance: null pointer");
-    // queries per pass (accumulators per lane) so that the table of (term, query) factors fits 48 KB of LDS up to
-    // J = 92 and, with the kernel's 88 static bytes, the 64 KB a launch may ask for without the large-LDS attribute
-    // beyond: 8 (36 J + 16) bytes at RT = 16 pass it from J = 227 on (real-term kernels up to J = 256 are within
-    // GF_MAX_WIDTH), so those take RT = 8 (8 (20 J + 8) bytes: 41 KB at J = 256)
-    const int J = Jr + Jc;
-    const int RT = (J <= 44) ? 64 : (J <= 92) ? 32 : (J <= 226) ? 16 : 8;
-    const size_t lds = sizeof(double) * ((size_t)4 * J + (size_t)2 * RT * J + RT);
-    const int64_t blocks = (N + 255) / 256;
-    if (blocks > 0x7fffffffLL) return gf_internal_error(-1, "gf_cross_covariance: problem too large");
-    const dim3 grid((unsigned)blocks, B);
-    hipStream_t st = (hipStream_t)stream;
-#define GF_CX(RTv) hipLaunchKernelGGL((k_cross<RTv>), grid, dim3(256), lds, st, N, R, Jr, Jc, ar, cr, ac, bc, cc, dc, t, t_bs, ts, ts_bs, out)
-    if (RT == 64) GF_CX(64); else if (RT == 32) GF_CX(32); else if (RT == 16) GF_CX(16); else GF_CX(8);
-#undef GF_CX
-    return check_launch("gf_cross_covariance");
-}
-
-// chunking of the conditional-mean sweeps: ~2048 waves over (problem, direction, chunk), chunks of
-// at least 256 rows; one chunk = the sequential k_gmm
-static void gmm_chunking(int B, int64_t N, int *nch, int64_t *chunk_len) {
-    int64_t n = N / 256;
-    const int64_t cap = (1024 / B) > 1 ? (1024 / B) : 1;
-    if (n > cap) n = cap;
-    if (n < 1) n = 1;
-    int64_t len = (N + n - 1) / n;
-    *nch = (int)((N + len - 1) / len);
-    *chunk_len = len;
-}
-
-// doubles of `work` that gf_general_matmul needs
-int64_t gf_general_matmul_work(int B, int64_t M, int64_t N, int W) {
-    int nch;
-    int64_t chunk_len;
-    if (B < 1 || N < 1 || M < 1 || W < 1) return 0;
-    gmm_chunking(B, N, &nch, &chunk_len);
-    const int CT = (W <= 64) ? 1 : (W <= 128) ? 2 : 4;
-    return (int64_t)B * 2 * M + (nch > 1 ? 3 * (int64_t)B * 2 * nch * CT * 64 : 0);
-}
-
-int gf_general_matmul(int B, int64_t M, int64_t N, int W, int ld,
-                      const double *c,
-                      const double *t1, int64_t t1_bs, const double *U1, const double *V1,
-                      const double *t2, int64_t t2_bs, const double *U2, const double *V2,
-                      const double *P2, const double *alpha, const int64_t *qidx,
-                      double *work, double *mu, void *stream) {
-    if (B < 1 || N < 1 || M < 1) return gf_internal_error(-1, "gf_general_matmul: empty problem (M=%lld, N=%lld)", (long long)M, (long long)N);
-    if (check_width_ld("gf_general_matmul", W, ld)) return -1;
-    if (!c || !t1 || !U1 || !V1 || !t2 || !U2 || !V2 || !P2 || !alpha || !qidx || !work || !mu)
-        return gf_internal_error(-1, "gf_general_matmul: null pointer");
-    GmmArgs A;
-    A.M = M; A.N = N; A.W = W; A.ld = ld; A.c = c;
-    A.t1 = t1; A.t1_bs = t1_bs; A.U1 = U1; A.V1 = V1;
-    A.t2 = t2; A.t2_bs = t2_bs; A.U2 = U2; A.V2 = V2; A.P2 = P2; A.alpha = alpha;
-    A.qidx = qidx; A.work = work;
-    hipStream_t st = (hipStream_t)stream;
-    const int CT = (W <= 64) ? 1 : (W <= 128) ? 2 : 4;
-    int nch;
-    int64_t chunk_len;
-    gmm_chunking(B, N, &nch, &chunk_len);
-    dispatch_among<1, 2, 4>(CT, [&](auto ct) {
-        constexpr int CTv = decltype(ct)::value;
-        if (nch == 1) {
-            hipLaunchKernelGGL(k_gmm<CTv>, dim3(B, 2), dim3(64), 0, st, A);
-            return;
-        }
-        GmmChunk C;                     // long series: chunk-parallel (decayed prefix sums)
-        C.chunk_len = chunk_len; C.nch = nch;
-        const size_t per = (size_t)B * 2 * nch * CT * 64;
-        C.Floc = work + (size_t)B * 2 * M;
-        C.Dloc = C.Floc + per;
-        C.Fstart = C.Dloc + per;
-        const dim3 grid(B, 2, nch);
-        hipLaunchKernelGGL((k_gmm_chunk<CTv, 0>), grid, dim3(64), 0, st, A, C);
-        hipLaunchKernelGGL(k_gmm_scan, dim3(B, 2), dim3(256), 0, st, CT * 64, C);
-        hipLaunchKernelGGL((k_gmm_chunk<CTv, 1>), grid, dim3(64), 0, st, A, C);
-    });
-    hipLaunchKernelGGL(k_add2, dim3((unsigned)((M + 255) / 256), B), dim3(256), 0, st, M, work, mu);
-    return check_launch("gf_general_matmul");
 }
 
 }  // extern "C"

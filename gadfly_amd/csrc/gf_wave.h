@@ -7,6 +7,11 @@
 
 namespace {
 
+// one v_mfma_f64_16x16x4 and its accumulator: four doubles per lane (the steady tail, the chunk combines' block
+// algebra, the linear sweeps, the dense scan)
+#define GF_MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+typedef double d4 __attribute__((ext_vector_type(4)));
+
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_get(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);

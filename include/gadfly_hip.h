@@ -124,7 +124,7 @@ int gf_factor(int B, int64_t N, int64_t n_first, int W, int ld,
 
 /*
  * Log-likelihood fast path for W <= 64 in block-scaled coordinates (see the derivation above
- * k_build2 in gadfly_hip.hip).  Same role as gf_build_matrices + gf_factor on the
+ * k_build2 in gadfly_stored.hip).  Same role as gf_build_matrices + gf_factor on the
  * log-likelihood path (gp.py:202 + gp.py:350); U~, V~ are u o rho and v / rho with
  * rho = exp(-c (t_n - t_ref)); de[n] = t_ref(n) - t_ref(n-1) >= 0 at reset rows (where the
  * accumulated decay exp(-c de) is applied once) and -1 elsewhere.

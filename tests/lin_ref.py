@@ -8,7 +8,7 @@ device by tests/test_lin_ref_host.py.  Never imported by the product.
 Every array carries a leading problem axis B (the row loop is Python: B problems share one trip), and every function
 takes ``dtype``: the same code in float64 is the "plain float64 restatement" whose error sets the device's bar.
 
-* :func:`sweep` -- the three recurrences of the comment above ``struct LinArgs`` (gadfly_hip.hip) over rows n0 .. n1 - 1
+* :func:`sweep` -- the three recurrences of the comment above ``struct LinArgs`` (gadfly_linear.hip) over rows n0 .. n1 - 1
   from a start state: Z, the end state, and the state in front of every chunk boundary it crosses, in the kernels'
   convention (lower / matmul: pending update folded in, the boundary row's own decay NOT yet applied; upper: the
   boundary's decay already applied).

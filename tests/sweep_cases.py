@@ -106,7 +106,7 @@ def carried_input(mode, ref, Y, scaled):
 
 
 # ---- chunk mode of the sweeps ------------------------------------------------------------------------------------
-# Convention of the kernels (SolveArgs and k_solve_vec in gadfly_hip.hip): the state of slot (problem, chunk) holds the
+# Convention of the kernels (SolveArgs and k_solve_vec in gadfly_stored.hip): the state of slot (problem, chunk) holds the
 # pending push of the row before the chunk folded in; ascending sweeps (LOWER, MATMUL) apply the decay of the boundary
 # on ENTRY, at the chunk's first row; the descending sweep (UPPER) applies it on EXIT, across its own first row.
 

@@ -1,5 +1,5 @@
-"""CPU: every argument check of the entry points defined in gadfly_hip.hip and gadfly_series.hip, by exact status and
-exact gf_last_error() text.
+"""CPU: every argument check of the entry points defined in gadfly_hip.hip, gadfly_stored.hip, gadfly_linear.hip and
+gadfly_series.hip, and of gf_dense_solve (gadfly_dense.hip), by exact status and exact gf_last_error() text.
 
 A case whose pointers are all NULL can never reach a launch: every entry point refuses NULL required pointers at
 the latest.  A case that has to pass the NULL check hands over the dummy address `D`; it runs only where there is

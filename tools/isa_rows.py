@@ -9,7 +9,8 @@
                                                    # block and per row; k_steady_finish's full block by phase
                                                    # (z = u + Q s, the state update, the join) with its dependent chains
     python tools/isa_rows.py --asm out.s --rank1   # k_steady_rank1: every block of its row loop
-    python tools/isa_rows.py --asm out.s --compare parent.s    # which kernels' instructions differ between two listings
+    python tools/isa_rows.py --asm out.s --compare parent.s    # which kernels' instructions or descriptors (.amdhsa_*:
+                                                   # registers, LDS, scratch) differ between two listings
 
 Prints every basic block of the row loop (the innermost range closed by a backward branch around the block with the
 most FP64 FMAs: the sweep's update and mat-vec) with its vector (VALU), LDS, scalar and branch instruction counts.
@@ -220,10 +221,11 @@ def finish_phases(lines, rows, kernel="k_steady_finish"):
               f"{behind} FMAs directly behind the write of their accumulator")
 
 
-def functions(lines, twice=None):
+def functions(lines, twice=None, desc=None):
     """name -> instruction lines of every function of a listing, with the per-function label numbers taken out (a
     function added in front renumbers the labels of all that follow).  `twice`, if given, collects the names that
-    occur more than once (listings of several translation units, concatenated)."""
+    occur more than once (listings of several translation units, concatenated); `desc`, if given, every kernel's
+    descriptor: the .amdhsa_* lines of its .amdhsa_kernel block (register counts, LDS and scratch bytes)."""
     out, name, body = {}, None, []
     for ln in lines:
         if name is None:
@@ -238,22 +240,29 @@ def functions(lines, twice=None):
             s = ln.split(";")[0].strip()
             if s and (not s.startswith(".") or s.startswith(".LBB")):     # instructions and block labels
                 body.append(re.sub(r"\.LBB\d+_", ".LBB_", s))
+            elif desc is not None and s.startswith(".amdhsa_") and not s.startswith(".amdhsa_kernel"):
+                desc.setdefault(name, []).append(" ".join(s.split()))
     return out
 
 
 def compare(lines, other):
-    """Which kernels' instructions differ between two listings (registers included: the operands are compared)."""
-    twice_a, twice_b = [], []
-    a, b = functions(lines, twice_a), functions(other, twice_b)
+    """Which kernels' instructions differ between two listings (registers included: the operands are compared), and
+    which kernels' descriptors (register counts, LDS and scratch bytes: the same instructions can run under others)."""
+    twice_a, twice_b, desc_a, desc_b = [], [], {}, {}
+    a, b = functions(lines, twice_a, desc_a), functions(other, twice_b, desc_b)
     changed = sorted(k for k in a.keys() & b.keys() if a[k] != b[k])
+    desc_changed = sorted(k for k in a.keys() & b.keys() if desc_a.get(k) != desc_b.get(k))
     print(f"{len(a)} functions in this listing, {len(b)} in the other; {len(a.keys() & b.keys())} in both, "
-          f"{len(changed)} of them differ")
+          f"{len(changed)} of them differ; {len(desc_a)} kernel descriptors here, {len(desc_b)} in the other, "
+          f"{len(desc_changed)} differ")
     for k in sorted(twice_a):
         print(f"  twice in this listing: {k}")
     for k in sorted(twice_b):
         print(f"  twice in the other: {k}")
     for k in changed:
         print(f"  differs: {k}")
+    for k in desc_changed:
+        print(f"  descriptor differs: {k}")
     for k in sorted(a.keys() - b.keys()):
         print(f"  only here: {k} ({len(a[k])} lines)")
     for k in sorted(b.keys() - a.keys()):
