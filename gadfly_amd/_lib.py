@@ -33,6 +33,7 @@ GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
 GF_SWEEP_AUTO, GF_SWEEP_COLUMN, GF_SWEEP_TILED = 0, 1, 2
 GF_SWEEP_ZERO_START = 0x100
 GF_SWEEP_LONG_SPAN = 0x200
+GF_SWEEP_AXIS_PROVEN = 0x400    # the finishing launches only: the caller has proved the tail's spacing tests
 GF_MAX_WIDTH = 256
 GF_GRAD_MAX_WIDTH = 63          # gf_loglike_grad: one wave per problem
 GF_GRAD_WORKSPACE_BYTES = 16 << 30   # default cap on gf_loglike_grad's workspace per call (batches run in groups)

@@ -886,7 +886,9 @@ tile_sums:
 // last row) touch no row before them; the s loop is bounded and the stores are masked.  (k_steady_finish: behind its
 // group's full blocks, with its own column of the group's U.)
 // Every spacing t_r - t_{r-1} of a tail row r is tested as RowGen tests it (a gap: > gthr; off the frozen cadence:
-// >= jthr): a hit raises ST_VIOL and the rows of that evaluation mean nothing (finite).
+// >= jthr): a hit raises ST_VIOL and the rows of that evaluation mean nothing (finite).  The finishing launches skip
+// the test, its loads of t and the flag where the caller has proved it for every tail row (PROVEN,
+// GF_SWEEP_AXIS_PROVEN: the engine's axis scan): the other bits of the launch do not depend on it.
 // ------------------------------------------------------------------------------------
 constexpr int STT_STAGE = 8;        // terms per staging pass of the p coefficients
 constexpr int FG = 6;               // terms per group of s broadcasts in the folded block's z phase
@@ -948,7 +950,7 @@ __device__ __forceinline__ cdd cdd_mul(const cdd a, const cdd b) {
 constexpr int CH_P = 64 * 64;       // workspace of a problem: P[64][64] over (s_r[0..31], s_i[0..31]), then the slots
 constexpr int CH_SLOT = 72;         // a chunk's slot: [0, 64) its end state, [64] its sum of z^2
 
-template <int ROWS, bool STORE, int CHUNK = 0>
+template <int ROWS, bool STORE, int CHUNK = 0, bool PROVEN = false>
 __device__ __forceinline__ void
 steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const double gap,
                  const double *__restrict__ ac_, const double *__restrict__ bc_,
@@ -959,6 +961,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
                  const int64_t sw_lo, const int64_t sw_hi,
                  const int64_t chunk_rows = 0, double *__restrict__ ws_ = nullptr, const int64_t ws_ld = 0) {
     static_assert(CHUNK == 0 || !STORE, "the chunked launch stores no row");
+    static_assert(!PROVEN || (!STORE && CHUNK != 3), "GF_SWEEP_AXIS_PROVEN is the finishing launches' (M's waves test nothing)");
     constexpr int JT = ROWS / 2;                    // term slots (Jc <= JT <= 32; slots from Jc on are zero)
     // the finishing instance's form of a block: the state update on both half-waves (lane 32 h + k: term k, rows 32 h ..
     // 32 h + 31 of a block), and H off the chain from one block's state to the next, z = H (y + C s) = H y + Q s with
@@ -1157,7 +1160,8 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     const int64_t last = N - 1;
     auto row_of = [&](const int64_t cb) { const int64_t i = cb + lane; return i < last ? i : last; };
     bool viol = false;
-    double t_nx = tg[row_of(r_lo)], tp_nx = tg[row_of(r_lo) - 1];
+    double t_nx = 0.0, tp_nx = 0.0;
+    if constexpr (!PROVEN) { t_nx = tg[row_of(r_lo)]; tp_nx = tg[row_of(r_lo) - 1]; }
     // the pieces every form of a block shares: term k of p (or of Q s) against the broadcast (s_r, s_i), even terms to
     // x0 and odd ones to x1; the state over two rows z_j, z_j+1, and over one
     auto add_term = [&](const int k, const double2 sv, double &x0, double &x1) {
@@ -1318,16 +1322,17 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     while (cb < r_hi) {
     if constexpr (CHUNK != 3) group_phase(cb);
     const double *ub = s_u + lane;                  // this lane's row of the block's u
-    const int64_t ge = (r_hi - cb > 16 * 64) ? cb + 16 * 64 : r_hi;
-    for (; cb + 64 <= ge; cb += 64, ub += SU) {
+    // the group's full blocks, counted in 32 bits (cb moves behind them)
+    const int nfull = (r_hi - cb >= 16 * 64) ? 16 : (int)((r_hi - cb) >> 6);
+    for (int c = 0; c < nfull; ++c, ub += SU) {
         if constexpr (CHUNK == 3) {                 // block j of this wave: unit state j (s_r of term j, then s_i)
-            const int j = (int)((cb - r_lo) >> 6);
+            const int j = (int)((cb - r_lo) >> 6) + c;
             sr = (j < Jc && lane == j) ? 1.0 : 0.0;
             si = (j >= Jc && lane == j - Jc) ? 1.0 : 0.0;
-        } else {
-        const double tv = t_nx, tp = tp_nx;         // t of the rows cb + lane
+        } else if constexpr (!PROVEN) {
+        const double tv = t_nx, tp = tp_nx;         // t of the rows cb + 64 c + lane
         {
-            const int64_t i = row_of(cb + 64);
+            const int64_t i = row_of(cb + 64 * (int64_t)(c + 1));
             t_nx = tg[i]; tp_nx = tg[i - 1];
         }
         const double dt = tv - tp;
@@ -1394,16 +1399,19 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         join(l32r, l32i);
         if constexpr (CHUNK == 3) {
             if (lane < 32) {                        // column j of M
-                const int j = (int)((cb - r_lo) >> 6), col = j < Jc ? j : 32 + j - Jc;
+                const int j = (int)((cb - r_lo) >> 6) + c, col = j < Jc ? j : 32 + j - Jc;
                 wsp[64 * lane + col] = sr;
                 wsp[64 * (32 + lane) + col] = si;
             }
         }
     }
-    if (cb < ge) {                                  // a partial last block (ge = N): lim rows
+    cb += 64 * (int64_t)nfull;
+    if (nfull < 16 && cb < r_hi) {                  // a partial last block (of the series, or of M's 2 Jc): lim rows
         const int lim = (int)(r_hi - cb);
-        const double dt = t_nx - tp_nx;
-        viol |= (lane < lim) && ((dt > gthr) || !(fabs(dt - delta) < jthr));
+        if constexpr (!PROVEN) {                    // (PROVEN: the caller's proof covers these rows too; t is not read)
+            const double dt = t_nx - tp_nx;
+            viol |= (lane < lim) && ((dt > gthr) || !(fabs(dt - delta) < jthr));
+        }
         wave_lds_fence();
         if (lane < 32) { s_s[2 * lane] = sr; s_s[2 * lane + 1] = si; }
         wave_lds_fence();
@@ -1446,7 +1454,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
     }
     if constexpr (CHUNK != 0) {
         if constexpr (CHUNK == 3) return;           // (its rows were no rows of the series)
-        if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
+        if constexpr (!PROVEN) { if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0; }
         double *__restrict__ slot = wsp + CH_P + ch * CH_SLOT;
         if (ch == nch - 1) {
             if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
@@ -1461,7 +1469,7 @@ steady_tail_rows(const int64_t N, const int64_t n_first, const int Jc, const dou
         return;
     }
     if (lane < 32) { hdr[ST_SR + lane] = sr; hdr[ST_SI + lane] = si; }
-    if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0;
+    if constexpr (!PROVEN) { if (__ballot(viol) != 0ull && lane == 0) hdr[ST_VIOL] = 1.0; }
     if constexpr (!STORE) {
         // d = d_inf on every tail row: sum log d = rows * log d_inf, sum z^2 / d = (sum z^2) / d_inf
         const double q = wave_sum(zsq);             // fixed order: the same bits for the same launch shape
@@ -1503,7 +1511,9 @@ k_steady_tail(const int64_t N, const int64_t n_first, const int Jc, const double
 //     of the tile that holds the switch, and the event stands behind that sweep: on a later tile the wave of a switched
 //     problem finds steady_rows_stored == 0 at its exit and leaves acc[b] alone, as k_reduce2<true> does;
 //   - the problems that have not switched are not this launch's: it leaves at the window test above.
-template <int ROWS>
+// PROVEN (GF_SWEEP_AXIS_PROVEN): the caller has proved both spacing tests for every tail row; t is not read, nothing
+// is tested and ST_VIOL is not written.
+template <int ROWS, bool PROVEN>
 __global__ void __launch_bounds__(64, 2)
 k_steady_finish(const int64_t N, const int Jc, const double gap,
                 const double *__restrict__ ac_, const double *__restrict__ bc_,
@@ -1511,14 +1521,14 @@ k_steady_finish(const int64_t N, const int Jc, const double gap,
                 const double *__restrict__ t_, const int64_t t_bs, const double *__restrict__ y_, const int64_t y_bs,
                 const int32_t *__restrict__ info, double *__restrict__ steady_, double *__restrict__ acc_,
                 const int64_t sw_lo, const int64_t sw_hi) {
-    steady_tail_rows<ROWS, false>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr, info,
-                                  steady_, acc_, sw_lo, sw_hi);
+    steady_tail_rows<ROWS, false, 0, PROVEN>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr,
+                                             info, steady_, acc_, sw_lo, sw_hi);
 }
 
 // The chunked finishing launch: the tail of a problem of the window in chunks of chunk_rows rows, one wave per chunk,
 // grid B x (the largest chunk count of a series of N rows; B x 1 for PASS = 3, the waves of M).  PASS = 3 and 1, then
 // k_steady_chunk_power, then PASS = 2, then k_steady_chunk_sum, on one stream (steady_tail_rows has the scheme).
-template <int ROWS, int PASS>
+template <int ROWS, int PASS, bool PROVEN = false>
 __global__ void __launch_bounds__(64, 2)
 k_steady_chunk(const int64_t N, const int Jc, const double gap,
                const double *__restrict__ ac_, const double *__restrict__ bc_,
@@ -1527,8 +1537,8 @@ k_steady_chunk(const int64_t N, const int Jc, const double gap,
                const int32_t *__restrict__ info, double *__restrict__ steady_,
                const int64_t sw_lo, const int64_t sw_hi, const int64_t chunk_rows, double *__restrict__ ws_,
                const int64_t ws_ld) {
-    steady_tail_rows<ROWS, false, PASS>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr, nullptr,
-                                        info, steady_, nullptr, sw_lo, sw_hi, chunk_rows, ws_, ws_ld);
+    steady_tail_rows<ROWS, false, PASS, PROVEN>(N, 0, Jc, gap, ac_, bc_, cc_, dc_, cmax_, t_, t_bs, y_, y_bs, nullptr,
+                                                nullptr, info, steady_, nullptr, sw_lo, sw_hi, chunk_rows, ws_, ws_ld);
 }
 
 // the window's problems with at least `least` chunks: first tail row, 0 for every other problem
@@ -3702,10 +3712,13 @@ static int steady_finish_launch(const char *who, int B, int64_t N, int Jr, int J
         return gf_internal_error(-1, "%s: null pointer", who);
     if (check_window(who, sw_lo, sw_hi)) return -1;
     if (sw_lo == sw_hi) return 0;       // an empty window: no launch
-    const double gap = sweep_gap(block, variant);   // the sweep's
+    const double gap = sweep_gap(block, variant & ~GF_SWEEP_AXIS_PROVEN);   // the sweep's
+    const bool proven = (variant & GF_SWEEP_AXIS_PROVEN) != 0;
     if (!dispatch_rows((2 * Jc + 3) / 4 * 4, [&](auto r) {
-            hipLaunchKernelGGL((k_steady_finish<decltype(r)::value>), dim3(B), dim3(64), 0, (hipStream_t)stream, N, Jc, gap,
-                               ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc, sw_lo, sw_hi);
+            constexpr int R = decltype(r)::value;
+            hipLaunchKernelGGL((proven ? k_steady_finish<R, true> : k_steady_finish<R, false>), dim3(B), dim3(64), 0,
+                               (hipStream_t)stream, N, Jc, gap, ac, bc, cc, dc, cmax, t, t_bs, y, y_bs, info, steady, acc,
+                               sw_lo, sw_hi);
         }))
         return gf_internal_error(-1, "%s: internal dispatch error", who);
     return check_launch(who);
@@ -3747,7 +3760,8 @@ int gf_steady_finish_chunked(int B, int64_t N, int Jr, int Jc, int block, int va
     if (chunk_blocks < 16 || (chunk_blocks & (chunk_blocks - 1)))
         return gf_internal_error(-1, "%s: chunk_blocks=%d must be a power of two >= 16 (chunks start on the groups' grid)", who, chunk_blocks);
     if (sw_lo == sw_hi) return 0;       // an empty window: no launch
-    const double gap = sweep_gap(block, variant);   // the sweep's
+    const double gap = sweep_gap(block, variant & ~GF_SWEEP_AXIS_PROVEN);   // the sweep's
+    const bool proven = (variant & GF_SWEEP_AXIS_PROVEN) != 0;
     const int64_t chunk_rows = 64 * (int64_t)chunk_blocks, ws_ld = gf_steady_chunk_size(N, chunk_blocks);
     const int64_t nmax64 = (N + chunk_rows - 1) / chunk_rows;
     if (nmax64 > 65535)
@@ -3763,10 +3777,10 @@ int gf_steady_finish_chunked(int B, int64_t N, int Jr, int Jc, int block, int va
                                    steady, sw_lo, sw_hi, chunk_rows, chunk_ws, ws_ld);
             };
             pass(k_steady_chunk<R, 3>, dim3(B));
-            pass(k_steady_chunk<R, 1>, dim3(B, nmax));
+            pass(proven ? k_steady_chunk<R, 1, true> : k_steady_chunk<R, 1, false>, dim3(B, nmax));
             hipLaunchKernelGGL(k_steady_chunk_power, dim3(B), dim3(256), 0, st, N, info, steady, sw_lo, sw_hi, chunk_rows,
                                squarings, chunk_ws, ws_ld);
-            pass(k_steady_chunk<R, 2>, dim3(B, nmax));
+            pass(proven ? k_steady_chunk<R, 2, true> : k_steady_chunk<R, 2, false>, dim3(B, nmax));
         }))
         return gf_internal_error(-1, "%s: internal dispatch error", who);
     hipLaunchKernelGGL(k_steady_chunk_sum, dim3((B + 63) / 64), dim3(64), 0, st, B, N, info, steady, sw_lo, sw_hi,

@@ -998,6 +998,11 @@ class StreamingBatch:
         self.steady_used = False            # the last streamed evaluation went through gf_loglike_steady
         self._steady = None                 # [B][gf_steady_size()] per-problem buffer of that entry point
         self._steady_axis = None            # (arm_from, largest spacing deviation behind it): once per evaluator
+        self._steady_cad_max = None         # the largest final cadence of the axes, from the same scan
+        self._steady_scanned = None         # the scan's own result (_steady_axis may be planted by a caller)
+        # the finishing launches skip their spacing tests where the scan has proved them (GF_SWEEP_AXIS_PROVEN,
+        # _steady_axis_proven).  False: the kernel tests every spacing itself, as before
+        self.steady_axis_proven = True
         # where the steady instance starts (its full rows cost ~6 % more than the plain instance's, so tiles that end
         # before any problem can switch run the plain one): learnt from the switch rows of earlier evaluations
         self._steady_from = 0               # first row whose tile runs the steady instance
@@ -1357,6 +1362,8 @@ class StreamingBatch:
             mid_end, k_m = 0, -1
         windows = steady_windows(split, mid_end)
         used = []                           # this evaluation's side streams, joined in front of gf_loglike_finish
+        # the finishing launches' variant: the sweep's, and the proof of the tail's spacing tests where the scan holds it
+        finish_variant = self._finish_variant(pack, block, variant) if self.steady_used else variant
 
         def side_stream(middle):
             """The early launch's stream, or the middle window's own."""
@@ -1379,10 +1386,7 @@ class StreamingBatch:
         def finish(name, stream, *tail):
             """One finishing launch on `stream`, with an event pair of its own."""
             with _timed(torch, self.time_factor, stream, self.finish_events):
-                head = finish_head(pack, B, N, self.Jr, self.Jc, block, variant, self.t, self.y, self.info,
-                                   self._steady, self.acc)
-                st = getattr(lib, name)(*head, *tail, stream.cuda_stream)
-                _lib.check(st, name)
+                self._finish_launch(name, stream, pack, block, finish_variant, *tail)
 
         for k in range(ntiles):
             n0 = k * T
@@ -1567,12 +1571,14 @@ class StreamingBatch:
                     dg = self.diag
                     arm_t = torch.maximum(arm_t, after_last(lambda a, b: dg[:, a:b] != dg[:, -1:], N))
                 arm = int(arm_t)
+                self._steady_cad_max = cmax                         # (what _steady_axis_proven bounds a spacing with)
                 if cmin <= 0.0 or N - arm < self.STEADY_MIN_ROWS:
                     arm = N
                 elif arm < N - 1:
                     jit = float(torch.stack([spacing_dev(a, min(a + step, N - 1)).max()
                                              for a in range(arm, N - 1, step)]).max())
             self._steady_axis = (arm, jit)
+            self._steady_scanned = self._steady_axis    # (a result planted later carries no proof: _steady_axis_proven)
         return self._steady_axis
 
     def _steady_arm_from(self):
@@ -1591,6 +1597,46 @@ class StreamingBatch:
         if arm >= self.N or not (jit < 1e-6 / wmax):
             return None
         return arm
+
+    def _steady_axis_proven(self, pack, block):
+        """GF_SWEEP_AXIS_PROVEN or 0 for the finishing launches of an evaluation that sweeps with `block`: the bit where
+        the scan proves BOTH tests of the tail for every spacing behind arm_from (the tail's rows lie behind the switch
+        row, which lies behind arm_from + 1024: DESIGN.md 3.10), 0 wherever one of them cannot be shown.
+        With cad the final cadence of an axis, every such spacing dt has |dt - cad| <= jit and dt <= cad_max + jit.
+          - off the cadence, |dt - delta| >= 2e-6 / wmax_b: the frozen cadence delta is the mean of 1024 such spacings,
+            so |delta - cad| <= jit and |dt - delta| <= 2 jit (+ the rounding of the mean and of the differences, a few
+            ulp of the cadence); wmax_b <= pack.wmax.  Shown where 2 jit + 2^-48 (cad_max + jit) < 2e-6 / pack.wmax.
+          - a gap, dt > gap / cmax_b with gap = span / (block - 1): the pack's block is the largest with
+            (block - 1) * 1.5 * max_b cmax_b * dt_med <= span (_make_pack, the only place a block is chosen, with the
+            span the sweep's variant names), so gap / cmax_b >= 1.5 dt_med.  Shown where cad_max + jit < 1.5 dt_med and
+            block > 1 (block = 1: gap = 0, every row a reset).  The host holds no cmax_b: an axis that ends on a
+            cadence of 1.5 medians or more keeps the kernel's own test.
+        Both with a factor 1 + 2^-40 on the left for the roundings of the thresholds."""
+        cad_max = getattr(self, "_steady_cad_max", None)
+        if self._steady_axis is None or self._steady_axis is not getattr(self, "_steady_scanned", None):
+            return 0                        # (no scan, or figures that are not the scan's own)
+        if cad_max is None or block <= 1 or block not in (pack.block, pack.stream_block):
+            return 0
+        jit = float(self._steady_axis[1])
+        wmax, dt_med = float(pack.wmax), float(getattr(self, "_dt_med", 0.0))
+        if not (wmax > 0.0 and dt_med > 0.0 and cad_max > 0.0 and jit >= 0.0):
+            return 0
+        slack = 1.0 + 2.0 ** -40
+        on_cadence = (2.0 * jit + 2.0 ** -48 * (cad_max + jit)) * slack < 2e-6 / wmax
+        no_gap = (cad_max + jit) * slack < 1.5 * dt_med
+        return _lib.GF_SWEEP_AXIS_PROVEN if (on_cadence and no_gap) else 0
+
+    def _finish_variant(self, pack, block, variant):
+        """`variant` of the finishing launches behind a sweep that ran with (block, variant): the sweep's own, and
+        GF_SWEEP_AXIS_PROVEN where the scan proves the tail's spacing tests (steady_axis_proven off: never)."""
+        return variant | (self._steady_axis_proven(pack, block) if self.steady_axis_proven else 0)
+
+    def _finish_launch(self, name, stream, pack, block, variant, *tail):
+        """One finishing launch (gf_steady_finish, gf_steady_finish_window or gf_steady_finish_chunked, `tail` behind
+        the 18 arguments they share) of the whole series on `stream`."""
+        head = finish_head(pack, self.B, self.N, self.Jr, self.Jc, block, variant, self.t, self.y, self.info,
+                           self._steady, self.acc)
+        _lib.check(getattr(self.lib, name)(*head, *tail, stream.cuda_stream), name)
 
     def steady_switch_rows(self):
         """Per problem, the first row the LAST streamed evaluation ran in steady mode (-1: never); synchronises."""

@@ -73,6 +73,13 @@ extern "C" {
  * gf_scaled_span(1) instead of gf_scaled_span(0) in c_max * (t - t_reset) -- fewer reset rows at the same `block`
  * rule, or a longer `block`.  Safe for amplitudes and pivots within 1e+-100. */
 #define GF_SWEEP_LONG_SPAN 0x200
+/* OR-ed into the `variant` of gf_steady_finish, gf_steady_finish_window and gf_steady_finish_chunked (no other entry
+ * point takes it): the CALLER has proved that every spacing t[r] - t[r - 1] of every tail row r (switch row <= r < N)
+ * of every problem of the call passes both of the tail's tests -- not a gap (<= gap / cmax[b], gap = gf_scaled_span /
+ * (block - 1)) and on the frozen cadence (|spacing - steady[b][6]| < 2e-6 / max(c, |d|)).  The launch then reads no
+ * time stamp, tests nothing and never writes steady[b][2]; every other word it writes takes the bits it takes without
+ * the flag.  A caller that promises more than its axis keeps gets finite numbers that mean nothing. */
+#define GF_SWEEP_AXIS_PROVEN 0x400
 
 int gf_version(void);
 const char *gf_last_error(void);
@@ -248,7 +255,8 @@ int gf_loglike_steady(int B, int64_t N, int64_t n_first, int Jr, int Jc, int blo
  *                               acc[b][0] += (N - switch row) log d,  acc[b][1] += (sum z^2) / d,
  *                               acc[b][2]  = min(acc[b][2], d)
  *                           (sums in a fixed order: deterministic for given B, N and switch rows).  Every spacing is
- *                           tested as gf_loglike_steady tests it (steady[b][2]).  Problems with info != 0 or
+ *                           tested as gf_loglike_steady tests it (steady[b][2]), unless `variant` carries
+                           GF_SWEEP_AXIS_PROVEN (above: then t is not read).  Problems with info != 0 or
  *                           without a switch are left alone.  block, variant: the sweep's (they set its gap test);
  *                           ac .. dc, cmax, t, y and their batch strides: the sweep's.
  *   gf_steady_finish_window : gf_steady_finish for the problems whose switch row steady[b][0] lies in [sw_lo, sw_hi)

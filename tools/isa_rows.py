@@ -7,7 +7,8 @@
     python tools/isa_rows.py --steady              # k_factor7<60, false, false, true>: its full row loop, AND
                                                    # k_steady_tail<60>, k_steady_finish<60>: the block loop, per 64-row
                                                    # block and per row; k_steady_finish's full block by phase
-                                                   # (z = u + Q s, the state update, the join) with its dependent chains
+                                                   # (z = u + Q s, the state update, the join) with its dependent chains,
+                                                   # without and with GF_SWEEP_AXIS_PROVEN (k_steady_finish<60, proven>)
     python tools/isa_rows.py --asm out.s --rank1   # k_steady_rank1: every block of its row loop
     python tools/isa_rows.py --asm out.s --compare parent.s    # which kernels' instructions or descriptors (.amdhsa_*:
                                                    # registers, LDS, scratch) differ between two listings
@@ -38,18 +39,20 @@ def compile_asm(out):
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 
 
-def kernel_tag(kernel, rows, rowstore, sample, steady=False):
+def kernel_tag(kernel, rows, rowstore, sample, steady=False, proven=False):
     # mangled: ..._19k_factor7ILi60ELb0ELb0ELb0EEEv...  (template <int ROWS, bool ROWSTORE, bool SAMPLE, bool STEADY>); k_factorw has a
     # second integer (its sweep waves) and k_factor3 / k_factorw no ROWSTORE.  The whole argument list is matched.
     mid = r"Li\d+E" if kernel == "k_factorw" else (f"Lb{int(rowstore)}E" if rowstore is not None else "")
     smp = f"Lb{int(sample)}E" if kernel in ("k_factor3", "k_factor7", "k_factorw") else ""
     if kernel == "k_factor7":
         smp += f"Lb{int(steady)}E"
+    if kernel == "k_steady_finish":             # template <int ROWS, bool PROVEN> (GF_SWEEP_AXIS_PROVEN)
+        smp += f"Lb{int(proven)}E"
     return re.compile(f"{len(kernel)}{kernel}ILi{rows}E{mid}{smp}E")
 
 
-def kernel_body(lines, kernel, rows, rowstore, sample=False, steady=False):
-    tag = kernel_tag(kernel, rows, rowstore, sample, steady)
+def kernel_body(lines, kernel, rows, rowstore, sample=False, steady=False, proven=False):
+    tag = kernel_tag(kernel, rows, rowstore, sample, steady, proven)
     start = None
     for i, ln in enumerate(lines):
         if start is None and re.match(r"^_Z\S+:", ln) and tag.search(ln.split(":")[0]):
@@ -116,15 +119,15 @@ def counts(ins):
     return c
 
 
-def steady_tail(lines, rows, kernel="k_steady_tail"):
+def steady_tail(lines, rows, kernel="k_steady_tail", proven=False):
     """k_steady_tail<rows> / k_steady_finish<rows>: the block loop (the smallest loop around the block with the most FMAs: p and H p) and
     the loops inside it (the s update, two rows per step, unrolled).  Instructions per 64-row block = the block loop's
     own instructions + each inner loop's body times its trips for 64 rows."""
-    bl = blocks(kernel_body(lines, kernel, rows, None))
-    tag = kernel_tag(kernel, rows, None, False)
+    bl = blocks(kernel_body(lines, kernel, rows, None, proven=proven))
+    tag = kernel_tag(kernel, rows, None, False, proven=proven)
     vgpr = next((ln.split(",")[-1].strip() for ln in lines if ".num_vgpr," in ln and tag.search(ln)), "?")
     total = counts([op for b in bl for op in b["ins"]])
-    print(f"{kernel}<{rows}>: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, "
+    print(f"{kernel}<{rows}{', proven' if proven else ''}>: {len(bl)} blocks, {total['valu']} VALU, {total['lds']} LDS, "
           f"{total['scratch']} scratch (spill) in all; {vgpr} VGPRs")
     reg = max(range(len(bl)), key=lambda i: counts(bl[i]["ins"])["fma"])
     i0, i1 = row_loop(bl, reg)
@@ -176,12 +179,12 @@ def _regs(operand):
     return {int(m.group(1))} if m else set()
 
 
-def finish_phases(lines, rows, kernel="k_steady_finish"):
+def finish_phases(lines, rows, kernel="k_steady_finish", proven=False):
     """The full block of the finishing launch (one basic block: the one with the most FMAs) by phase: z = u + Q s up to
     the store of z (ds_write_b64), the state update up to the join (its first v_permlane32_swap), and the rest.  Per
     phase: vector instructions, FP64 FMAs and multiplies, LDS reads, s_waitcnt, the longest chain of dependent FP64
     instructions, and the FMAs issued directly behind an FP64 instruction that writes the accumulator they add to."""
-    body = kernel_body(lines, kernel, rows, None)
+    body = kernel_body(lines, kernel, rows, None, proven=proven)
     cur, best = [], []
     for ln in body + [".LBB_end:"]:
         s = ln.strip()
@@ -195,7 +198,7 @@ def finish_phases(lines, rows, kernel="k_steady_finish"):
             cur.append((parts[0], [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []))
     cut1 = next((i for i, x in enumerate(best) if x[0] == "ds_write_b64"), len(best))
     cut2 = next((i for i, x in enumerate(best) if x[0].startswith("v_permlane32_swap")), len(best))
-    print(f"{kernel}<{rows}>, the full block ({len(best)} instructions, {sum(x[0].startswith('v_') for x in best)} "
+    print(f"{kernel}<{rows}{', proven' if proven else ''}>, the full block ({len(best)} instructions, {sum(x[0].startswith('v_') for x in best)} "
           f"vector) by phase:")
     for name, part in (("z = u + Q s", best[:cut1]), ("state update", best[cut1:cut2]), ("join and loop", best[cut2:])):
         depth, deepest, behind, prev = {}, 0, 0, set()
@@ -366,8 +369,9 @@ def main():
     show(i0, i1, reg)
     if a.steady and not a.all:
         steady_tail(lines, a.rows)
-        steady_tail(lines, a.rows, "k_steady_finish")
-        finish_phases(lines, a.rows)
+        for proven in (False, True):            # without and with GF_SWEEP_AXIS_PROVEN
+            steady_tail(lines, a.rows, "k_steady_finish", proven)
+            finish_phases(lines, a.rows, proven=proven)
     return 0
 
 
