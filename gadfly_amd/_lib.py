@@ -26,7 +26,8 @@ SOURCES = [os.path.join(CSRC, "gadfly_hip.hip"), os.path.join(CSRC, "gadfly_stor
            os.path.join(CSRC, "gadfly_fisher.hip"), os.path.join(CSRC, "gadfly_rhs.hip"),
            os.path.join(CSRC, "gadfly_lsfft.hip"), os.path.join(CSRC, "gadfly_gradtp.hip"),
            os.path.join(CSRC, "gadfly_detrend.hip"), os.path.join(CSRC, "gadfly_linmodel.hip"),
-           os.path.join(CSRC, "gadfly_quadform.hip"), os.path.join(CSRC, "gadfly_gradw.hip")]
+           os.path.join(CSRC, "gadfly_quadform.hip"), os.path.join(CSRC, "gadfly_gradw.hip"),
+           os.path.join(CSRC, "gadfly_solvew.hip")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gadfly_hip.h")
 
 GF_SOLVE_LOWER, GF_SOLVE_UPPER, GF_MATMUL_LOWER = 0, 1, 2
@@ -154,6 +155,11 @@ SIGNATURES = {
     "gf_solve_batch_work": (_i64, [_i64, _int, _i64]),
     "gf_solve_batch": (_int, [_int, _i64, _int, _int] + [_vp] * 7 + [_int, _int] + [_vp] * 6
                        + [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64] + [_vp] * 5 + [_vp]),
+    "gf_solve_wide_max_width": (_int, []),
+    "gf_solve_wide_seg": (_i64, [_i64, _int]),
+    "gf_solve_wide_work": (_i64, [_i64, _int, _i64]),
+    "gf_solve_batch_wide": (_int, [_int, _i64, _int, _int] + [_vp] * 7
+                            + [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64] + [_vp] * 4 + [_vp]),
     "gf_general_matmul_work": (_i64, [_int, _i64, _i64, _int]),
     "gf_general_matmul": (_int, [_int, _i64, _i64, _int, _int, _vp,
                                  _vp, _i64, _vp, _vp,

@@ -572,8 +572,57 @@ class BatchedLogLikelihood:
         """:meth:`leave_one_out_device`, returned as numpy."""
         return tuple(self._to_host(x) for x in self.leave_one_out_device(pack_or_kernels, include_mean=include_mean))
 
+    def _predict_wide(self, pack_or_kernels, kernel, include_mean, return_alpha, t):
+        """:meth:`predict_device` with ``wide=True``: alpha (and mu at the observed times) from
+        ``gf_solve_batch_wide``; a component's share and the means at new times from ``gf_predict_batch_at`` over the
+        kernel's groups of whole terms."""
+        from .predict import check_width, component_pack, predict_at_groups, solve_batch_wide, term_groups
+        eng = self.engine
+        Jr0, Jc0 = eng._struct0
+        check_width(Jr0 + 2 * Jc0, wide=True)
+        ts, nq, as_list, mean = None, None, False, None
+        if t is not None:
+            ts, nq, as_list = self._query_times(t)
+            mean = self._query_mean(include_mean)
+        component = None if kernel is None else component_pack(kernel, self.B, wide=True)
+        if pack_or_kernels is not None:
+            Jr, Jc, real, comp, diag_add = self._host_pack(pack_or_kernels)
+        elif self._pack0 is not None:
+            Jr, Jc, real, comp, diag_add = self._pack0
+        else:                               # (a wide kernel with real terms: the engine holds them rewritten)
+            from .engine import _coeff_pack
+            Jr, Jc, real, comp, diag_add = _coeff_pack(eng._coeffs_list)[:5]
+        sums =t is not None or component is not None
+        res = solve_batch_wide(eng, Jr, Jc, real, comp, diag_add, self.predict_workspace_bytes,
+                               want_alpha=return_alpha or sums, want_mu=not sums)
+        self._record_predict(res)
+        if not sums:
+            mu = res["mu"]
+            self._add_mean(mu, include_mean)
+            mu = self._cut_rows(mu)
+        else:
+            groups = term_groups(*((Jr, Jc, real, comp) if component is None else component))
+            if t is None:                   # the component's share at the observed stamps: t* = t
+                at = predict_at_groups(eng, groups, res["alpha"], eng.t, nobs=self.rows, nq=self.rows)
+                self._predict_at_events = at["events"]
+                mu = at["mu"]
+                self._add_mean(mu, include_mean)
+                mu = self._cut_rows(mu)
+            else:
+                if ts.shape[1] == 0:
+                    mu = self._empty_queries()
+                else:
+                    at = predict_at_groups(eng, groups, res["alpha"], ts, nobs=self.rows, nq=nq)
+                    self._predict_at_events = at["events"]
+                    mu = at["mu"]
+                    if mean is not None:
+                        mu += eng.torch.as_tensor(np.array(mean), dtype=eng.torch.float64, device=eng.device)
+                mu = self._cut_queries(mu, nq, as_list)
+        alpha = self._cut_rows(res["alpha"])
+        return (mu, alpha) if return_alpha else mu
+
     def predict_device(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None,
-                       return_var=False):
+                       return_var=False, wide=False):
         """Conditional means of the B problems at their observed times in one device call: what
         ``GaussianProcess(kernel_b, t, yerr).predict(y)`` gives one kernel at a time -- mu = y - diag alpha with
         alpha = K^-1 (y - mean) -- as a float64 device tensor (B, N); a ragged batch returns a list of B tensors cut
@@ -603,7 +652,20 @@ class BatchedLogLikelihood:
         process (exactly 0 where diag_n = 0), at new times K(0) - K(t*, t) Sigma^-1 K(t, t*) with the kernel in its
         coefficient form at every lag (an exposure-integrated kernel is exact for queries at least its exposure time
         from every stamp).  One ``gf_var_batch`` launch takes the place of ``gf_solve_batch``: the means keep their
-        bits.  With ``kernel=component`` it raises ``NotImplementedError``."""
+        bits.  With ``kernel=component`` it raises ``NotImplementedError``.
+
+        ``wide``: one workgroup per problem, the route for celerite widths beyond 63 -- gadfly's
+        86-term default kernel among them -- up to ``gf_solve_wide_max_width()`` (192); narrow kernels are taken too
+        (same results to rounding, not to the bit).  alpha and the means at the observed times come from
+        ``gf_solve_batch_wide``; the means at new times ``t`` and a component's share (of any width up to the same
+        limit, at the observed stamps or at ``t``) are ``gf_predict_batch_at``'s sums over groups of whole terms of
+        width <= 63, added on the device: exact, K(t*, t) alpha being a sum over terms.  ``return_var`` with ``wide``
+        raises ``NotImplementedError``: variances of wide kernels are not built."""
+        if wide:
+            if return_var:
+                raise NotImplementedError("return_var with wide=True: conditional variances of wide kernels are not "
+                                          "built (gf_var_batch is a one-wave kernel, W <= 63)")
+            return self._predict_wide(pack_or_kernels, kernel, include_mean, return_alpha, t)
         if return_var:
             return self._predict_var(pack_or_kernels, kernel, include_mean, return_alpha, t)
         if t is not None:
@@ -898,10 +960,10 @@ class BatchedLogLikelihood:
                                                             seed=seed, include_mean=include_mean))
 
     def predict(self, pack_or_kernels=None, kernel=None, include_mean=True, return_alpha=False, t=None,
-                return_var=False):
+                return_var=False, wide=False):
         """:meth:`predict_device`, returned as numpy (lists of arrays for a ragged batch or a list of query times)."""
         out = self.predict_device(pack_or_kernels, kernel=kernel, include_mean=include_mean,
-                                  return_alpha=return_alpha, t=t, return_var=return_var)
+                                  return_alpha=return_alpha, t=t, return_var=return_var, wide=wide)
         return tuple(self._to_host(x) for x in out) if (return_alpha or return_var) else self._to_host(out)
 
     def evaluate_device(self, pack=None):
@@ -1047,14 +1109,14 @@ def log_likelihood_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, device=N
 
 
 def predict_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, kernel=None, device=None, t_pred=None,
-                  return_var=False):
+                  return_var=False, wide=False):
     """One-shot form of :meth:`BatchedLogLikelihood.predict`: the conditional means of B problems at their observed
     times as numpy, (B, N) or a list of B arrays for ragged ``t``; ``kernel=`` selects the share of one part of the
     kernel (a list of B components, or one for all).  ``t_pred``: new times to predict at instead, what
     :meth:`BatchedLogLikelihood.predict` takes as ``t=`` (here ``t`` names the observed stamps).  ``return_var``: also
-    the conditional variances, ``(mu, var)``."""
+    the conditional variances, ``(mu, var)``.  ``wide``: the route for kernels wider than W = 63 (as there)."""
     return BatchedLogLikelihood(kernels, t, y, yerr=yerr, diag=diag, mean=mean,
-                                device=device).predict(kernel=kernel, t=t_pred, return_var=return_var)
+                                device=device).predict(kernel=kernel, t=t_pred, return_var=return_var, wide=wide)
 
 
 def sample_conditional_batch(kernels, t, y, yerr=None, diag=None, mean=0.0, t_pred=None, size=None, normals=None,

@@ -7,6 +7,9 @@ backwards, no stored factor); this module stacks the component's coefficients.  
 alpha to new times t* (DESIGN.md 3.11): the two sorted-axis sums of the full kernel or of a component, no workspace.
 ``gf_var_batch`` is ``gf_solve_batch`` with one more backward recurrence: the inverse diagonal h, the
 conditional variances at the observed times and at new ones, the staged queries counted in its workspace.
+``gf_solve_batch_wide`` is ``gf_solve_batch`` without a component for kernels wider than one wave (one
+workgroup per problem); their sums at new times, and a component's share, are ``gf_predict_batch_at``'s over groups of
+whole terms (:func:`term_groups`).
 ``gf_solve_batch_rhs`` and ``gf_predict_batch_at_rhs`` are the first two for R right-hand sides per
 problem through one pass over the rows, column by column the same bits.  The groups
 under the byte cap, the query axes and the launches are :mod:`gadfly_amd.rowcall`'s.
@@ -17,33 +20,45 @@ import torch
 from . import _lib
 from .rowcall import GroupedCall, check_pack_batch, group_plan, query_axes
 
-__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "predict_at", "variance_plan",
+__all__ = ["check_width", "workspace_plan", "component_pack", "solve_batch", "solve_batch_wide", "term_groups",
+           "predict_at", "predict_at_groups", "variance_plan",
            "variance_batch", "rhs_workspace_plan", "solve_batch_rhs", "predict_at_rhs", "DEFAULT_WORKSPACE_BYTES"]
 
 #: default cap on the workspace of one call (the batch is split into groups beneath it)
 DEFAULT_WORKSPACE_BYTES = _lib.GF_SOLVE_WORKSPACE_BYTES
 
 
-def check_width(W, what="this kernel"):
-    """The one-wave solve kernel's width limit: NotImplementedError beyond it."""
+def check_width(W, what="this kernel", wide=False):
+    """The one-wave solve kernel's width limit: NotImplementedError beyond it.  ``wide``: the limit of the route with
+    one workgroup per problem (``gf_solve_wide_max_width()``) instead."""
+    if wide:
+        limit = int(_lib.load().gf_solve_wide_max_width())
+        if W > limit:
+            raise NotImplementedError(
+                f"batched conditional means with wide=True take celerite widths W <= {limit} (one workgroup per "
+                f"problem); {what} has W = {W}")
+        return
     if W > _lib.GF_SOLVE_MAX_WIDTH:
         raise NotImplementedError(
             f"batched conditional means take celerite widths W <= {_lib.GF_SOLVE_MAX_WIDTH} (one wave per problem); "
             f"{what} has W = {W}")
 
 
-def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0):
-    """(doubles per problem, problems per group, number of groups) of a gf_solve_batch call."""
-    check_width(W)
-    return group_plan(_lib.load().gf_solve_batch_work(int(N), int(W), int(seg)), B, cap_bytes,
+def workspace_plan(N, W, B, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0, wide=False):
+    """(doubles per problem, problems per group, number of groups) of a gf_solve_batch call -- ``wide``: of a
+    gf_solve_batch_wide call."""
+    check_width(W, wide=wide)
+    lib = _lib.load()
+    work = lib.gf_solve_wide_work if wide else lib.gf_solve_batch_work
+    return group_plan(work(int(N), int(W), int(seg)), B, cap_bytes,
                       f"no solve workspace for N = {N}, W = {W}, seg = {seg}")
 
 
-def component_pack(kernel, B):
+def component_pack(kernel, B, wide=False):
     """Stacked host coefficients (Jr', Jc', real', comp') of a component for B problems from a list of B kernels, one
     kernel for all problems, or a host pack (``sho_coefficient_pack``, ``engine._coeff_pack``) of B (or one) rows.
     ValueError when the list does not hold B kernels or they do not share one term structure; NotImplementedError
-    when the component is wider than one wave."""
+    when the component is wider than one wave -- ``wide``: than :func:`check_width` allows with ``wide``."""
     from .engine import _coeff_pack
     if isinstance(kernel, tuple) and len(kernel) >= 4 and isinstance(kernel[0], (int, np.integer)):
         Jr, Jc = int(kernel[0]), int(kernel[1])
@@ -61,7 +76,7 @@ def component_pack(kernel, B):
         Jr, Jc, real, comp, _, _ = _coeff_pack([k.get_device_coefficients() for k in kernel])
     if Jr + 2 * Jc < 1:
         raise ValueError("the component has no terms")
-    check_width(Jr + 2 * Jc, "the component")
+    check_width(Jr + 2 * Jc, "the component", wide=wide)
     check_pack_batch(B, Jr, Jc, real, comp, np.zeros(B))
     return Jr, Jc, np.ascontiguousarray(real), np.ascontiguousarray(comp)
 
@@ -93,6 +108,67 @@ def solve_batch(engine, Jr, Jc, real, comp, diag_add, component=None, cap_bytes=
             g.nb, N, Jr, Jc, *g.coef[0], jr2, jc2, *g.coef[1], *g.data, int(seg), *g.work,
             g.at(alpha, N), g.at(mu, N), g.at(mu_comp, N), g.at(ll), g.at(info), g.stream))
         return dict(alpha=alpha, mu=mu, mu_comp=mu_comp, ll=ll, info=info, events=events, **rc.plan)
+
+
+def solve_batch_wide(engine, Jr, Jc, real, comp, diag_add, cap_bytes=DEFAULT_WORKSPACE_BYTES, seg=0, want_alpha=True,
+                     want_mu=True):
+    """:func:`solve_batch` through ``gf_solve_batch_wide``: one workgroup per problem, celerite widths
+    up to ``gf_solve_wide_max_width()``, no component.  The same dict, ``mu_comp`` always None."""
+    W = Jr + 2 * Jc
+    if (Jr, Jc) != engine._struct0:
+        raise ValueError("coefficient pack does not match the batch structure")
+    B, N = engine.B, engine.N
+    check_pack_batch(B, Jr, Jc, real, comp, diag_add)
+    plan = workspace_plan(N, W, B, cap_bytes, seg, wide=True)
+    f64 = dict(dtype=torch.float64, device=engine.device)
+    with torch.cuda.device(engine.device):
+        rc = GroupedCall(engine, "gf_solve_batch_wide", plan, (real, comp, diag_add))
+        ll = torch.empty((B,), **f64)
+        info = torch.zeros((B,), dtype=torch.int32, device=engine.device)
+        alpha = torch.empty((B, N), **f64) if want_alpha else None
+        mu = torch.empty((B, N), **f64) if want_mu else None
+        events = rc.run(lambda g: g.launch(
+            g.nb, N, Jr, Jc, *g.coef[0], *g.data, int(seg), *g.work,
+            g.at(alpha, N), g.at(mu, N), g.at(ll), g.at(info), g.stream))
+        return dict(alpha=alpha, mu=mu, mu_comp=None, ll=ll, info=info, events=events, **rc.plan)
+
+
+def term_groups(Jr, Jc, real, comp, max_width=_lib.GF_SOLVE_MAX_WIDTH):
+    """A stacked coefficient pack (real (2, B, max(Jr, 1)), comp (4, B, max(Jc, 1))) cut into consecutive groups of
+    whole terms of celerite width <= ``max_width`` each, in the original order -- the real terms first, then the
+    complex ones, a complex term's two columns never apart: a list of ``(Jr_g, Jc_g, real_g, comp_g)`` that
+    :func:`predict_at` accepts.  K(t*, t) alpha is a sum over terms, so the groups' results add up to the whole
+    kernel's.  A pack that fits comes back as one group holding the same arrays."""
+    Jr, Jc = int(Jr), int(Jc)
+    if Jr + 2 * Jc <= max_width:
+        return [(Jr, Jc, real, comp)]
+    if max_width < 2:
+        raise ValueError("groups of whole terms need a width of at least 2")
+    real, comp = np.asarray(real, dtype=np.float64), np.asarray(comp, dtype=np.float64)
+    B = real.shape[1]
+    groups, ir, ic = [], 0, 0
+    while ir < Jr or ic < Jc:
+        jr = min(Jr - ir, max_width)
+        jc = min(Jc - ic, (max_width - jr) // 2) if ir + jr == Jr else 0
+        r, c = np.zeros((2, B, max(jr, 1))), np.zeros((4, B, max(jc, 1)))
+        r[:, :, :jr], c[:, :, :jc] = real[:, :, ir:ir + jr], comp[:, :, ic:ic + jc]
+        groups.append((jr, jc, r, c))
+        ir, ic = ir + jr, ic + jc
+    return groups
+
+
+def predict_at_groups(engine, groups, alpha, ts, nobs=None, nq=None):
+    """:func:`predict_at` for a kernel given as :func:`term_groups`: one ``gf_predict_batch_at`` launch per group on
+    the same ``alpha``, the results added on the device in group order, the events concatenated.  Returns
+    dict(``mu``, ``events``) as :func:`predict_at`.  No host synchronisation."""
+    if not groups:
+        raise ValueError("the kernel has no terms")
+    mu, events = None, []
+    for g in groups:
+        at = predict_at(engine, *g, alpha, ts, nobs=nobs, nq=nq)
+        mu = at["mu"] if mu is None else mu.add_(at["mu"])
+        events += at["events"]
+    return dict(mu=mu, events=events)
 
 
 def predict_at(engine, Jr, Jc, real, comp, alpha, ts, nobs=None, nq=None):

@@ -21,6 +21,8 @@
  *                                                      kernel of gadfly/core.py, W = 172)
  *   gf_solve_batch      driver.factor + solve_lower + solve_upper + general_matmul_lower / _upper at t* = t
  *                                                      <- gp.py:370, :232 for B kernels at once
+ *   gf_solve_batch_wide    the same without a component for wide kernels, one workgroup per problem (W up to 192;
+ *                                                      DESIGN.md 3.9.1)
  *   gf_var_batch        the same plus the diagonal of K* - K*^T (K + diag)^-1 K* (celerite2's
  *                       ConditionalDistribution.variance)   <- gp.py:241-306 (predict(..., return_var=True)) for B
  *                                                      kernels at once
@@ -903,6 +905,39 @@ int gf_solve_batch(int B, int64_t N, int Jr, int Jc,
                    const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
                    const double *y, int64_t y_bs, int64_t seg, double *work, int64_t work_bs,
                    double *alpha, double *mu, double *mu_comp, double *ll, int32_t *info, void *stream);
+
+/*
+ * alpha = K^-1 y and the conditional means for wide kernels: gf_solve_batch's mathematics, layouts,
+ * outputs and failure convention without a component, with one WORKGROUP of several waves per problem, for
+ * 1 <= W = Jr + 2 Jc <= gf_solve_wide_max_width() (192: gadfly's 86-term default kernel is W = 172; -3 beyond, the
+ * limit in gf_last_error()).  Narrow widths are accepted, so that the route can be set against gf_solve_batch on one
+ * problem (same results to rounding, not to the bit).  A component's share comes from gf_predict_batch_at on alpha.
+ *   gf_solve_wide_seg(N, W)         default rows per segment (0 for a shape the call refuses)
+ *   gf_solve_wide_work(N, W, seg)   doubles per problem (0 for a shape the call refuses): ceil(N / seg) checkpoints
+ *                                   of (NC + 4) RT doubles, one segment of staged rows at 3 RT each, z and D of every
+ *                                   row; RT = NC = 64, 128, 192 for W <= 64, <= 128, <= 192
+ *   coefficients, diag_add, t, diag, y and their strides as gf_solve_batch (0 = shared, otherwise at least N; diag
+ *     may be NULL)
+ *   seg: rows per segment, 0 = gf_solve_wide_seg(N, W) (values above N mean N).  Every output is bit-identical for
+ *     every seg
+ *   work: work_bs >= gf_solve_wide_work(N, W, seg) doubles per problem; B * work_bs in all.  What it holds on entry
+ *     does not matter
+ *   alpha [B][N]    K^-1 y                                                   (may be NULL)
+ *   mu [B][N]       y - diag alpha; diag = NULL gives y                      (may be NULL)
+ *   ll [B]          log-likelihood, -inf where a pivot is not positive (info = the 1-based failing row); every row of
+ *                   alpha and mu of such a problem is NaN, the other problems are unaffected to the bit
+ * Returns -1 for bad shapes, strides, null pointers or a short work_bs, all checked before any device call.
+ * No atomics: results are bit-identical from run to run and do not depend on the other problems of the call.
+ */
+int gf_solve_wide_max_width(void);
+int64_t gf_solve_wide_seg(int64_t N, int W);
+int64_t gf_solve_wide_work(int64_t N, int W, int64_t seg);
+int gf_solve_batch_wide(int B, int64_t N, int Jr, int Jc,
+                        const double *ar, const double *cr, const double *ac, const double *bc,
+                        const double *cc, const double *dc, const double *diag_add,
+                        const double *t, int64_t t_bs, const double *diag, int64_t diag_bs,
+                        const double *y, int64_t y_bs, int64_t seg, double *work, int64_t work_bs,
+                        double *alpha, double *mu, double *ll, int32_t *info, void *stream);
 
 /*
  * Conditional means of B problems at new times t* (DESIGN.md 3.11): what celerite2's general_matmul_lower +

@@ -112,14 +112,91 @@ def at_legs(names, reps, rng):
         torch.cuda.empty_cache()
 
 
+WIDE_SHAPES = {"w1": (256, 65_000, 86), "w2": (64, 20_000, 40), "w3": (1, 100_000, 86)}
+
+
+def wide_legs(names, reps, nloop, rng, grad_reps=3):
+    """predict_device(wide=True) on a grid that lost 10 % of its cadences, one JSON line per shape:
+    solve_device_ms, the gf_solve_batch_wide launches (HIP events, summed over the groups, median of `reps`);
+    predict_numpy_ms, predict(wide=True) as numpy, wall time of one call; the loop it replaces, GaussianProcess(kernel_b,
+    t, yerr).predict(y) one kernel at a time, construction included, over `nloop` problems and scaled to B; at_device_ms
+    and at_share, the gf_predict_batch_at launches of predict_device(t=the lost cadences, wide=True) and their share of
+    that call's device time; grad_device_ms, value_and_grad(wide=True) on the same batch (median of `grad_reps`)."""
+    for name in names:
+        B, N, J = WIDE_SHAPES[name]
+        kern, S0, w0, Q, delta = walkers(B, J, rng)
+        grid = uniform_times(int(round(N / 0.9)), 60.0)
+        keep = np.zeros(len(grid), dtype=bool)
+        keep[rng.choice(len(grid), size=N, replace=False)] = True
+        t, ts = grid[keep], grid[~keep]
+        y = 100.0 * rng.normal(size=N)
+        ev = gadfly_amd.BatchedLogLikelihood([kern] * B, t, y, yerr=30.0)
+        pack = sho_coefficient_pack(S0, w0, Q, delta)
+
+        def run_predict():
+            ev.predict_device(pack, wide=True)
+            return ev.last_predict_device_ms
+
+        api, dev = median_ms(run_predict, reps)
+        ws, groups, group_size = ev.last_predict_plan
+        rec = dict(shape=name, B=B, N=N, J=J, W=2 * J, solve_device_ms=round(dev, 2), predict_api_ms=round(api, 2),
+                   us_per_row=round(1e3 * dev / (groups * N), 3), workspace_bytes=int(ws), groups=int(groups),
+                   group_size=int(group_size), reps=reps)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mu = ev.predict(pack, wide=True)
+        rec["predict_numpy_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+        rec["finite"] = bool(np.all(np.isfinite(mu)))
+        if nloop > 0:
+            walls, worst = [], 0.0
+            for b in range(nloop + 1):                          # (the first problem warms up and is dropped)
+                i = b % B
+                kb = kernel_of(S0[i], w0[i], Q[i], delta)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gp = gadfly_amd.GaussianProcess(kb, t=t, yerr=30.0, device="cuda:0")
+                m1 = gp.predict(y)
+                walls.append(time.perf_counter() - t0)
+                worst = max(worst, float(np.max(np.abs(m1 - mu[i])) / np.max(np.abs(m1))))
+                del gp
+            per = float(np.median(walls[1:])) * 1e3
+            rec.update(loop_problems=nloop, loop_ms_per_problem=round(per, 2), loop_scaled_ms=round(per * B, 1),
+                       speedup_over_loop=round(per * B / rec["predict_numpy_ms"], 2),
+                       speedup_device_over_loop=round(per * B / dev, 2), worst_against_loop=float(f"{worst:.2e}"))
+        del mu
+        solve, at = [], []
+        for r in range(reps + 1):                               # (the first call warms up and is dropped)
+            out = ev.predict_device(pack, t=ts, wide=True)
+            at.append(ev.last_predict_at_ms)
+            solve.append(ev.last_predict_device_ms - at[-1])
+            del out
+        s_ms, a_ms = float(np.median(solve[1:])), float(np.median(at[1:]))
+        rec.update(M=len(ts), at_solve_device_ms=round(s_ms, 2), at_device_ms=round(a_ms, 2),
+                   at_share=round(a_ms / (a_ms + s_ms), 4))
+        if grad_reps > 0:
+            def run_grad():
+                ev.value_and_grad(S0, w0, Q, delta, wide=True)
+                return ev.last_grad_device_ms
+
+            _, g_ms = median_ms(run_grad, grad_reps)
+            rec.update(grad_device_ms=round(g_ms, 2), grad_over_solve=round(g_ms / dev, 2))
+        print(json.dumps(rec), flush=True)
+        del ev
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="a,b,c")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop", type=int, default=16)
     ap.add_argument("--at", default="", help="legs of the prediction at new times (a, b) to measure instead")
+    ap.add_argument("--wide", default="", help="shapes of the wide route (w1, w2, w3) to measure instead")
+    ap.add_argument("--grad-reps", type=int, default=3, help="value_and_grad(wide=True) calls of a wide shape (0: none)")
     args = ap.parse_args()
     rng = np.random.Generator(np.random.PCG64(2024))
+    if args.wide:
+        return wide_legs(args.wide.split(","), args.reps, args.loop, rng, args.grad_reps)
     if args.at:
         return at_legs(args.at.split(","), args.reps, rng)
     for name in args.shapes.split(","):
